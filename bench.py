@@ -73,6 +73,11 @@ def parse():
                          "7 %% faster")
     ap.add_argument('--single-device', action='store_true',
                     help="rehearsal: every rank uses cuda:0")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: its "
+                         "batch's refined parameters, cluster costs, status and counters; with N > 1 also "
+                         "the rows gathered from every rank) as DIR/<name>.npy, float64, at most 64 MB in "
+                         "all (a fixed, seeded sample of rows beyond that)")
     return ap.parse_args()
 
 
@@ -159,6 +164,29 @@ def algorithmic_flops(problem, hb, n_iter):
         sel = n == size
         by_size[int(size)] = (int(sel.sum()), float(it[sel].mean()))
     return float((flops_it * it).sum()), float((n * p * it).sum()), by_size
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT):
+    """Write every array as out_dir/<name>.npy in float64.  Beyond `limit` bytes in all, each
+    array is cut to a seeded sample of its leading dimension (indices in <name>_sample_rows.npy)."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        # each sampled row costs its bytes plus its 8-byte index in <name>_sample_rows.npy
+        frac = 0.99 * limit / (total + 8 * sum(len(a) for a in arrays.values()))
+        for k in list(arrays):
+            a = arrays[k]
+            rows = np.sort(np.random.RandomState(0).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            arrays[k] = a[rows]
+            arrays[k + '_sample_rows'] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    return {"dir": out_dir, "arrays": sorted(arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "sampled": total > limit}
 
 
 def main():
@@ -442,6 +470,13 @@ def main():
         final_gather()
     fence()                 # (--transport ipc: the rows are in rank 0's inbox once every rank's engines are done)
     elapsed = time.perf_counter() - t0
+    # what the last timed step computed, taken before anything below runs the engines again
+    last_outputs = None
+    if args.dump_outputs and rank == 0:
+        d_last = dbs[(step_no[0] - 1) % nfl]
+        last_outputs = {k: d_last.t[k].cpu().numpy() for k in ('params_out', 'cost', 'status', 'n_rounds', 'n_iter')}
+        if 'params_std' in d_last.t:
+            last_outputs['params_std'] = d_last.t['params_std'].cpu().numpy()
     # kernel durations of ONE batch running alone, default scheduling (no throughput flag):
     # HIP events recorded on the launch stream inside the library
     import copy
@@ -486,6 +521,8 @@ def main():
         for r in range(1, world):
             rows = last[r][:counts[r], 2:4]
             gather_ok = gather_ok and bool(torch.isfinite(rows).all()) and bool((rows > -20).all())
+        if last_outputs is not None:
+            last_outputs['gathered_rows'] = np.concatenate([last[r][:counts[r]].cpu().numpy() for r in range(world)])
 
     # --transport ipc: RCCL comes up only now, outside the timed region, and gathers the rows of
     # the last step once more over xGMI: what it delivers must be what the inbox holds
@@ -751,6 +788,8 @@ def main():
                 "kind": "port", "one_thread_value": base['one'][0],
                 "sample": "the full workload of one GPU (%d cluster-fits): oracle/ctr_oracle.c = "
                           "the engine's bounded LM in scalar C, OpenMP over clusters" % n_fits}
+        if last_outputs is not None:
+            result["dumped_outputs"] = dump_outputs(args.dump_outputs, last_outputs)
         print(json.dumps(result), flush=True)
     if multi:
         if use_ipc:

@@ -1,4 +1,4 @@
-"""Generate tests/golden/draw_cases.npz: features drawn by the REFERENCE's ``artificial.draw_feature``
+"""Generate tests/golden/draw_cases.npz and draw_random.npz: features drawn by the REFERENCE's ``artificial.draw_feature``
 (artificial.py:81-141, run through oracle/refshim.py:reference_draw_feature) -- what pins
 ``clustertracking_amd.artificial.draw_feature`` / ``draw_gaussian`` (the generator of every synthetic
 frame of the tests and benchmarks, restated because the reference's module does not run on NumPy 2).
@@ -48,5 +48,28 @@ def main():
     np.savez_compressed(os.path.join(HERE, 'draw_cases.npz'), **out)
 
 
+def random_cases():
+    """The seeded random features of tests/test_artificial_draw.py's second test, in its order:
+    (name, feat_func, kwargs, shape, position, size) with the image a uint8 zero frame, max_value 150."""
+    rng = np.random.RandomState(5)
+    for feat_func, kw in (('gauss', {}), ('ring', dict(thickness=0.25)), ('disc', dict(disc_size=0.4))):
+        for ndim in (2, 3):
+            shape = (36, 40) if ndim == 2 else (18, 26, 24)
+            for i in range(4):
+                pos = tuple(rng.uniform(0, np.array(shape) - 1e-9))
+                size = tuple(rng.uniform(2., 4.5, ndim))
+                yield '%s%dd_%d' % (feat_func, ndim, i), feat_func, kw, shape, pos, size
+
+
+def main_random():
+    out = {}
+    for name, feat_func, kw, shape, pos, size in random_cases():
+        out[name + '_pos'] = np.array(pos)
+        out[name + '_size'] = np.array(size)
+        out[name] = refshim.reference_draw_feature(np.zeros(shape, np.uint8), pos, size, 150, feat_func, **kw)
+    np.savez_compressed(os.path.join(HERE, 'draw_random.npz'), **out)
+
+
 if __name__ == '__main__':
     main()
+    main_random()

@@ -35,18 +35,21 @@ def test_drawn_features_equal_the_references_bit_for_bit():
 
 
 def test_against_the_reference_itself_when_it_is_here():
-    import pytest
-    import refshim
-    if not refshim.available():
-        pytest.skip("no /root/reference in this environment")
+    """Seeded random gaussian, ring and disc features, 2D / 3D, against the images the reference drew
+    for exactly these inputs (tests/golden/draw_random.npz, make_golden_draw.py:random_cases)."""
+    z = np.load(os.path.join(_cases.GOLDEN, 'draw_random.npz'))
     rng = np.random.RandomState(5)
+    n = 0
     for feat_func, kw in (('gauss', {}), ('ring', dict(thickness=0.25)), ('disc', dict(disc_size=0.4))):
         for ndim in (2, 3):
             shape = (36, 40) if ndim == 2 else (18, 26, 24)
-            for _ in range(4):
+            for i in range(4):
                 pos = tuple(rng.uniform(0, np.array(shape) - 1e-9))
                 size = tuple(rng.uniform(2., 4.5, ndim))
-                im = np.zeros(shape, np.uint8)
-                want = refshim.reference_draw_feature(im, pos, size, 150, feat_func, **kw)
-                got = artificial.draw_feature(im.copy(), pos, size, 150, feat_func, **kw)
-                assert_equal(got, want)
+                name = '%s%dd_%d' % (feat_func, ndim, i)
+                assert_equal(np.array(pos), z[name + '_pos'], err_msg=name)     # the inputs it was drawn for
+                assert_equal(np.array(size), z[name + '_size'], err_msg=name)
+                got = artificial.draw_feature(np.zeros(shape, np.uint8), pos, size, 150, feat_func, **kw)
+                assert_equal(got, z[name], err_msg=name)
+                n += 1
+    assert n == len([k for k in z.files if not k.endswith(('_pos', '_size'))]) == 24
