@@ -54,6 +54,12 @@ STATUS_TEXT = {
 }
 
 
+# ctr_cluster_kernel (include/ctrefine.h): the kernel a cluster goes to
+KBIN_SMALL1, KBIN_SMALL2, KBIN_BLOCK, KBIN_CONS, KBIN_LARGE, KBIN_TOO_LARGE = 1, 2, 3, 4, 5, 6
+KFAM_NONE, KFAM_SMALL, KFAM_GAUSS, KFAM_GAUSS_TP, KFAM_LOWPASS, KFAM_RING, KFAM_DISC, \
+    KFAM_INV_SERIES, KFAM_LARGE, KFAM_LARGE_LOWPASS = range(10)
+
+
 FLAG_THROUGHPUT = 1   # ctr_problem.flags (include/ctrefine.h): scheduling hint, results unchanged
 FLAG_ISOLATE_TAIL = 2  # only the kernel of the likely slow fits beside the main stream
 FLAG_WINDOW_FILTER = 4  # noise_size was given: the window is thresholded even with every sigma 0
@@ -83,6 +89,12 @@ class Batch(C.Structure):
         ('n_rounds', C.c_void_p), ('n_iter', C.c_void_p), ('params_std', C.c_void_p),
         ('result_rows', C.c_void_p), ('done_flag', C.c_void_p), ('done_value', C.c_int64),
     ]
+
+
+class KernelChoice(C.Structure):
+    """``ctr_kernel_choice`` (include/ctrefine.h)."""
+    _fields_ = [('bin', C.c_int32), ('family', C.c_int32), ('nt', C.c_int32),
+                ('lanes', C.c_int32), ('n_vars', C.c_int32), ('reserved0', C.c_int32)]
 
 
 class Synth(C.Structure):

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get('CTREFINE_LIB') or os.path.join(_HERE, 'csrc', 'libctr
 
 # every symbol include/ctrefine.h declares
 EXPORTS = ('ctr_abi_version', 'ctr_create', 'ctr_destroy', 'ctr_last_error',
-           'ctr_validate_problem', 'ctr_cluster_n_vars', 'ctr_refine_batch',
+           'ctr_validate_problem', 'ctr_cluster_n_vars', 'ctr_cluster_kernel', 'ctr_refine_batch',
            'ctr_plan_create', 'ctr_plan_destroy', 'ctr_refine_batch_device',
            'ctr_frame_max_device', 'ctr_synchronize', 'ctr_last_kernel_ms',
            'ctr_find_clusters', 'ctr_engine_wait_stream', 'ctr_stream_wait_engine',
@@ -79,6 +79,8 @@ def load():
         lib.ctr_validate_problem.restype = C.c_int
         lib.ctr_cluster_n_vars.argtypes = [P(_abi.Problem), C.c_int]
         lib.ctr_cluster_n_vars.restype = C.c_int
+        lib.ctr_cluster_kernel.argtypes = [P(_abi.Problem), C.c_int64, P(_abi.KernelChoice)]
+        lib.ctr_cluster_kernel.restype = C.c_int
         lib.ctr_refine_batch.argtypes = [C.c_void_p, P(_abi.Problem), P(_abi.Batch)]
         lib.ctr_refine_batch.restype = C.c_int
         lib.ctr_plan_create.argtypes = [C.c_void_p, P(_abi.Problem), C.c_int64,
@@ -122,6 +124,16 @@ def load():
             raise EngineError("libctrefine.so ABI version mismatch")
         _lib = lib
         return lib
+
+
+def cluster_kernel(problem, n_features):
+    """The kernel a cluster of ``n_features`` goes to (``ctr_cluster_kernel``, no device needed):
+    an ``_abi.KernelChoice``."""
+    out = _abi.KernelChoice()
+    rc = load().ctr_cluster_kernel(C.byref(problem), int(n_features), C.byref(out))
+    if rc != _abi.OK:
+        raise ValueError("ctr_cluster_kernel: invalid problem or n_features (%d)" % rc)
+    return out
 
 
 class Engine(object):

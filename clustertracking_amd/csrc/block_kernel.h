@@ -1633,8 +1633,10 @@ refine_block_kernel(const KArgs k) {
             converged = (last_acc && stepmax <= xtol) || fabs(pred) <= tiny;
             // converging faster than linearly and the step after this one would be below xtol:
             // finished by TAKING this step, without the pixel pass that would only confirm it
-            // (oracle solve(): fast exit)
-            if (!converged && last_acc && pred > 0. && stepmax < prev_step && isfinite(prev_step) &&
+            // (oracle solve(): fast exit).  Not when params_std is wanted: the std is built from the
+            // J^T J of the last pixel pass, which must belong to the final point (the oracle
+            // evaluates it there: solution_std)
+            if (!converged && k.params_std == nullptr && last_acc && pred > 0. && stepmax < prev_step && isfinite(prev_step) &&
                 stepmax * (stepmax / prev_step) <= xtol) {
               for (int i = lane; i < nv; i += WAVE) v[i] = vt[i];
               wsync();

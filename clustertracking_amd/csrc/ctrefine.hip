@@ -257,6 +257,85 @@ int launch_frame_max(ctr_handle* h, const void* frames, int dtype, int64_t n_fra
   return CTR_OK;
 }
 
+// a lowpass of the window (ctr_problem.noise_size / CTR_FLAG_WINDOW_FILTER; noise_size given
+// with every sigma 0: the reference's lowpass is then its threshold alone)
+bool lowpass_of(const ctr_problem* p) {
+  bool lp = (p->flags & CTR_FLAG_WINDOW_FILTER) != 0;
+  for (int a = 0; a < p->ndim; ++a) lp = lp || p->noise_size[a] > 0.;
+  return lp;
+}
+
+// The per-cluster decision of ctr_plan_create (ctr_cluster_kernel); p is validated.
+int choose_kernel(const ctr_problem* p, int64_t n, ctr_kernel_choice* out) {
+  std::memset(out, 0, sizeof *out);
+  out->n_vars = -1;
+  if (n < 0) return CTR_ERR_INVALID;
+  // singles / pairs with the default modes (fitfunc.py:356,379-387) go to the small kernel
+  bool default_modes = p->modes[0] == CTR_MODE_CLUSTER && p->modes[1] == CTR_MODE_VAR;
+  for (int a = 0; a < p->ndim; ++a) default_modes = default_modes && p->modes[2 + a] == CTR_MODE_VAR;
+  for (int k2 = 2 + p->ndim; k2 < p->n_params; ++k2) default_modes = default_modes && p->modes[k2] == CTR_MODE_CONST;
+  int npf = 0, nsh = 0;   // per-feature / shared variables
+  for (int k2 = 0; k2 < p->n_params; ++k2) {
+    if (p->modes[k2] == CTR_MODE_VAR) ++npf;
+    else if (p->modes[k2] != CTR_MODE_CONST) ++nsh;
+  }
+  const bool lowpass = lowpass_of(p);
+  // (the lowpass lives in its own instantiations of the block kernel: every cluster goes there)
+  if (lowpass) default_modes = false;
+  // (so do the ring / disc profiles; clusters beyond the block kernel get status 5 there)
+  const bool other_profile = p->fit_function != CTR_FIT_GAUSS;
+  if (other_profile) default_modes = false;
+  int bin;
+  const bool constrained = (p->constraint_kind == CTR_CONS_DIMER && n == 2);
+  const bool any_cons = (p->constraint_kind == CTR_CONS_DIMER && n == 2) ||
+                        (p->constraint_kind == CTR_CONS_TRIMER && n == 3) ||
+                        (p->constraint_kind == CTR_CONS_TETRAMER && n == 4);
+  if (n <= 0x3fffffLL) out->n_vars = n_vars(p, (int)n);
+  if (n > 0x3fffffLL) bin = BIN_TOO_LARGE;
+  else if (n > MAXF) bin = BIN_LARGE;
+  else if (default_modes && n == 1) bin = BIN_SMALL1;
+  else if (default_modes && n == 2 && !constrained) bin = BIN_SMALL2;
+  else {
+    const int nv = out->n_vars;
+    const int nt = (nv + 1 + 15) / 16;
+    bin = nt > MAXNT ? BIN_LARGE : (nt < 1 ? 0 : nt - 1);
+    if (bin < MAXNT && n > (16 * (bin + 1) < MAXF ? 16 * (bin + 1) : MAXF)) bin = BIN_LARGE;
+    if (any_cons && bin < 2) bin = bin == 0 ? BIN_CONS1 : BIN_CONS2;   // (at most 29 variables)
+    else if (any_cons && bin < MAXNT) bin = BIN_TOO_LARGE;             // (ring / disc with every column free)
+  }
+  if (bin == BIN_LARGE) {
+    // the large kernel's 16-column row: [r, shared.., own.., r_o, shared_o..]
+    bool wide_mask = false;   // (its list of mask pixels packs box coordinates in 10 bits per axis)
+    for (int a = 0; a < p->ndim; ++a) wide_mask = wide_mask || p->radius[a] > 500;
+    if (npf < 1 || 2 + 2 * nsh + npf > 16 || other_profile || wide_mask) bin = BIN_TOO_LARGE;
+  }
+  // which table the kernel comes from (ctr_refine_batch_device)
+  int fam = CTR_KFAM_NONE;
+  if (bin == BIN_SMALL1 || bin == BIN_SMALL2) fam = CTR_KFAM_SMALL;
+  else if (bin == BIN_LARGE) fam = lowpass ? CTR_KFAM_LARGE_LOWPASS : CTR_KFAM_LARGE;
+  else if (bin != BIN_TOO_LARGE) {
+    if (p->fit_function == CTR_FIT_RING) fam = CTR_KFAM_RING;
+    else if (p->fit_function == CTR_FIT_DISC) fam = CTR_KFAM_DISC;
+    else if (p->fit_function == CTR_FIT_INV_SERIES) fam = CTR_KFAM_INV_SERIES;
+    else if (lowpass) fam = CTR_KFAM_LOWPASS;
+    // (2D only: a 3D window has thousands of pixels, more wavefronts per cluster pay there)
+    else if ((p->flags & CTR_FLAG_THROUGHPUT) != 0 && p->ndim == 2) fam = CTR_KFAM_GAUSS_TP;
+    else fam = CTR_KFAM_GAUSS;
+  }
+  out->family = fam;
+  if (bin < MAXNT) { out->bin = CTR_KBIN_BLOCK; out->nt = bin + 1; }
+  else if (bin == BIN_CONS1 || bin == BIN_CONS2) { out->bin = CTR_KBIN_CONS; out->nt = bin == BIN_CONS1 ? 1 : 2; }
+  else if (bin == BIN_SMALL1 || bin == BIN_SMALL2) {
+    out->bin = bin == BIN_SMALL1 ? CTR_KBIN_SMALL1 : CTR_KBIN_SMALL2;
+    // lanes per cluster by the size of a single-feature window (ctr_refine_batch_device)
+    int64_t vol = 1;
+    for (int a = 0; a < p->ndim; ++a) vol *= 2 * (int64_t)p->radius[a] + 1;
+    out->lanes = bin == BIN_SMALL2 || vol > 600 ? 64 : 8;
+  }
+  else out->bin = bin == BIN_LARGE ? CTR_KBIN_LARGE : CTR_KBIN_TOO_LARGE;
+  return CTR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -278,6 +357,13 @@ int ctr_validate_problem(const ctr_problem* p, char* msg, int msg_len) {
 }
 
 int ctr_cluster_n_vars(const ctr_problem* p, int n_features) { return p ? n_vars(p, n_features) : -1; }
+
+int ctr_cluster_kernel(const ctr_problem* p, int64_t n_features, ctr_kernel_choice* out) {
+  if (!out) return CTR_ERR_INVALID;
+  std::string msg;
+  if (validate(p, msg)) { std::memset(out, 0, sizeof *out); out->n_vars = -1; return CTR_ERR_INVALID; }
+  return choose_kernel(p, n_features, out);
+}
 
 int ctr_create(ctr_handle** out, int device) {
   if (!out) return fail(nullptr, CTR_ERR_INVALID, "null out pointer");
@@ -370,56 +456,34 @@ int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
   plan->prob = *p;
   plan->n_clusters = n_clusters;
   plan->device = h->device;
-  // singles / pairs with the default modes (fitfunc.py:356,379-387) go to the small kernel
-  bool default_modes = p->modes[0] == CTR_MODE_CLUSTER && p->modes[1] == CTR_MODE_VAR;
-  for (int a = 0; a < p->ndim; ++a) default_modes = default_modes && p->modes[2 + a] == CTR_MODE_VAR;
-  for (int k2 = 2 + p->ndim; k2 < p->n_params; ++k2) default_modes = default_modes && p->modes[k2] == CTR_MODE_CONST;
+  // (the lowpass lives in its own instantiations of the block kernel: ctr_cluster_kernel)
+  plan->lowpass = lowpass_of(p);
+  std::vector<long long> ws_off((size_t)n_clusters, 0);
+  long long ws_total = 0;
+  long long box_cap = 1;     // pixels of a mask's bounding box (large_ws)
+  for (int a = 0; a < p->ndim; ++a) box_cap *= 2 * (long long)p->radius[a] + 1;
   int npf = 0, nsh = 0;   // per-feature / shared variables
   for (int k2 = 0; k2 < p->n_params; ++k2) {
     if (p->modes[k2] == CTR_MODE_VAR) ++npf;
     else if (p->modes[k2] != CTR_MODE_CONST) ++nsh;
   }
-  // (noise_size given with every sigma 0: the reference's lowpass is then its threshold alone)
-  plan->lowpass = (p->flags & CTR_FLAG_WINDOW_FILTER) != 0;
-  for (int a = 0; a < p->ndim; ++a) plan->lowpass = plan->lowpass || p->noise_size[a] > 0.;
-  // (the lowpass lives in its own instantiations of the block kernel: every cluster goes there)
-  if (plan->lowpass) default_modes = false;
-  // (so do the ring / disc profiles; clusters beyond the block kernel get status 5 there)
-  const bool other_profile = p->fit_function != CTR_FIT_GAUSS;
-  if (other_profile) default_modes = false;
-  std::vector<long long> ws_off((size_t)n_clusters, 0);
-  long long ws_total = 0;
-  long long box_cap = 1;     // pixels of a mask's bounding box (large_ws)
-  for (int a = 0; a < p->ndim; ++a) box_cap *= 2 * (long long)p->radius[a] + 1;
   for (int64_t c = 0; c < n_clusters; ++c) {
     const int64_t n = (int64_t)feat_offset_host[c + 1] - feat_offset_host[c];
     if (n < 0) { delete plan; return fail(h, CTR_ERR_INVALID, "feat_offset must be non-decreasing"); }
-    int bin;
-    const bool constrained = (p->constraint_kind == CTR_CONS_DIMER && n == 2);
-    const bool any_cons = (p->constraint_kind == CTR_CONS_DIMER && n == 2) ||
-                          (p->constraint_kind == CTR_CONS_TRIMER && n == 3) ||
-                          (p->constraint_kind == CTR_CONS_TETRAMER && n == 4);
-    if (n > 0x3fffffLL) bin = BIN_TOO_LARGE;
-    else if (n > MAXF) bin = BIN_LARGE;
-    else if (default_modes && n == 1) bin = BIN_SMALL1;
-    else if (default_modes && n == 2 && !constrained) bin = BIN_SMALL2;
-    else {
-      const int nv = n_vars(p, (int)n);
-      const int nt = (nv + 1 + 15) / 16;
-      bin = nt > MAXNT ? BIN_LARGE : (nt < 1 ? 0 : nt - 1);
-      if (bin < MAXNT && n > (16 * (bin + 1) < MAXF ? 16 * (bin + 1) : MAXF)) bin = BIN_LARGE;
-      if (any_cons && bin < 2) bin = bin == 0 ? BIN_CONS1 : BIN_CONS2;   // (at most 29 variables)
-      else if (any_cons && bin < MAXNT) bin = BIN_TOO_LARGE;             // (ring / disc with every column free)
+    ctr_kernel_choice kc;
+    (void)choose_kernel(p, n, &kc);
+    int bin = BIN_TOO_LARGE;
+    switch (kc.bin) {
+      case CTR_KBIN_SMALL1: bin = BIN_SMALL1; break;
+      case CTR_KBIN_SMALL2: bin = BIN_SMALL2; break;
+      case CTR_KBIN_BLOCK: bin = kc.nt - 1; break;
+      case CTR_KBIN_CONS: bin = kc.nt == 1 ? BIN_CONS1 : BIN_CONS2; break;
+      case CTR_KBIN_LARGE: bin = BIN_LARGE; break;
+      default: break;
     }
     if (bin == BIN_LARGE) {
-      // the large kernel's 16-column row: [r, shared.., own.., r_o, shared_o..]
-      bool wide_mask = false;   // (its list of mask pixels packs box coordinates in 10 bits per axis)
-      for (int a = 0; a < p->ndim; ++a) wide_mask = wide_mask || p->radius[a] > 500;
-      if (npf < 1 || 2 + 2 * nsh + npf > 16 || other_profile || wide_mask) bin = BIN_TOO_LARGE;
-      else {
-        ws_off[(size_t)c] = ws_total;
-        ws_total += large_ws((int)n, npf, nsh, box_cap).total;
-      }
+      ws_off[(size_t)c] = ws_total;
+      ws_total += large_ws((int)n, npf, nsh, box_cap).total;
     }
     bin_of[(size_t)c] = bin;
     plan->bin_count[bin]++;

@@ -202,6 +202,37 @@ int ctr_validate_problem(const ctr_problem* p, char* msg, int msg_len);
  * (vect_from_params layout, fitfunc.py:207-263, groups=None). */
 int ctr_cluster_n_vars(const ctr_problem* p, int n_features);
 
+/* Which kernel a cluster of n_features goes to (the per-cluster decision of ctr_plan_create,
+ * which calls this function); needs no device.  Added in ABI 7 without a version change: it
+ * changes no existing struct or call.
+ *   bin     CTR_KBIN_*: small kernel (singles / pairs with the default parameter modes), block
+ *           kernel by nt, the block kernel's constrained instantiations (dimer / trimer / tetramer
+ *           clusters, nt 1..2), large-cluster kernel, or beyond the engine (status 5)
+ *   family  CTR_KFAM_*: which table of instantiations the kernel is taken from.  Constrained
+ *           clusters take the constrained entry of that table.  GAUSS_TP (CTR_FLAG_THROUGHPUT)
+ *           exists in 2D only: a 3D problem with the flag takes the GAUSS table
+ *   nt      block and constrained bins: tiles of 16 columns (variables + 1), else 0
+ *   lanes   small kernel: lanes per cluster -- singles 8, or 64 when the window of one feature
+ *           has more than 600 pixels; pairs 64.  (With CTR_FLAG_THROUGHPUT, a bin of >= 64 pairs
+ *           and windows of <= 600 pixels, the pairs that are not closer than a quarter of the mask
+ *           radius run 16 lanes each instead: decided on the device per batch.)  Else 0
+ *   n_vars  optimiser variables (ctr_cluster_n_vars); -1 when n_features is beyond the engine
+ * Returns CTR_ERR_INVALID for a malformed problem or a negative n_features. */
+enum { CTR_KBIN_SMALL1 = 1, CTR_KBIN_SMALL2 = 2, CTR_KBIN_BLOCK = 3, CTR_KBIN_CONS = 4,
+       CTR_KBIN_LARGE = 5, CTR_KBIN_TOO_LARGE = 6 };
+enum { CTR_KFAM_NONE = 0, CTR_KFAM_SMALL = 1, CTR_KFAM_GAUSS = 2, CTR_KFAM_GAUSS_TP = 3,
+       CTR_KFAM_LOWPASS = 4, CTR_KFAM_RING = 5, CTR_KFAM_DISC = 6, CTR_KFAM_INV_SERIES = 7,
+       CTR_KFAM_LARGE = 8, CTR_KFAM_LARGE_LOWPASS = 9 };
+typedef struct ctr_kernel_choice {
+  int32_t bin;     /* CTR_KBIN_* */
+  int32_t family;  /* CTR_KFAM_*; NONE for CTR_KBIN_TOO_LARGE */
+  int32_t nt;
+  int32_t lanes;
+  int32_t n_vars;
+  int32_t reserved0;
+} ctr_kernel_choice;
+int ctr_cluster_kernel(const ctr_problem* p, int64_t n_features, ctr_kernel_choice* out);
+
 /* Host-pointer entry: copies the batch to the device, runs it, copies the
  * results back.  Synchronous.  Replaces refine.py:343-430. */
 int ctr_refine_batch(ctr_handle* h, const ctr_problem* p, const ctr_batch* b);
@@ -210,7 +241,14 @@ int ctr_refine_batch(ctr_handle* h, const ctr_problem* p, const ctr_batch* b);
  * GPU): a plan bins the clusters of a batch by problem size on the host once (and owns the
  * HBM workspace of its large clusters: use a plan with the handle it was created on);
  * the run is asynchronous on the given HIP stream (hipStream_t passed as
- * void*; NULL = the handle's own stream). */
+ * void*; NULL = the handle's own stream).
+ * Measurement-only switches, read from the environment on every ctr_refine_batch_device call;
+ * leave them unset in production:
+ *   CTR_LARGE_CG_TOL2="far,near"  squared relative residual tolerances of the large-cluster
+ *                                 kernel's conjugate-gradient solve, far from / near the solution
+ *                                 (default 1e-12,1e-22).  CHANGES RESULTS:
+ *                                 1e-8 for far gives about 6e-7 px against the oracle instead of 5e-8
+ *   CTR_LARGE_WORKGROUPS=<1..16>  workgroups per large cluster (leader included); scheduling only */
 int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
                     const int32_t* feat_offset_host, ctr_plan** out);
 void ctr_plan_destroy(ctr_plan* plan);

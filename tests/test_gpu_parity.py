@@ -482,7 +482,7 @@ def test_refine_with_device_labels_matches_reference_labels(engine):
         assert_equal(r_ref[col].values, r_dev[col].values)
 
 
-# ---- randomized configurations: every kernel variant against the oracle ------------------
+# ---- randomized configurations (Gaussians, no lowpass) against the oracle; every kernel cell: test_gpu_dispatch_matrix.py
 
 _random_case = _cases.random_case
 
