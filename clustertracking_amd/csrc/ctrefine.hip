@@ -38,9 +38,6 @@ namespace {
 
 // ---- host side ------------------------------------------------------------------------
 
-typedef const void* kernel_fn;   // a kernel of another translation unit (kargs.h)
-typedef const void* small_fn;
-
 std::string g_create_error;
 std::mutex g_mutex;
 
@@ -54,6 +51,10 @@ std::mutex g_mutex;
 constexpr int BIN_TOO_LARGE = MAXNT, BIN_SMALL1 = MAXNT + 1, BIN_SMALL2 = MAXNT + 2, BIN_LARGE = MAXNT + 3,
               BIN_CONS1 = MAXNT + 4, BIN_CONS2 = MAXNT + 5, NBINS = MAXNT + 6;
 static_assert(NBINS <= 16, "FrontArgs (aux_kernels.h) holds 16 bins");
+// slots of the handle's kernel table (ctr_handle::kernels): a block family's NT 1..8 at nt - 1 and
+// its constrained NT 1..2 at MAXNT + nt - 1; the small kernel's tiers; the large kernel's one at 0
+constexpr int NFAM = CTR_KFAM_LARGE_LOWPASS + 1, NSLOT = MAXNT + 2;
+constexpr int SLOT_SINGLES8 = 0, SLOT_SINGLES64 = 1, SLOT_PAIRS64 = 2, SLOT_PAIRS16 = 3;
 // side streams for concurrent bin launches.  Three, not more: HIP deals streams to the hardware
 // queues round robin, and with 1 + 3 streams per handle and a queue count that is a multiple of 4
 // the streams that share a queue have the same role in different handles; eight handles in flight
@@ -75,6 +76,9 @@ struct ctr_plan {
   mutable int large_epoch = 0;     // launches of the large kernel on this plan (tags its leader / helper words)
   int64_t bin_begin[NBINS + 1] = {0};
   int64_t bin_count[NBINS] = {0};
+  // choose_kernel's family and singles lanes of each bin (the same for every cluster of a bin)
+  int32_t bin_family[NBINS] = {0};
+  int32_t bin_lanes[NBINS] = {0};
   // lowpass of the window (ctr_problem.noise_size): taps per axis on the device (kargs.h: lp_w)
   bool lowpass = false;
   double* d_lp_w = nullptr;
@@ -93,29 +97,9 @@ struct ctr_handle {
   unsigned long long* d_enc = nullptr;
   double* d_fmax = nullptr;
   int64_t fmax_cap = 0;
-  kernel_fn table[2][2][MAXNT];
-  size_t smem_bytes[2][2][MAXNT];
-  int block_threads[2][2][MAXNT];
-  bool attr_set[2][2][MAXNT] = {};
-  KernelInfo cons[2][2][2][2];       // [ndim-2][iso][throughput][nt-1]: constrained clusters
-  bool cons_attr[2][2][2][2] = {};
-  kernel_fn table_tp[2][2][MAXNT];   // the same for CTR_FLAG_THROUGHPUT (fewest wavefronts)
-  size_t smem_bytes_tp[2][2][MAXNT];
-  int block_threads_tp[2][2][MAXNT];
-  bool attr_set_tp[2][2][MAXNT] = {};
-  small_fn small_table[2][2][2];  // [ndim-2][iso][nf-1]; singles with 8 lanes per cluster (eight per wavefront)
-  small_fn small_wide1[2][2];     // singles with 64 lanes per cluster (large windows)
-  small_fn small_bulk2[2][2];     // pairs with 16 lanes per cluster (the bulk of a pairs bin)
-  KernelInfo lp[2][2][MAXNT];     // block kernel with the lowpass of the window: [ndim-2][iso][nt-1]
-  KernelInfo lp_cons[2][2][2];    // ... for constrained clusters, nt = 1, 2
-  KernelInfo fit[3][2][2][MAXNT]; // ring / disc / inv_series profiles: [fit-1][ndim-2][iso][nt-1]
-  KernelInfo fit_cons[3][2][2][2];
-  bool fit_attr[3][2][2][MAXNT] = {};
-  bool fit_cons_attr[3][2][2][2] = {};
-  bool lp_attr[2][2][MAXNT] = {};
-  bool lp_cons_attr[2][2][2] = {};
-  KernelInfo large[2][2][2];      // refine_large_kernel<ndim, iso, lowpass>
-  bool large_attr[2][2][2] = {};
+  // the kernel of every cell of the dispatch: [CTR_KFAM_*][ndim-2][iso][slot] (kernel_of); an
+  // unreachable cell is null.  attr_set: its dynamic LDS limit is set (table_kernel)
+  struct { KernelInfo k; bool attr_set; } kernels[NFAM][2][2][NSLOT] = {};
   hipEvent_t ev_done = nullptr;   // end of the last ctr_refine_batch_device call of this handle
   hipStream_t side[NSIDE] = {};
   hipEvent_t ev_fork = nullptr, ev_gate = nullptr, ev_order = nullptr, ev_join[NSIDE] = {};
@@ -336,6 +320,43 @@ int choose_kernel(const ctr_problem* p, int64_t n, ctr_kernel_choice* out) {
   return CTR_OK;
 }
 
+// The instantiation of one cell of the kernel table (ctr_create); {nullptr} where there is none.
+KernelInfo kernel_of(int fam, int ndim, int iso, int slot) {
+  const KernelInfo none{nullptr, 0, 0};
+  if (fam == CTR_KFAM_NONE) return none;
+  if (fam == CTR_KFAM_SMALL) {
+    static const int tier[4][2] = {{1, 8}, {1, 64}, {2, 64}, {2, 16}};   // (features, lanes) by slot
+    if (slot > SLOT_PAIRS16) return none;
+    return KernelInfo{ctr_small_kernel(ndim, tier[slot][0], iso, tier[slot][1]), 0, WAVE};
+  }
+  if (fam == CTR_KFAM_LARGE || fam == CTR_KFAM_LARGE_LOWPASS)
+    return slot == 0 ? ctr_large_kernel(ndim, iso, fam == CTR_KFAM_LARGE_LOWPASS) : none;
+  typedef KernelInfo (*block_unit)(int, int, int, int, int);
+  static const block_unit units[] = {ctr_block_kernel_2d, ctr_block_kernel_3d, ctr_block_kernel_lp,
+                                     ctr_block_kernel_fit2d, ctr_block_kernel_fit3d, ctr_block_kernel_inv};
+  for (block_unit unit : units) {
+    const KernelInfo k = unit(fam, ndim, iso, slot % MAXNT + 1, slot >= MAXNT);
+    if (k.fn) return k;
+  }
+  return none;
+}
+
+// The kernel of a cell, its dynamic LDS limit set the first time it is launched.  A cell without
+// an instantiation is an error (the plan's decision and the table disagree), never a launch.
+int table_kernel(ctr_handle* h, int fam, int ndim, int iso, int slot, const KernelInfo** out) {
+  auto& e = h->kernels[fam][ndim - 2][iso][slot];
+  if (!e.k.fn)
+    return fail(h, CTR_ERR_DEVICE, "no kernel instantiated for family " + std::to_string(fam) + ", " +
+                                       std::to_string(ndim) + "D, iso " + std::to_string(iso) + ", slot " + std::to_string(slot));
+  if (!e.attr_set) {
+    if (e.k.smem > 0)   // (the small kernels have no dynamic LDS)
+      HIP_TRY(h, hipFuncSetAttribute(e.k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.k.smem));
+    e.attr_set = true;
+  }
+  *out = &e.k;
+  return CTR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -393,32 +414,10 @@ int ctr_create(ctr_handle** out, int device) {
   for (auto& ev : h->ev_join) evok = evok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
   evok = evok && hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) == hipSuccess;
   if (!evok || hipMalloc((void**)&h->d_counter, sizeof(int) * 8) != hipSuccess) { delete h; return fail(nullptr, CTR_ERR_DEVICE, "cannot create events / counters"); }
-  for (int di = 0; di < 2; ++di)
-    for (int ii = 0; ii < 2; ++ii) {
-      h->small_wide1[di][ii] = ctr_small_kernel(2 + di, 1, ii, 64);
-      h->small_bulk2[di][ii] = ctr_small_kernel(2 + di, 2, ii, 16);
-      h->small_table[di][ii][0] = ctr_small_kernel(2 + di, 1, ii, 8);
-      h->small_table[di][ii][1] = ctr_small_kernel(2 + di, 2, ii, 64);
-      h->large[di][ii][0] = ctr_large_kernel(2 + di, ii, 0);
-      h->large[di][ii][1] = ctr_large_kernel(2 + di, ii, 1);
-      for (int nt = 1; nt <= MAXNT; ++nt) {
-        const KernelInfo a = di == 0 ? ctr_block_kernel_2d(ii, nt, 0, 0) : ctr_block_kernel_3d(ii, nt, 0, 0);
-        const KernelInfo t = di == 0 ? ctr_block_kernel_2d(ii, nt, 1, 0) : ctr_block_kernel_3d(ii, nt, 1, 0);
-        h->lp[di][ii][nt - 1] = ctr_block_kernel_lp(2 + di, ii, nt, 0);
-        if (nt <= 2) h->lp_cons[di][ii][nt - 1] = ctr_block_kernel_lp(2 + di, ii, nt, 1);
-        for (int fi = 0; fi < 2; ++fi) {
-          h->fit[fi][di][ii][nt - 1] = di == 0 ? ctr_block_kernel_fit2d(ii, nt, 0, fi + 1) : ctr_block_kernel_fit3d(ii, nt, 0, fi + 1);
-          if (nt <= 2) h->fit_cons[fi][di][ii][nt - 1] = di == 0 ? ctr_block_kernel_fit2d(ii, nt, 1, fi + 1) : ctr_block_kernel_fit3d(ii, nt, 1, fi + 1);
-        }
-        h->fit[2][di][ii][nt - 1] = ctr_block_kernel_inv(2 + di, ii, nt, 0);
-        if (nt <= 2) h->fit_cons[2][di][ii][nt - 1] = ctr_block_kernel_inv(2 + di, ii, nt, 1);
-        if (nt <= 2)
-          for (int tp = 0; tp < 2; ++tp)
-            h->cons[di][ii][tp][nt - 1] = di == 0 ? ctr_block_kernel_2d(ii, nt, tp, 1) : ctr_block_kernel_3d(ii, nt, tp, 1);
-        h->table[di][ii][nt - 1] = a.fn; h->smem_bytes[di][ii][nt - 1] = a.smem; h->block_threads[di][ii][nt - 1] = a.threads;
-        h->table_tp[di][ii][nt - 1] = t.fn; h->smem_bytes_tp[di][ii][nt - 1] = t.smem; h->block_threads_tp[di][ii][nt - 1] = t.threads;
-      }
-    }
+  for (int fam = 0; fam < NFAM; ++fam)
+    for (int di = 0; di < 2; ++di)
+      for (int ii = 0; ii < 2; ++ii)
+        for (int slot = 0; slot < NSLOT; ++slot) h->kernels[fam][di][ii][slot].k = kernel_of(fam, 2 + di, ii, slot);
   *out = h;
   return CTR_OK;
 }
@@ -484,6 +483,12 @@ int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
     if (bin == BIN_LARGE) {
       ws_off[(size_t)c] = ws_total;
       ws_total += large_ws((int)n, npf, nsh, box_cap).total;
+    }
+    // (family and lanes depend on the problem alone: the launch takes them from the plan)
+    if (plan->bin_count[bin] == 0) { plan->bin_family[bin] = kc.family; plan->bin_lanes[bin] = kc.lanes; }
+    else if (plan->bin_family[bin] != kc.family || plan->bin_lanes[bin] != kc.lanes) {
+      delete plan;
+      return fail(h, CTR_ERR_INVALID, "internal: clusters of one bin with different kernels");
     }
     bin_of[(size_t)c] = bin;
     plan->bin_count[bin]++;
@@ -610,7 +615,7 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     if (std::sscanf(e, "%lf,%lf", &a, &b) == 2 && a > 0. && b > 0.) { k.cg_tol2_far = a; k.cg_tol2_near = b; }
   }
   for (int a = 0; a < 3; ++a) k.lp_half[a] = plan->lp_half[a];
-  const int di = p.ndim == 3 ? 1 : 0, ii = p.isotropic ? 1 : 0;
+  const int ii = p.isotropic ? 1 : 0;
   // The bins are independent: the big bin of singles runs on the caller's
   // stream, the others on side streams forked from / joined to it by events, so
   // that a few slow many-feature clusters overlap with the bulk.
@@ -649,56 +654,27 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     if (!used[j]) { used[j] = true; (void)hipStreamWaitEvent(h->side[j], h->ev_fork, 0); }
     return h->side[j];
   };
-  // generic bins first (largest problems first) so that their tails start early
-  for (int bin = MAXNT - 1; bin >= 0; --bin) {
+  // block bins first, largest problems first (NT 8 -> 1, then the constrained NT 2 -> 1) so that
+  // their tails start early
+  for (int i = 0; i < MAXNT + 2; ++i) {
+    const int bin = i < MAXNT ? MAXNT - 1 - i : (i == MAXNT ? BIN_CONS2 : BIN_CONS1);
     const int64_t cnt = plan->bin_count[bin];
     if (cnt == 0) continue;
-    // (2D only: a 3D window has thousands of pixels, more wavefronts per cluster pay there)
-    const bool tp = (p.flags & CTR_FLAG_THROUGHPUT) != 0 && p.ndim == 2;
-    const bool lpk = plan->lowpass;
-    const int fi = p.fit_function - 1;   // >= 0: ring / disc / inv_series
-    kernel_fn fn = fi >= 0 ? h->fit[fi][di][ii][bin].fn : lpk ? h->lp[di][ii][bin].fn : (tp ? h->table_tp[di][ii][bin] : h->table[di][ii][bin]);
-    const size_t bytes = fi >= 0 ? h->fit[fi][di][ii][bin].smem : lpk ? h->lp[di][ii][bin].smem : (tp ? h->smem_bytes_tp[di][ii][bin] : h->smem_bytes[di][ii][bin]);
-    const int threads = fi >= 0 ? h->fit[fi][di][ii][bin].threads : lpk ? h->lp[di][ii][bin].threads : (tp ? h->block_threads_tp[di][ii][bin] : h->block_threads[di][ii][bin]);
-    bool& attr = fi >= 0 ? h->fit_attr[fi][di][ii][bin] : lpk ? h->lp_attr[di][ii][bin] : (tp ? h->attr_set_tp[di][ii][bin] : h->attr_set[di][ii][bin]);
-    if (!attr) {
-      HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-      attr = true;
-    }
-    k.order = ord + plan->bin_begin[bin];
-    k.n_bin = (int32_t)cnt;
-    {
-      void* kargs[] = {(void*)&k};
-      HIP_TRY(h, hipLaunchKernel(fn, dim3((unsigned)cnt), dim3((unsigned)threads), kargs, bytes, pick_stream(false)));
-    }
-  }
-  for (int cb = 1; cb >= 0; --cb) {
-    const int bin = cb == 0 ? BIN_CONS1 : BIN_CONS2;
-    const int64_t cnt = plan->bin_count[bin];
-    if (cnt == 0) continue;
-    const int tp = ((p.flags & CTR_FLAG_THROUGHPUT) != 0 && p.ndim == 2) ? 1 : 0;
-    const int fi = p.fit_function - 1;   // >= 0: ring / disc / inv_series
-    const KernelInfo& ki = fi >= 0 ? h->fit_cons[fi][di][ii][cb] : plan->lowpass ? h->lp_cons[di][ii][cb] : h->cons[di][ii][tp][cb];
-    bool& cattr = fi >= 0 ? h->fit_cons_attr[fi][di][ii][cb] : plan->lowpass ? h->lp_cons_attr[di][ii][cb] : h->cons_attr[di][ii][tp][cb];
-    if (!cattr) {
-      HIP_TRY(h, hipFuncSetAttribute(ki.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ki.smem));
-      cattr = true;
-    }
+    const KernelInfo* ki;
+    rc = table_kernel(h, plan->bin_family[bin], p.ndim, ii, i < MAXNT ? bin : MAXNT + (bin == BIN_CONS2), &ki);
+    if (rc) return rc;
     k.order = ord + plan->bin_begin[bin];
     k.n_bin = (int32_t)cnt;
     void* kargs[] = {(void*)&k};
-    HIP_TRY(h, hipLaunchKernel(ki.fn, dim3((unsigned)cnt), dim3((unsigned)ki.threads), kargs, ki.smem, pick_stream(false)));
+    HIP_TRY(h, hipLaunchKernel(ki->fn, dim3((unsigned)cnt), dim3((unsigned)ki->threads), kargs, ki->smem, pick_stream(false)));
   }
   if (plan->bin_count[BIN_LARGE] > 0) {
     // a leader workgroup of 512 threads per cluster + helpers for its pixel passes
     // (large_kernel.h): as many as fill the machine, none when the clusters alone do
     const int64_t cnt = plan->bin_count[BIN_LARGE];
-    const int lpi = plan->lowpass ? 1 : 0;
-    const KernelInfo& ki = h->large[di][ii][lpi];
-    if (!h->large_attr[di][ii][lpi]) {
-      HIP_TRY(h, hipFuncSetAttribute(ki.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ki.smem));
-      h->large_attr[di][ii][lpi] = true;
-    }
+    const KernelInfo* ki;
+    rc = table_kernel(h, plan->bin_family[BIN_LARGE], p.ndim, ii, 0, &ki);
+    if (rc) return rc;
     int64_t per_cluster = 512 / cnt;               // workgroups per cluster, leader included
     per_cluster = per_cluster < 1 ? 1 : (per_cluster > 8 ? 8 : per_cluster);
     // (several batches in flight fill the machine by themselves: a waiting helper would only hold
@@ -717,7 +693,7 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     slow_tier = true;
     hipStream_t sl = pick_stream(false);
     slow_tier = false;
-    HIP_TRY(h, hipLaunchKernel(ki.fn, dim3((unsigned)(cnt * per_cluster)), dim3((unsigned)ki.threads), kargs, ki.smem, sl));
+    HIP_TRY(h, hipLaunchKernel(ki->fn, dim3((unsigned)(cnt * per_cluster)), dim3((unsigned)ki->threads), kargs, ki->smem, sl));
   }
   if (plan->bin_count[BIN_TOO_LARGE] > 0) {
     const int64_t cnt = plan->bin_count[BIN_TOO_LARGE];
@@ -738,6 +714,13 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     const int bin = nf == 1 ? BIN_SMALL1 : BIN_SMALL2;
     const int64_t cnt = plan->bin_count[bin];
     if (cnt == 0) continue;
+    // lanes per cluster (choose_kernel): singles 8 (eight clusters per wavefront: the solve,
+    // replicated in the lanes of a group, is shared by as many) while a window is a few passes,
+    // 64 once it is thousands of pixels (3D); pairs 64
+    const bool wide = plan->bin_lanes[bin] == 64;
+    const KernelInfo* ki;
+    rc = table_kernel(h, plan->bin_family[bin], p.ndim, ii, nf == 2 ? SLOT_PAIRS64 : (wide ? SLOT_SINGLES64 : SLOT_SINGLES8), &ki);
+    if (rc) return rc;
     slow_tier = nf == 2;
     hipStream_t st = pick_stream(nf == 1);
     slow_tier = false;
@@ -745,13 +728,8 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     int* counter = h->d_counter + nf;
     k.order = ord + plan->bin_begin[bin];
     k.n_bin = (int32_t)cnt;
-    // lanes per cluster by the size of a single-feature window: 8 (eight clusters per
-    // wavefront: the solve, replicated in the lanes of a group, is shared by as many) while
-    // a window is a few passes, 64 once it is thousands of pixels (3D)
-    int64_t vol = 1;
+    int64_t vol = 1;   // (pixels of a single-feature window)
     for (int a = 0; a < p.ndim; ++a) vol *= 2 * (int64_t)p.radius[a] + 1;
-    const bool wide = nf == 2 || vol > 600;
-    small_fn fn = nf == 2 ? h->small_table[di][ii][1] : (wide ? h->small_wide1[di][ii] : h->small_table[di][ii][0]);
     int64_t waves = wide ? cnt : (cnt + 7) / 8;
     if (nf == 2 && vol <= 600 && cnt >= 64 && (p.flags & CTR_FLAG_THROUGHPUT) != 0) {
       // Pairs in two tiers (CTR_FLAG_THROUGHPUT: +9 % with four batches in flight, but the
@@ -761,6 +739,9 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
       // radius first and counted them (on the device): the 64-lane kernel takes exactly
       // those, the 16-lane kernel, on a stream of its own, the others -- which kernel fits a
       // pair depends on the pair alone, not on the order of the batch.
+      const KernelInfo* kb;
+      rc = table_kernel(h, plan->bin_family[bin], p.ndim, ii, SLOT_PAIRS16, &kb);
+      if (rc) return rc;
       k.split = plan->d_front + 2 * bin;
       hipStream_t sb = pick_stream(false);
       if (gate) (void)hipStreamWaitEvent(sb, h->ev_gate, 0);
@@ -773,7 +754,7 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
       if (wb > 8192) wb = 8192;
       {
         void* kargs[] = {(void*)&k, (void*)&cbulk};
-        HIP_TRY(h, hipLaunchKernel(h->small_bulk2[di][ii], dim3((unsigned)wb), dim3(WAVE), kargs, 0, sb));
+        HIP_TRY(h, hipLaunchKernel(kb->fn, dim3((unsigned)wb), dim3(WAVE), kargs, 0, sb));
       }
       k.split_part = 1;
       if (waves > 2048) waves = 2048;   // persistent: a wavefront takes pair after pair
@@ -781,7 +762,7 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     if (waves > 8192) waves = 8192;
     {
       void* kargs[] = {(void*)&k, (void*)&counter};
-      HIP_TRY(h, hipLaunchKernel(fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st));
+      HIP_TRY(h, hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st));
     }
     k.split = nullptr;
     k.split_part = 0;

@@ -106,16 +106,15 @@ __host__ __device__ inline LargeWs large_ws(int n, int npf, int ns, long long ca
 
 // refine_large_kernel<ND, ISO>(KArgs, double* ws, const long long* ws_off_of_cluster, int epoch):
 // grid = n_bin leaders + n_bin * (G - 1) helpers (large_kernel.h)
-// refine_block_kernel<ND, ISO, NT, W, CONS>: nt = 1..8; throughput != 0: the fewest wavefronts;
-// cons != 0: the instantiation for clusters with equality constraints (nt = 1, 2 only)
-KernelInfo ctr_block_kernel_2d(int iso, int nt, int throughput, int cons);
-KernelInfo ctr_block_kernel_3d(int iso, int nt, int throughput, int cons);
-// the same with the lowpass of the window (LP = true); one instantiation per (ndim, iso, nt, cons)
-KernelInfo ctr_block_kernel_lp(int ndim, int iso, int nt, int cons);
-// ring / disc profiles (FIT = CTR_FIT_RING / CTR_FIT_DISC); cons: nt = 1..3
-KernelInfo ctr_block_kernel_fit2d(int iso, int nt, int cons, int fit);
-KernelInfo ctr_block_kernel_fit3d(int iso, int nt, int cons, int fit);
-KernelInfo ctr_block_kernel_inv(int ndim, int iso, int nt, int cons);   // FIT = CTR_FIT_INV_SERIES
+// refine_block_kernel<ND, ISO, NT, W, CONS, LP, FIT> of one cell of a block family
+// (CTR_KFAM_*; block_table.h): nt = 1..8; cons != 0: the instantiation for clusters with equality
+// constraints (nt = 1, 2 only).  {nullptr} for a cell the unit does not hold.
+KernelInfo ctr_block_kernel_2d(int family, int ndim, int iso, int nt, int cons);     // GAUSS, GAUSS_TP; 2D
+KernelInfo ctr_block_kernel_3d(int family, int ndim, int iso, int nt, int cons);     // GAUSS; 3D
+KernelInfo ctr_block_kernel_lp(int family, int ndim, int iso, int nt, int cons);     // LOWPASS (LP = true)
+KernelInfo ctr_block_kernel_fit2d(int family, int ndim, int iso, int nt, int cons);  // RING, DISC; 2D
+KernelInfo ctr_block_kernel_fit3d(int family, int ndim, int iso, int nt, int cons);  // RING, DISC; 3D
+KernelInfo ctr_block_kernel_inv(int family, int ndim, int iso, int nt, int cons);    // INV_SERIES
 // refine_small_kernel<ND, NF, ISO, SG>(KArgs, int* counter); nullptr if not instantiated
 const void* ctr_small_kernel(int ndim, int nf, int iso, int sg);
 KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpass of the window

@@ -1,5 +1,6 @@
-// tu_block2d.hip -- the 2D instantiations of refine_block_kernel (compiled on their own so
-// that the engine builds in parallel); see block_kernel.h.
+// tu_block2d.hip -- the 2D instantiations of refine_block_kernel for the gaussian, default and
+// CTR_FLAG_THROUGHPUT wavefront counts (compiled on their own so that the engine builds in
+// parallel); see block_kernel.h, block_table.h.
 #include <cmath>
 
 #include "kargs.h"
@@ -8,46 +9,15 @@ namespace {
 
 #include "device_common.h"
 #include "block_kernel.h"
-
-constexpr size_t LDS_CU = 160 * 1024;  // LDS of one CU
-
-template <int NT> struct WavesFor { static constexpr int value = NT <= 2 ? 8 : (NT <= 3 ? 4 : (NT <= 6 ? 2 : 1)); };
-// CTR_FLAG_THROUGHPUT: fewest wavefronts per cluster (a quarter of the LDS and of the wave slots
-// for 3-4 features; two or three workgroups per CU instead of one for 5-30 features)
-template <int NT> struct WavesThroughput { static constexpr int value = NT <= 2 ? 2 : 1; };
-
-template <bool ISO, int NT, bool TP, bool CONS = false>
-KernelInfo one() {
-  constexpr int W = TP ? WavesThroughput<NT>::value : WavesFor<NT>::value;
-  static_assert(SmemB<NT, W, CONS>::bytes <= LDS_CU, "LDS budget of one CU");
-  return KernelInfo{(const void*)refine_block_kernel<2, ISO, NT, W, CONS>, SmemB<NT, W, CONS>::bytes, WAVE * W};
-}
-
-template <bool ISO, bool TP>
-KernelInfo by_nt(int nt, int cons) {
-  if (cons) {   // constrained clusters have at most 4 features = 29 variables
-    if (nt == 1) return one<ISO, 1, TP, true>();
-    if (nt == 2) return one<ISO, 2, TP, true>();
-    return KernelInfo{nullptr, 0, 0};
-  }
-  switch (nt) {
-    case 1: return one<ISO, 1, TP>();
-    case 2: return one<ISO, 2, TP>();
-    case 3: return one<ISO, 3, TP>();
-    case 4: return one<ISO, 4, TP>();
-    case 5: return one<ISO, 5, TP>();
-    case 6: return one<ISO, 6, TP>();
-    case 7: return one<ISO, 7, TP>();
-    case 8: return one<ISO, 8, TP>();
-    default: return KernelInfo{nullptr, 0, 0};
-  }
-}
+#include "block_table.h"
 
 }  // namespace
 
-KernelInfo ctr_block_kernel_2d(int iso, int nt, int throughput, int cons) {
-  if (throughput) return iso ? by_nt<true, true>(nt, cons) : by_nt<false, true>(nt, cons);
-  return iso ? by_nt<true, false>(nt, cons) : by_nt<false, false>(nt, cons);
+KernelInfo ctr_block_kernel_2d(int family, int ndim, int iso, int nt, int cons) {
+  if (ndim != 2) return KernelInfo{nullptr, 0, 0};
+  if (family == CTR_KFAM_GAUSS) return block_kernel<2, false, false, CTR_FIT_GAUSS>(iso, nt, cons);
+  if (family == CTR_KFAM_GAUSS_TP) return block_kernel<2, true, false, CTR_FIT_GAUSS>(iso, nt, cons);
+  return KernelInfo{nullptr, 0, 0};
 }
 
 #ifdef CTR_STAMPS

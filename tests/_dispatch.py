@@ -2,10 +2,11 @@
 
 ``ctr_plan_create`` (clustertracking_amd/csrc/ctrefine.hip) sends every cluster to one template
 instantiation; ``ctr_cluster_kernel`` (include/ctrefine.h) reports which.  A *cell* is one such
-instantiation as the dispatch reaches it.  ``launchable_cells()`` writes them out from the kernel
-tables -- the non-null entries of ``pick`` (tu_small.hip), ``by_nt`` (tu_block2d/3d.hip,
-tu_block_lp.hip, tu_block_fit2d/3d.hip, tu_block_inv.hip) and ``one`` (tu_large.hip) -- not from
-the function under test.  ``TOO_LARGE_CELLS`` lists the clusters the engine refuses (status 5).
+instantiation as the dispatch reaches it, one non-null entry of the handle's kernel table
+(``ctr_handle::kernels``, indexed by family, ndim, iso and slot; filled by ``kernel_of`` from
+tu_small.hip, the tu_block*.hip units through block_table.h, and tu_large.hip).
+``launchable_cells()`` writes them out from what those units instantiate, not from the function
+under test.  ``TOO_LARGE_CELLS`` lists the clusters the engine refuses (status 5).
 
 ``build_case(cell)`` draws, with a fixed seed, a frame per cluster holding one compact patch of
 touching features (``artificial.draw_feature`` with the cell's profile, low Poisson noise) and a
@@ -57,11 +58,11 @@ def cell_id(c):
 def launchable_cells():
     cells = []
     for nd, iso in GEOMS:
-        # tu_small.hip pick(): singles at 8 / 64 lanes, pairs at 64 / 16 lanes
+        # tu_small.hip: singles at 8 / 64 lanes, pairs at 64 / 16 lanes (one table slot each)
         for kind, lanes in (('small1', 8), ('small1', 64), ('small2', 64), ('small2', 16)):
             cells.append(Cell('small', nd, iso, kind, 0, lanes))
-        # block kernels by_nt(): NT 1..8 and the constrained NT 1..2 of every table; the
-        # CTR_FLAG_THROUGHPUT table of the gaussian in 2D only (tu_block3d.hip ignores the flag)
+        # block kernels (block_table.h): NT 1..8 and the constrained NT 1..2 of every family; the
+        # CTR_FLAG_THROUGHPUT family of the gaussian in 2D only (its 3D cells stay null)
         for fam in ('gauss', 'gauss_tp', 'lowpass', 'ring', 'disc', 'inv_series'):
             if fam == 'gauss_tp' and nd == 3:
                 continue
@@ -69,7 +70,7 @@ def launchable_cells():
                 cells.append(Cell(fam, nd, iso, 'block', nt, 0))
             for nt in (1, 2):
                 cells.append(Cell(fam, nd, iso, 'cons', nt, 0))
-        # tu_large.hip one(): without / with the lowpass
+        # tu_large.hip: without / with the lowpass
         for fam in ('large', 'large_lowpass'):
             cells.append(Cell(fam, nd, iso, 'large', 0, 0))
     return cells
