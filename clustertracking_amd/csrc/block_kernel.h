@@ -46,13 +46,26 @@ __device__ __forceinline__ double readlane_f64(double x, int srclane) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// a value that is the same in every lane, moved to scalar registers (the kernel's loop-invariant
+// doubles would otherwise each hold two vector registers for the whole kernel)
+__device__ __forceinline__ double uniform_f64(double x) {
+  const long long b = __double_as_longlong(x);
+  const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffLL));
+  const int hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 // nwt: add the exact second-order part.  qk[kr] is the entry between this lane's variable
 // and the variable of kind kr (0 signal, 1 + a position) of the same feature; ic = vinfo[c].
 template <int NR, int NK>
 __device__ __forceinline__ bool column_solve(const double* Mp, int nv, double mu, bool is_free,
                                              int lane, double& x_own, bool nwt, const int* vinfo,
                                              int ic, const double (&qk)[NK]) {
-  const int c = lane;
+  // the lane's addresses below are invariant in the loops around the call (the kernel's phase loop,
+  // the step's attempts): an opaque copy of the lane index keeps the compiler from hoisting all NR
+  // of them out of those (they would be carried through the pixel pass in registers, or spilled)
+  int c = lane;
+  asm volatile("" : "+v"(c));
   const bool colv = c < nv && is_free;
   const unsigned long long fmask = __ballot(colv);
   double col[NR];
@@ -121,6 +134,15 @@ struct LayoutB {
   int per_feat[CTR_MAX_PARAMS];
   __device__ __forceinline__ int vidx(int kk, int i) const {
     return slot[kk] < 0 ? -1 : (per_feat[kk] ? nshared + i * npf + slot[kk] : slot[kk]);
+  }
+  // vidx for a parameter column known only at run time (or different in every lane): selected
+  // from the unrolled compile-time cases, so that slot / per_feat are never indexed at run time
+  // (a runtime index puts the whole layout in per-lane scratch memory)
+  __device__ __forceinline__ int vidx_any(int kk, int i) const {
+    int b = -1;
+#pragma unroll
+    for (int t = 0; t < CTR_MAX_PARAMS; ++t) b = kk == t ? vidx(t, i) : b;
+    return b;
   }
   // bit mask of the 16-column blocks that hold the columns of feature i
   __device__ __forceinline__ unsigned blocks(int i) const {
@@ -258,10 +280,14 @@ __device__ unsigned long long g_stamps[16];
 // inv_series_<N> N + 1 (signal_mult, param_a, ...); all three iterate with the Gauss-Newton model.
 // Minimum wavefronts per SIMD asked of the compiler (the register budget) for the instantiations
 // of the throughput scheduling (2D, fewest wavefronts per cluster: W = 2 for NT <= 2, 1 above).
-// NT = 1 (3-4 features): 3 -- 168 VGPRs + 272 B of scratch instead of 231 + 100 at 2 per SIMD:
-// +6 % on cfg 2 with ten batches in flight (interleaved A/B, tools/ab_bench.sh: 48.4 -> 51.4 M fits/s;
-// 4 per SIMD: 128 VGPRs + 484 B, -8 %).  The kernel waits on dependent FP64 chains; a third
-// wavefront per SIMD hides more of them than the spills cost.
+// NT = 1 (3-4 features): 3 -- 168 VGPRs and no scratch (2D iso and aniso; tests/test_kernel_resources.py).
+// A third wavefront per SIMD gave +6 % on cfg 2 with ten batches in flight even while it spilled
+// (168 VGPRs + 296 B; interleaved A/B, tools/ab_bench.sh: 48.4 -> 51.4 M fits/s): the kernel waits
+// on dependent FP64 chains.  The spills were not the step's working set but values the compiler
+// hoisted out of the phase loop (per-lane LDS addresses, the layout in scratch through a runtime
+// index, a few invariant doubles); see `lane` at the top of the loop and LayoutB::vidx_any.
+// 4 per SIMD buys nothing here: 26.6 KB of LDS per workgroup already limit a CU to 6 workgroups
+// (3 wavefronts per SIMD), and the compiler spills again at 128 VGPRs.
 #ifndef CTR_OCC_NT1
 #define CTR_OCC_NT1 3
 #endif
@@ -294,7 +320,8 @@ refine_block_kernel(const KArgs k) {
   constexpr bool SAFE_R2 = FIT == CTR_FIT_RING || FIT == CTR_FIT_DISC;   // r2_*_safe (fitfunc.py:396-411)
   constexpr int LDC = SM::NVC;
   extern __shared__ double smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (scalar)
+  int lane = tid & 63;   // (made opaque at the top of the phase loop: see there)
   const int cl = k.order[blockIdx.x];
   const int f0 = k.feat_offset[cl], n = k.feat_offset[cl + 1] - f0;
   const double* params = k.params + (size_t)f0 * NP;
@@ -335,9 +362,16 @@ refine_block_kernel(const KArgs k) {
 #pragma unroll
   for (int a = 0; a < ND; ++a) {
     radius[a] = k.prob.radius[a];
-    inv_r2[a] = 1. / ((double)radius[a] * (double)radius[a]);
+    inv_r2[a] = uniform_f64(1. / ((double)radius[a] * (double)radius[a]));
     fshape[a] = k.shape[a];
   }
+  // vidx of a parameter column known only at run time.  The lowpass instantiations keep indexing
+  // the layout at run time (it then lives in scratch memory): their calls of lowpass_pixel would
+  // otherwise save the layout's registers around every call (3D, NT = 1: 128 -> 528 B of scratch)
+  auto vidx_rt = [&](int kk, int i) -> int {
+    if constexpr (LP) return L.vidx(kk, i);
+    else return L.vidx_any(kk, i);
+  };
   // parameter kk of feature i at vector vv (vect_to_params, fitfunc.py:266-315)
   auto par = [&](const double* vv, int i, int kk) -> double {
     const int b = L.vidx(kk, i);
@@ -699,7 +733,7 @@ refine_block_kernel(const KArgs k) {
             }
             wsync();
             if (lane < PW * PW) {
-              const int ct = L.vidx(1 + et, i), cu = L.vidx(1 + eu, i);
+              const int ct = vidx_rt(1 + et, i), cu = vidx_rt(1 + eu, i);
               if (ct >= 0 && cu >= 0 && ct >= cu) dest[tri(ct) + cu] += wsum[widx];
             }
             wsync();
@@ -770,11 +804,13 @@ refine_block_kernel(const KArgs k) {
   bool last_acc = true;
   double gain = INFINITY;  // relative merit decrease of the last accepted step
   const double fm = k.fmax[k.frame_index[cl]];
-  const double norm = fm * fm / k.prob.residual_factor;  // refine.py:354
-  const double ms2 = k.prob.max_shift * k.prob.max_shift;
+  const double norm = uniform_f64(fm * fm / k.prob.residual_factor);  // refine.py:354
+  const double ms2 = uniform_f64(k.prob.max_shift * k.prob.max_shift);
 
   // start of a round (wave 0): window, clipped start vector, derived constants
   auto begin_round = [&]() -> int {
+    it = 0;   // (first: a store to it or to status on the two exits would be merged into one store
+              // through a pointer that selects between them, and both would live in scratch memory)
     int origin[ND], wshape[ND];
     if (!window_of(origin, wshape)) { status = CTR_STATUS_OUT_OF_BOUNDS; return BP_FINISH; }
     bool infeasible = false;
@@ -793,7 +829,6 @@ refine_block_kernel(const KArgs k) {
     // the start vector need not satisfy the constraints: restore feasibility first
     retr_fail = m > 0 && !retract(vt, cvt, Cjt, cpair + MAXC, 0ull);
     fill_fpar(vt, size_is_var || round == 0);
-    it = 0;
     return BP_EVAL_INIT;
   };
 
@@ -803,15 +838,20 @@ refine_block_kernel(const KArgs k) {
   }
   __syncthreads();
 
-  v4d acc[SM::NTILE];
   // second-order sums U[a<=b] = sum_p res J_pos_a dE/dpos_b of feature `lane` (this wave's share)
   constexpr int NUF = ND * (ND + 1) / 2;
-  double uacc[NUF];
-#pragma unroll
-  for (int t = 0; t < NUF; ++t) uacc[t] = 0.;
   while (true) {
+    // Everything the loop computes from the lane index alone (LDS addresses of the lane's row,
+    // column, variable, ...) is loop-invariant; hoisted out of the loop, all of it would stay live
+    // across both the pixel pass and the step and be spilled.  An opaque copy of the index per
+    // iteration keeps each such value next to its use.
+    asm volatile("" : "+v"(lane));
     const int phase = ctl[0];
     if (phase == BP_FINISH) break;
+    // the accumulators of this iteration's pixel pass: declared here so that they are not carried
+    // from one iteration to the next (they are dead from the write-back of an accepted point on)
+    v4d acc[SM::NTILE];
+    double uacc[NUF];
     double Sloc = 0.;
     int P = 0;
     if (phase == BP_EVAL_INIT || phase == BP_EVAL_TRIAL) {
@@ -1735,7 +1775,7 @@ refine_block_kernel(const KArgs k) {
       }
       double* ps = k.params_std + (size_t)f0 * NP;
       for (int e = lane; e < n * NP; e += WAVE) {
-        const int b = L.vidx(e % NP, e / NP);
+        const int b = vidx_rt(e % NP, e / NP);
         ps[e] = (pd && b >= 0) ? sd[b] : NAN;
       }
     }
