@@ -7,14 +7,16 @@ for the part of it that this engine accelerates.
 import logging
 
 from .refine import refine_leastsq, prepare_batch, write_back
-from .find import find_clusters
+from .find import (find_clusters, grey_dilation, locate_maxima, percentile_threshold,
+                   where_close, drop_close)
 from .fitfunc import FitFunctions
 from .utils import ArrayReader, RefineException
 from . import constraints, artificial, link
 
 link_df = link.link
 
-__all__ = ['refine_leastsq', 'find_clusters', 'link', 'link_df', 'FitFunctions', 'constraints',
+__all__ = ['refine_leastsq', 'find_clusters', 'grey_dilation', 'locate_maxima',
+           'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',
            'write_back']
 

@@ -107,6 +107,18 @@ class Synth(C.Structure):
     ]
 
 
+class Locate(C.Structure):
+    """``ctr_locate`` (include/ctrefine.h): feature location on the device."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('frame_dtype', C.c_int32), ('n_frames', C.c_int64),
+        ('shape', C.c_int64 * MAX_NDIM), ('separation', C.c_double * MAX_NDIM),
+        ('percentile', C.c_double), ('margin', C.c_int64 * MAX_NDIM),
+        ('precise', C.c_int32), ('reserved0', C.c_int32), ('capacity', C.c_int64),
+        ('frames', C.c_void_p), ('frame_offset', C.c_void_p), ('pos_out', C.c_void_p),
+        ('total', C.c_void_p), ('threshold', C.c_void_p),
+    ]
+
+
 def make_problem(ndim, isotropic, modes, radius, constraint=None, max_iter=10,
                  max_shift=1., max_rms_dev=1., residual_factor=100000.,
                  solver_maxiter=100, xtol=0., ftol=0., noise_size=None, threshold=None,

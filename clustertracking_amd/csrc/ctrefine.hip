@@ -984,6 +984,15 @@ int ctr_draw_frames_device(ctr_handle* h, const ctr_synth* sy, void* frames_out,
   return CTR_OK;
 }
 
+int ctr_locate_maxima_device(ctr_handle* h, const ctr_locate* l, void* hip_stream) {
+  if (!h) return CTR_ERR_INVALID;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const char* msg = "";
+  const int rc = ctr_locate_launch(l, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_locate_maxima_device: ") + msg);
+  return CTR_OK;
+}
+
 int ctr_synchronize(ctr_handle* h, void* hip_stream) {
   if (!h) return CTR_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));

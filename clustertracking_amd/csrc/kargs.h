@@ -118,5 +118,8 @@ KernelInfo ctr_block_kernel_inv(int family, int ndim, int iso, int nt, int cons)
 // refine_small_kernel<ND, NF, ISO, SG>(KArgs, int* counter); nullptr if not instantiated
 const void* ctr_small_kernel(int ndim, int nf, int iso, int sg);
 KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpass of the window
+// feature location (tu_locate.hip, locate_kernels.h): checks the descriptor and queues the whole
+// pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
+int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

@@ -296,6 +296,41 @@ typedef struct ctr_synth {
 } ctr_synth;
 int ctr_draw_frames_device(ctr_handle* h, const ctr_synth* s, void* frames_out, void* hip_stream);
 
+/* Feature location on the device: the local-maximum rule of reference find.grey_dilation
+ * (find.py:166-277) for every frame of a block.  Per frame:
+ *   threshold = np.percentile of the non-zero pixels (linear method, NumPy's arithmetic in the
+ *     frame's type: float32 for float32 frames, float64 otherwise); NaN (no non-zero pixel, a NaN
+ *     pixel) = no features;
+ *   box = int(2 separation / sqrt(ndim)) per axis; a pixel is a maximum where it equals the
+ *     maximum of its box (scipy.ndimage.grey_dilation, constant border 0: offsets
+ *     -((n-1)/2) .. n/2 along an axis of box n) and exceeds the threshold;
+ *   maxima closer than `margin` to an edge are dropped;
+ *   precise != 0: of two maxima closer than separation (scaled distance <= 1 - 1e-7), the one
+ *     lower in the order (pixel value, sum of pos / separation, C-order position) is dropped;
+ *     all pairs are decided at once.
+ * Positions are written in C order of their frame, frames one after the other.  The total is
+ * not known in advance: when *total > capacity only the first `capacity` rows are written (the
+ * offsets and the total are complete) and the caller retries with a larger buffer.
+ * Device pointers; asynchronous on `hip_stream` (NULL = the handle's stream). */
+typedef struct ctr_locate {
+  int32_t ndim;                /* 2 or 3 */
+  int32_t frame_dtype;         /* CTR_DTYPE_* */
+  int64_t n_frames;
+  int64_t shape[CTR_MAX_NDIM]; /* (z,) y, x */
+  double separation[CTR_MAX_NDIM]; /* per axis, >= 0 */
+  double percentile;           /* [0, 100] */
+  int64_t margin[CTR_MAX_NDIM];    /* per axis, >= 0 (reference default: int(separation / 2)) */
+  int32_t precise;             /* != 0: drop maxima closer than separation to a brighter one */
+  int32_t reserved0;
+  int64_t capacity;            /* rows of pos_out */
+  const void* frames;          /* [n_frames, *shape] */
+  int64_t* frame_offset;       /* [n_frames + 1] out: rows of frame t are [off[t], off[t+1]) */
+  int32_t* pos_out;            /* [capacity, ndim] out: (z,) y, x */
+  int64_t* total;              /* [1] out: rows found (may exceed capacity) */
+  double* threshold;           /* [n_frames] out, or NULL: the percentile threshold (NaN: none) */
+} ctr_locate;
+int ctr_locate_maxima_device(ctr_handle* h, const ctr_locate* l, void* hip_stream);
+
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
  * several batches in flight hand finished batches on (e.g. to the result gather) from the host
