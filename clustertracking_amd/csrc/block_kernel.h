@@ -288,18 +288,9 @@ __device__ unsigned long long g_stamps[16];
 // index, a few invariant doubles); see `lane` at the top of the loop and LayoutB::vidx_any.
 // 4 per SIMD buys nothing here: 26.6 KB of LDS per workgroup already limit a CU to 6 workgroups
 // (3 wavefronts per SIMD), and the compiler spills again at 128 VGPRs.
-#ifndef CTR_OCC_NT1
-#define CTR_OCC_NT1 3
-#endif
-#ifndef CTR_OCC_NT2
-#define CTR_OCC_NT2 1
-#endif
-#ifndef CTR_OCC_NT34
-#define CTR_OCC_NT34 1
-#endif
+// NT = 2 and NT = 3-4 ask for 1, as every other instantiation does.
 constexpr int block_occ(int nt, int w, bool cons, bool lp, int fit) {
-  return (cons || lp || fit != 0) ? 1 : (nt == 1 && w == 2) ? CTR_OCC_NT1 : (nt == 2 && w == 2) ? CTR_OCC_NT2
-       : ((nt == 3 || nt == 4) && w == 1) ? CTR_OCC_NT34 : 1;
+  return (cons || lp || fit != 0) ? 1 : (nt == 1 && w == 2) ? 3 : 1;
 }
 template <int ND, bool ISO, int NT, int W, bool CONS, bool LP = false, int FIT = 0>
 __global__ void __launch_bounds__(WAVE * W, (block_occ(NT, W, CONS, LP, FIT)))

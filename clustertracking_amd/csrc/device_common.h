@@ -182,26 +182,6 @@ __device__ __forceinline__ void profile_inv_dev(int nx, double r2, const double*
 
 __device__ __forceinline__ int tri(int i) { return (i * (i + 1)) >> 1; }
 
-struct Layout {
-  int n, nv;
-  int var_of[CTR_MAX_PARAMS];
-  int per_feat[CTR_MAX_PARAMS];
-};
-
-// vect_from_params layout with groups=None (fitfunc.py:207-263)
-__device__ __forceinline__ void make_layout(const ctr_problem& p, int n, Layout& L) {
-  int nv = 0;
-  L.n = n;
-#pragma unroll
-  for (int k = 0; k < CTR_MAX_PARAMS; ++k) {
-    int m = k < p.n_params ? p.modes[k] : CTR_MODE_CONST;
-    if (m == CTR_MODE_CONST) { L.var_of[k] = -1; L.per_feat[k] = 0; }
-    else if (m == CTR_MODE_VAR) { L.var_of[k] = nv; L.per_feat[k] = 1; nv += n; }
-    else { L.var_of[k] = nv; L.per_feat[k] = 0; nv += 1; }
-  }
-  L.nv = nv;
-}
-
 // ---- masks (refine.py:43-44) --------------------------------------------------
 
 template <int ND>

@@ -24,10 +24,7 @@
 #ifndef CTREFINE_LARGE_KERNEL_H
 #define CTREFINE_LARGE_KERNEL_H
 
-#ifndef CTR_LARGE_WAVES
-#define CTR_LARGE_WAVES 8
-#endif
-constexpr int LW = CTR_LARGE_WAVES; // wavefronts per workgroup (512 threads: 256 VGPRs per lane -- with 1024
+constexpr int LW = 8;              // wavefronts per workgroup (512 threads: 256 VGPRs per lane -- with 1024
                                    // the kernel spilled 0.8-1.3 KB per lane; two workgroups fit a CU's LDS)
 constexpr int LT = LW * WAVE;      // threads
 constexpr int LRS = 17;            // row stride of a wave's LDS tile (odd: conflict-free ds_write_b64)

@@ -214,107 +214,17 @@ __global__ void __launch_bounds__(WAVE, NF == 1 ? 3 : 1) refine_small_kernel(con
       const float inv_w1 = ND == 3 ? 1.f / (float)wshape[1] : 1.f;
       const bool big_window = npix >= (1 << 21);
       const double bg = vt[0];
-#ifndef CTR_SMALL_PX
-#define CTR_SMALL_PX 2
-#endif
-#ifndef CTR_SMALL_PX2
-#define CTR_SMALL_PX2 1
-#endif
-#ifndef CTR_SMALL_BRANCHFREE2
-#define CTR_SMALL_BRANCHFREE2 1
-#endif
-      if constexpr (NF == 1 || CTR_SMALL_BRANCHFREE2) {
-        constexpr int PX = NF == 1 ? CTR_SMALL_PX : CTR_SMALL_PX2;
-        // PX pixels per lane in flight and no branch around the model -- the chains of dependent
-        // f64 operations of the pixels (and of the two features of a pair) interleave: the
-        // kernel is latency bound at 2-3 waves per SIMD; a lane outside the window or a mask
-        // contributes zeros.  Same sums as the loop below, other order.
-        for (int base = 0; __any(base < npix_here); base += PX * SG) {
-          double rw[PX][NR], Ek[PX][NF][ND];
+      constexpr int PX = NF == 1 ? 2 : 1;
+      // PX pixels per lane in flight and no branch around the model -- the chains of dependent
+      // f64 operations of the pixels (and of the two features of a pair) interleave: the
+      // kernel is latency bound at 2-3 waves per SIMD; a lane outside the window or a mask
+      // contributes zeros.
+      for (int base = 0; __any(base < npix_here); base += PX * SG) {
+        double rw[PX][NR], Ek[PX][NF][ND];
 #pragma unroll
-          for (int u = 0; u < PX; ++u) {
-            const int q = base + u * SG + sub;
-            const bool valid = q < npix_here;
-            int idx[ND];
-            size_t off;
-            {
-              const int t = big_window ? q / w_last : (int)(((float)q + 0.5f) * inv_w2);
-              const int x = q - t * w_last;
-              if (ND == 3) {
-                const int z = big_window ? t / wshape[1] : (int)(((float)t + 0.5f) * inv_w1);
-                const int y = t - z * wshape[1];
-                idx[0] = z; idx[1] = y; idx[ND - 1] = x;
-                off = ((size_t)(z + origin[0]) * fshape[1] + (y + origin[1])) * fshape[ND - 1] + (x + origin[ND - 1]);
-              } else {
-                idx[0] = t; idx[ND - 1] = x;
-                off = (size_t)(t + origin[0]) * fshape[ND - 1] + (x + origin[ND - 1]);
-              }
-            }
-            const double pix = valid ? load_pixel(frame, k.frame_dtype, off) : 0.;
-            bool in[NF], any = false;
-            double gv[NF], tt[NF][ND];
-            double res = pix - bg;
-#pragma unroll
-            for (int i = 0; i < NF; ++i) {
-              double rel[ND];
-#pragma unroll
-              for (int a = 0; a < ND; ++a) rel[a] = mco[i][a] - (double)origin[a];
-              in[i] = valid && in_mask<ND>(idx, rel, inv_r2, radius);
-              any = any || in[i];
-              double r2 = 0.;
-#pragma unroll
-              for (int a = 0; a < ND; ++a) {
-                const double dd = (double)(idx[a] + origin[a]) - vt[1 + NF + a * NF + i];
-                tt[i][a] = dd * isz2[i][a];
-                r2 += dd * tt[i][a];
-              }
-              gv[i] = exp(-0.5 * ND * r2);
-              res -= in[i] ? vt[1 + i] * gv[i] : 0.;
-            }
-            const bool ok = any && (res == res);
-            P += any ? 1 : 0;
-            rw[u][0] = ok ? -1. : 0.;
-            rw[u][NV] = ok ? res : 0.;
-#pragma unroll
-            for (int i = 0; i < NF; ++i) {
-              const bool oi = ok && in[i];
-              const double sng = -vt[1 + i] * (double)ND * gv[i];
-              rw[u][1 + i] = oi ? -gv[i] : 0.;
-#pragma unroll
-              for (int a = 0; a < ND; ++a) {
-                rw[u][1 + NF + a * NF + i] = oi ? sng * tt[i][a] : 0.;
-                Ek[u][i][a] = oi ? (double)ND * tt[i][a] : 0.;
-              }
-            }
-          }
-          int e = 0;
-#pragma unroll
-          for (int p = 0; p < NR; ++p)
-#pragma unroll
-            for (int c2 = p; c2 < NR; ++c2) {
-              double t = rw[0][p] * rw[0][c2];
-#pragma unroll
-              for (int u = 1; u < PX; ++u) t += rw[u][p] * rw[u][c2];
-              M[e] += t;
-              ++e;
-            }
-#pragma unroll
-          for (int i = 0; i < NF; ++i)
-#pragma unroll
-            for (int a = 0; a < ND; ++a)
-#pragma unroll
-              for (int b = a; b < ND; ++b) {
-                double t = 0.;
-#pragma unroll
-                for (int u = 0; u < PX; ++u) t += (rw[u][NV] * rw[u][1 + NF + a * NF + i]) * Ek[u][i][b];
-                M[e] += t;
-                ++e;
-              }
-        }
-      } else
-      for (int base = 0; __any(base < npix_here); base += SG) {
-        const int q = base + sub;
-        if (q < npix_here) {
+        for (int u = 0; u < PX; ++u) {
+          const int q = base + u * SG + sub;
+          const bool valid = q < npix_here;
           int idx[ND];
           size_t off;
           {
@@ -330,67 +240,66 @@ __global__ void __launch_bounds__(WAVE, NF == 1 ? 3 : 1) refine_small_kernel(con
               off = (size_t)(t + origin[0]) * fshape[ND - 1] + (x + origin[ND - 1]);
             }
           }
-          // fetched first: the load latency hides behind the mask tests and the model
-          const double pix = load_pixel(frame, k.frame_dtype, off);
-          double row[NR];
-#pragma unroll
-          for (int j = 0; j < NR; ++j) row[j] = 0.;
-          bool any = false;
-          double res = 0.;
-          double Ed[NF][ND];  // d(-ND/2 r2)/d pos of the features covering this pixel, else 0
-#pragma unroll
-          for (int i = 0; i < NF; ++i)
-#pragma unroll
-            for (int a = 0; a < ND; ++a) Ed[i][a] = 0.;
+          const double pix = valid ? load_pixel(frame, k.frame_dtype, off) : 0.;
+          bool in[NF], any = false;
+          double gv[NF], tt[NF][ND];
+          double res = pix - bg;
 #pragma unroll
           for (int i = 0; i < NF; ++i) {
             double rel[ND];
 #pragma unroll
             for (int a = 0; a < ND; ++a) rel[a] = mco[i][a] - (double)origin[a];
-            if (in_mask<ND>(idx, rel, inv_r2, radius)) {
-              any = true;
-              double r2 = 0., dd[ND];
+            in[i] = valid && in_mask<ND>(idx, rel, inv_r2, radius);
+            any = any || in[i];
+            double r2 = 0.;
 #pragma unroll
-              for (int a = 0; a < ND; ++a) {
-                dd[a] = (double)(idx[a] + origin[a]) - vt[1 + NF + a * NF + i];
-                r2 += dd[a] * dd[a] * isz2[i][a];
-              }
-              const double gv = exp(-0.5 * ND * r2);
-              const double sig = vt[1 + i];
-              res -= sig * gv;
-              row[1 + i] = -gv;
-              const double sng = -sig * (double)ND * gv;
-#pragma unroll
-              for (int a = 0; a < ND; ++a) {
-                const double t = dd[a] * isz2[i][a];
-                row[1 + NF + a * NF + i] = sng * t;
-                Ed[i][a] = (double)ND * t;
-              }
+            for (int a = 0; a < ND; ++a) {
+              const double dd = (double)(idx[a] + origin[a]) - vt[1 + NF + a * NF + i];
+              tt[i][a] = dd * isz2[i][a];
+              r2 += dd * tt[i][a];
             }
+            gv[i] = exp(-0.5 * ND * r2);
+            res -= in[i] ? vt[1 + i] * gv[i] : 0.;
           }
-          if (any) {
-            res += pix - bg;
-            ++P;
-            if (res == res) {
-              row[0] = -1.;
-              row[NV] = res;
-              int e = 0;
+          const bool ok = any && (res == res);
+          P += any ? 1 : 0;
+          rw[u][0] = ok ? -1. : 0.;
+          rw[u][NV] = ok ? res : 0.;
 #pragma unroll
-              for (int p = 0; p < NR; ++p)
+          for (int i = 0; i < NF; ++i) {
+            const bool oi = ok && in[i];
+            const double sng = -vt[1 + i] * (double)ND * gv[i];
+            rw[u][1 + i] = oi ? -gv[i] : 0.;
 #pragma unroll
-                for (int c2 = p; c2 < NR; ++c2) { M[e] += row[p] * row[c2]; ++e; }
-              // second-order sums (block_kernel.h / oracle solve(): the exact model Hessian)
-#pragma unroll
-              for (int i = 0; i < NF; ++i)
-#pragma unroll
-                for (int a = 0; a < ND; ++a) {
-                  const double rj = res * row[1 + NF + a * NF + i];
-#pragma unroll
-                  for (int b = a; b < ND; ++b) { M[e] += rj * Ed[i][b]; ++e; }
-                }
+            for (int a = 0; a < ND; ++a) {
+              rw[u][1 + NF + a * NF + i] = oi ? sng * tt[i][a] : 0.;
+              Ek[u][i][a] = oi ? (double)ND * tt[i][a] : 0.;
             }
           }
         }
+        int e = 0;
+#pragma unroll
+        for (int p = 0; p < NR; ++p)
+#pragma unroll
+          for (int c2 = p; c2 < NR; ++c2) {
+            double t = rw[0][p] * rw[0][c2];
+#pragma unroll
+            for (int u = 1; u < PX; ++u) t += rw[u][p] * rw[u][c2];
+            M[e] += t;
+            ++e;
+          }
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+          for (int a = 0; a < ND; ++a)
+#pragma unroll
+            for (int b = a; b < ND; ++b) {
+              double t = 0.;
+#pragma unroll
+              for (int u = 0; u < PX; ++u) t += (rw[u][NV] * rw[u][1 + NF + a * NF + i]) * Ek[u][i][b];
+              M[e] += t;
+              ++e;
+            }
       }
     }
     if (__any(evaluating)) {

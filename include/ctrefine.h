@@ -241,14 +241,7 @@ int ctr_refine_batch(ctr_handle* h, const ctr_problem* p, const ctr_batch* b);
  * GPU): a plan bins the clusters of a batch by problem size on the host once (and owns the
  * HBM workspace of its large clusters: use a plan with the handle it was created on);
  * the run is asynchronous on the given HIP stream (hipStream_t passed as
- * void*; NULL = the handle's own stream).
- * Measurement-only switches, read from the environment on every ctr_refine_batch_device call;
- * leave them unset in production:
- *   CTR_LARGE_CG_TOL2="far,near"  squared relative residual tolerances of the large-cluster
- *                                 kernel's conjugate-gradient solve, far from / near the solution
- *                                 (default 1e-12,1e-22).  CHANGES RESULTS:
- *                                 1e-8 for far gives about 6e-7 px against the oracle instead of 5e-8
- *   CTR_LARGE_WORKGROUPS=<1..16>  workgroups per large cluster (leader included); scheduling only */
+ * void*; NULL = the handle's own stream). */
 int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
                     const int32_t* feat_offset_host, ctr_plan** out);
 void ctr_plan_destroy(ctr_plan* plan);

@@ -2,7 +2,7 @@
 of the built libctrefine.so (CPU only).
 
 The 3-4-feature cells of the throughput table (refine_block_kernel<2, ISO, NT=1, W=2>, gaussian,
-unconstrained, no lowpass) run at CTR_OCC_NT1 = 3 wavefronts per SIMD (block_kernel.h), the NT = 2
+unconstrained, no lowpass) run at 3 wavefronts per SIMD (block_kernel.h: block_occ), the NT = 2
 cells of that table at one.  They must do so without scratch memory: a later edit that brings
 spills back, or that needs more registers than their wavefronts per SIMD leave, fails here instead
 of silently costing throughput."""
