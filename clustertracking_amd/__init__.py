@@ -8,7 +8,7 @@ import logging
 
 from .refine import refine_leastsq, prepare_batch, write_back
 from .find import (find_clusters, grey_dilation, locate_maxima, percentile_threshold,
-                   where_close, drop_close)
+                   where_close, drop_close, characterize, characterize_arrays, locate)
 from .fitfunc import FitFunctions
 from .utils import ArrayReader, RefineException
 from . import constraints, artificial, link
@@ -16,6 +16,7 @@ from . import constraints, artificial, link
 link_df = link.link
 
 __all__ = ['refine_leastsq', 'find_clusters', 'grey_dilation', 'locate_maxima',
+           'characterize', 'characterize_arrays', 'locate',
            'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',
            'write_back']

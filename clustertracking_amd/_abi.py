@@ -119,6 +119,18 @@ class Locate(C.Structure):
     ]
 
 
+class Characterize(C.Structure):
+    """``ctr_characterize`` (include/ctrefine.h): mass, signal and size of located features."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('frame_dtype', C.c_int32), ('n_frames', C.c_int64),
+        ('shape', C.c_int64 * MAX_NDIM), ('radius', C.c_int64 * MAX_NDIM),
+        ('isotropic', C.c_int32), ('reserved0', C.c_int32), ('scale_factor', C.c_double),
+        ('frames', C.c_void_p), ('n_features', C.c_int64), ('frame_offset', C.c_void_p),
+        ('pos', C.c_void_p), ('pos_i32', C.c_void_p),
+        ('mass', C.c_void_p), ('signal', C.c_void_p), ('size', C.c_void_p),
+    ]
+
+
 def make_problem(ndim, isotropic, modes, radius, constraint=None, max_iter=10,
                  max_shift=1., max_rms_dev=1., residual_factor=100000.,
                  solver_maxiter=100, xtol=0., ftol=0., noise_size=None, threshold=None,

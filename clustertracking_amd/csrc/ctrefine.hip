@@ -1001,6 +1001,19 @@ int ctr_locate_maxima_device(ctr_handle* h, const ctr_locate* l, void* hip_strea
   return CTR_OK;
 }
 
+int ctr_characterize_device(ctr_handle* h, const ctr_characterize* c, void* hip_stream) {
+  // the descriptor is checked before the handle is touched: a bad one is reported (through
+  // ctr_last_error of a null handle) even where there is no device to make a handle on
+  const char* msg = "";
+  int rc = ctr_characterize_launch(c, false, nullptr, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_characterize_device: ") + msg);
+  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_characterize_device: null handle");
+  HIP_TRY(h, hipSetDevice(h->device));
+  rc = ctr_characterize_launch(c, true, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_characterize_device: ") + msg);
+  return CTR_OK;
+}
+
 int ctr_synchronize(ctr_handle* h, void* hip_stream) {
   if (!h) return CTR_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));

@@ -121,5 +121,8 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // feature location (tu_locate.hip, locate_kernels.h): checks the descriptor and queues the whole
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
+// feature characterisation (tu_characterize.hip, characterize_kernels.h): checks the descriptor
+// and, with launch_it, queues the kernel on `s`.  CTR_OK or an error code with a static message.
+int ctr_characterize_launch(const ctr_characterize* c, bool launch_it, hipStream_t s, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

@@ -11,6 +11,12 @@ run on the host, the local-maximum search itself on the MI355X
 (``ctr_locate_maxima_device``) for one frame (``grey_dilation``)
 or a block of frames (``locate_maxima``).  There is no CPU fallback.
 
+Characterisation follows reference ``find_link.characterize`` (find_link.py:44-79) and the
+``minmass`` filter of ``find_link`` (find_link.py:927-971): mass, signal and size of every located
+maximum on the MI355X (``ctr_characterize_device``) -- ``characterize`` for one
+frame, ``characterize_arrays`` for a block, ``locate`` for the chain locate -> characterize ->
+``mass >= minmass`` with the positions staying on the device in between.
+
 The labels themselves follow the reference's merge rule (when a pair (a, b) is
 joined, b's whole cluster takes a's current label; pairs are visited in the
 iteration order of the set returned by ``cKDTree.query_pairs``), so that ids
@@ -220,10 +226,12 @@ def _device_frames(frames, device, dtype):
 
 
 def locate_arrays(frames, separation, percentile=64, margin=None, precise=True, device=0,
-                  dtype=None, capacity=None):
+                  dtype=None, capacity=None, _on_device=False):
     """The device pass behind :func:`locate_maxima`: (positions int32 [N, ndim] in frame order,
     frame_offset int64 [T + 1], per-frame threshold float64 [T]) as NumPy arrays.
-    ``capacity``: rows to reserve at first; a larger buffer is taken when the frames hold more."""
+    ``capacity``: rows to reserve at first; a larger buffer is taken when the frames hold more.
+    (``_on_device``, internal: the three as torch tensors on the device, preceded by the frames'
+    tensor and pixel type -- what :func:`locate` hands to :func:`characterize_arrays`.)"""
     eng = _lib.default_engine(device)     # EngineError without a library or a GPU
     import torch
     t, pix = _device_frames(frames, device, dtype)
@@ -272,6 +280,8 @@ def locate_arrays(frames, separation, percentile=64, margin=None, precise=True, 
             if n <= capacity:
                 break
             capacity = n        # more maxima than rows: run again with room for all of them
+        if _on_device:
+            return t, pix, pos[:n], offset, thr[:n_frames]
         return (pos[:n].cpu().numpy(), offset.cpu().numpy(), thr[:n_frames].cpu().numpy())
 
 
@@ -302,3 +312,165 @@ def grey_dilation(image, separation, percentile=64, margin=None, precise=True, d
     if len(pos) == 0:
         return np.empty((0, image.ndim))
     return pos.astype(np.int64)
+
+
+# ---- characterisation (reference find_link.py:44-79, 927-971) -------------------------------
+
+def _size_columns(ndim, isotropic):
+    return ['size'] if isotropic else ['size_z', 'size_y', 'size_x'][3 - ndim:]
+
+
+def _characterize_device(frames, pos, frame_offset, radius, isotropic, scale_factor, device, dtype):
+    """:func:`characterize_arrays` with the results left on the device (torch tensors)."""
+    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
+    import torch
+    t, pix = _device_frames(frames, device, dtype)
+    ndim = t.dim() - 1
+    if ndim not in (2, 3):
+        raise ValueError("frames must be [T, (z,) y, x]")
+    radius = validate_tuple(radius, ndim)
+    if any(int(r) != r for r in radius):
+        raise ValueError("radius must be integer")
+    dev = t.device
+    n_frames = int(t.shape[0])
+    with torch.cuda.device(dev):
+        if isinstance(pos, torch.Tensor):
+            if pos.device != dev:
+                raise ValueError("pos must be on cuda:%d (it is on %s)" % (device, pos.device))
+            if pos.dtype not in (torch.int32, torch.float64):
+                raise ValueError("a position tensor is int32 or float64, not %s" % pos.dtype)
+            pos_t = pos.contiguous()
+        else:
+            pos = np.asarray(pos)
+            pos = np.ascontiguousarray(pos, dtype=np.int32 if pos.dtype == np.int32 else np.float64)
+            pos_t = torch.from_numpy(pos.reshape(-1, ndim) if pos.size == 0 else pos).to(dev)
+        if pos_t.dim() != 2 or pos_t.shape[1] != ndim:
+            raise ValueError("pos must be [N, %d]" % ndim)
+        n = int(pos_t.shape[0])
+        if isinstance(frame_offset, torch.Tensor):
+            if frame_offset.device != dev or frame_offset.dtype != torch.int64:
+                raise ValueError("a frame_offset tensor is int64 on cuda:%d" % device)
+            off_t = frame_offset.contiguous()
+            if off_t.numel() != n_frames + 1:
+                raise ValueError("frame_offset must have n_frames + 1 entries")
+        else:
+            off = np.ascontiguousarray(frame_offset, dtype=np.int64)
+            if off.shape != (n_frames + 1,) or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
+                raise ValueError("frame_offset must be [n_frames + 1], rising from 0 to the number of features")
+            off_t = torch.from_numpy(off).to(dev)
+        mass = torch.empty(n, dtype=torch.float64, device=dev)
+        signal = torch.empty(n, dtype=torch.float64, device=dev)
+        size = torch.empty((n, 1 if isotropic else ndim), dtype=torch.float64, device=dev)
+        if n == 0:      # nothing to launch (and an empty tensor has no address to pass)
+            if not (float(scale_factor) != 0.):
+                raise ValueError("scale_factor must be a non-zero number")
+            return mass, signal, size
+        ch = _abi.Characterize()
+        ch.ndim = ndim
+        ch.frame_dtype = _abi.DTYPE_CODES[np.dtype(pix)]
+        ch.n_frames = n_frames
+        for a in range(ndim):
+            ch.shape[a] = int(t.shape[1 + a])
+            ch.radius[a] = int(radius[a])
+        ch.isotropic = int(bool(isotropic))
+        ch.scale_factor = float(scale_factor)
+        ch.frames = t.data_ptr()
+        ch.n_features = n
+        ch.frame_offset = off_t.data_ptr()
+        if pos_t.dtype == torch.int32:
+            ch.pos_i32 = pos_t.data_ptr()
+        else:
+            ch.pos = pos_t.data_ptr()
+        ch.mass, ch.signal, ch.size = mass.data_ptr(), signal.data_ptr(), size.data_ptr()
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            eng.characterize_device(ch, cur.cuda_stream)
+        else:   # legacy default stream: the engine's stream, ordered by events on the device
+            eng.engine_wait_stream(0)
+            eng.characterize_device(ch, 0)
+            eng.stream_wait_engine(0)
+        torch.cuda.synchronize(dev)   # the inputs uploaded here live until the kernel has read them
+    return mass, signal, size
+
+
+def characterize_arrays(frames, pos, frame_offset, radius, isotropic=True, scale_factor=1.,
+                        device=0, dtype=None):
+    """Mass, signal and size of the features of a block of frames on the MI355X, by the rule of
+    reference ``find_link.characterize`` (``ctr_characterize_device``).
+
+    frames: ndarray [T, (z,) y, x] or a torch tensor on cuda:``device`` (as for
+    :func:`locate_arrays`); pos: [N, ndim] centres sorted by frame, float64 or int32, ndarray or
+    tensor on the device; frame_offset: [T + 1] int64, rows ``[off[t], off[t + 1])`` belong to
+    frame t -- the device tensors of a preceding locate go in as they are.
+    Returns NumPy float64 arrays (mass [N], signal [N], size [N] or [N, ndim])."""
+    mass, signal, size = _characterize_device(frames, pos, frame_offset, radius, isotropic, scale_factor,
+                                              device, dtype)
+    size = size.cpu().numpy()
+    return mass.cpu().numpy(), signal.cpu().numpy(), size[:, 0] if isotropic else size
+
+
+def characterize(coords, image, radius, isotropic=True, scale_factor=None, device=0):
+    """Reference ``find_link.characterize`` (find_link.py:44-79) on the MI355X: dict with ``mass``,
+    ``signal`` and ``size`` (isotropic) or ``size_z`` / ``size_y`` / ``size_x`` of the features at
+    ``coords`` [N, ndim] of one frame.  ``scale_factor=None`` reads
+    ``image.metadata['scale_factor']`` when there is one, else 1."""
+    if scale_factor is None:
+        try:
+            scale_factor = image.metadata['scale_factor']
+        except (AttributeError, KeyError):
+            scale_factor = 1.
+    _lib.default_engine(device)     # EngineError without a library or a GPU
+    image = np.asarray(image)
+    coords = np.asarray(coords, dtype=np.float64).reshape(-1, image.ndim)
+    radius = validate_tuple(radius, image.ndim)
+    mass, signal, size = characterize_arrays(image[None], coords, [0, len(coords)], radius, isotropic,
+                                             scale_factor, device)
+    result = dict(mass=mass, signal=signal)
+    if isotropic:
+        result['size'] = size
+    else:
+        for a, key in enumerate(_size_columns(image.ndim, False)):
+            result[key] = size[:, a].copy()
+    return result
+
+
+def locate(frames, separation, diameter=None, minmass=0, percentile=64, margin=None, precise=True,
+           device=0, dtype=None):
+    """Features of a block of frames with their mass, signal and size: :func:`locate_maxima`,
+    then :func:`characterize_arrays` with the positions still on the device, then the rows with
+    ``mass >= minmass`` (reference ``find_link``, find_link.py:927-971, without the relocation).
+
+    ``diameter`` defaults to ``separation``; the mask radius is ``int(diameter // 2)`` per axis,
+    the sizes are per axis when a diameter is given and anisotropic, and ``margin`` defaults to
+    ``max(diameter // 2, separation // 2 - 1)`` per axis.  Returns a DataFrame with the columns
+    (z,) y, x, mass, signal, size (or size_z, size_y, size_x), frame, rows as
+    :func:`locate_maxima` orders them; these are the start values ``refine_leastsq`` wants."""
+    if not hasattr(frames, 'shape'):
+        frames = np.asarray(frames)
+    shape = tuple(frames.shape)
+    ndim = len(shape) - 1
+    if ndim not in (2, 3):
+        raise ValueError("frames must be [T, (z,) y, x]")
+    separation = validate_tuple(separation, ndim)
+    # find_link.py:923: the isotropy is that of the diameter AS GIVEN (none given: isotropic)
+    isotropic = not hasattr(diameter, '__iter__') or all(d == diameter[0] for d in diameter)
+    diameter = separation if diameter is None else validate_tuple(diameter, ndim)
+    radius = tuple(int(d // 2) for d in diameter)
+    if margin is None:
+        margin = tuple(int(max(d // 2, s // 2 - 1)) for d, s in zip(diameter, separation))
+    margin = validate_tuple(margin, ndim)
+    if any(n <= 2 * m for n, m in zip(shape[1:], margin)):
+        raise ValueError("the margin %s leaves nothing of frames of shape %s: use a smaller diameter or "
+                         "separation" % (margin, shape[1:]))
+    _lib.default_engine(device)     # EngineError without a library or a GPU
+    t, pix, pos, offset, _ = locate_arrays(frames, separation, percentile, margin, precise, device, dtype,
+                                           _on_device=True)
+    mass, signal, size = _characterize_device(t, pos, offset, radius, isotropic, 1., device, pix)
+    result = pd.DataFrame(pos.cpu().numpy().astype(np.float64), columns=['z', 'y', 'x'][3 - ndim:])
+    result['mass'] = mass.cpu().numpy()
+    result['signal'] = signal.cpu().numpy()
+    size = size.cpu().numpy()
+    for a, key in enumerate(_size_columns(ndim, isotropic)):
+        result[key] = size[:, a]
+    result['frame'] = np.repeat(np.arange(len(frames), dtype=np.int64), np.diff(offset.cpu().numpy()))
+    return result[result['mass'] >= minmass].reset_index(drop=True)

@@ -324,6 +324,47 @@ typedef struct ctr_locate {
 } ctr_locate;
 int ctr_locate_maxima_device(ctr_handle* h, const ctr_locate* l, void* hip_stream);
 
+/* Mass, signal and size of located features on the device: the rule of reference
+ * find_link.characterize (find_link.py:44-79), the link between
+ * ctr_locate_maxima_device and the start values of a refinement.  Per feature with centre c
+ * (any float64; integer when it comes from ctr_locate.pos_out) and integer radius per axis:
+ *   window: corner int(round(c - radius)) per axis (half to even), shape 2 radius + 1; pixels
+ *     beyond the frame count as 0 (masks.py:9-27);
+ *   pixel mask: sum(((idx - (c - corner)) / radius)^2) <= 1 on the unrounded centre, edge
+ *     included (masks.py:71-120), evaluated as the refine kernels evaluate it;
+ *   mass = sum(window mask) / scale_factor, signal = max(window mask) / scale_factor: masked-out
+ *     and padded pixels are zeros that take part in the maximum;
+ *   weights over the window offsets k (from the centre of the WINDOW), support
+ *     sum((k / radius)^2) <= 1 (trackpy's r_squared_mask / x_squared_masks):
+ *     isotropic: size = sqrt(sum(sum_a(k_a^2) window mask) / mass), size[N];
+ *     otherwise: size_a = sqrt(ndim sum(k_a^2 window mask) / mass), size[N, ndim].
+ *   Integer frames: the sums are exact 64-bit integers, then one float64 division and one
+ *   square root.  Float frames: sums in float64.  mass 0 gives size NaN, a negative quotient NaN.
+ * Rows [frame_offset[t], frame_offset[t+1]) are the features of frame t (what ctr_locate
+ * writes).  Exactly one of pos / pos_i32 is non-NULL.  The descriptor is checked before the
+ * handle: with a NULL handle a bad descriptor is reported through the last error of the NULL
+ * handle and a good one gives CTR_ERR_INVALID ("null handle").
+ * Device pointers; asynchronous on `hip_stream` (NULL = the handle's stream). */
+typedef struct ctr_characterize {
+  int32_t ndim;                /* 2 or 3 */
+  int32_t frame_dtype;         /* CTR_DTYPE_* */
+  int64_t n_frames;
+  int64_t shape[CTR_MAX_NDIM]; /* (z,) y, x */
+  int64_t radius[CTR_MAX_NDIM];    /* per axis, >= 0 */
+  int32_t isotropic;           /* != 0: one size per feature */
+  int32_t reserved0;
+  double scale_factor;         /* divides mass and signal; not 0 (reference default: 1) */
+  const void* frames;          /* [n_frames, *shape] */
+  int64_t n_features;
+  const int64_t* frame_offset; /* [n_frames + 1] */
+  const double* pos;           /* [N, ndim] centres (z,) y, x, or NULL */
+  const int32_t* pos_i32;      /* [N, ndim] integer centres (ctr_locate.pos_out), or NULL */
+  double* mass;                /* [N] out */
+  double* signal;              /* [N] out */
+  double* size;                /* [N] (isotropic) or [N, ndim] out */
+} ctr_characterize;
+int ctr_characterize_device(ctr_handle* h, const ctr_characterize* c, void* hip_stream);
+
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
  * several batches in flight hand finished batches on (e.g. to the result gather) from the host
