@@ -14,10 +14,11 @@ from .utils import ArrayReader, RefineException
 from . import constraints, artificial, link
 
 link_df = link.link
+link_arrays = link.link_arrays
 
 __all__ = ['refine_leastsq', 'find_clusters', 'grey_dilation', 'locate_maxima',
            'characterize', 'characterize_arrays', 'locate',
-           'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'FitFunctions', 'constraints',
+           'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'link_arrays', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',
            'write_back']
 

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 IPC_HANDLE_BYTES = 128
 MAX_NDIM = 3
 MAX_NOISE_SIZE = 4.0
@@ -128,6 +128,20 @@ class Characterize(C.Structure):
         ('frames', C.c_void_p), ('n_features', C.c_int64), ('frame_offset', C.c_void_p),
         ('pos', C.c_void_p), ('pos_i32', C.c_void_p),
         ('mass', C.c_void_p), ('signal', C.c_void_p), ('size', C.c_void_p),
+    ]
+
+
+LINK_OK, LINK_OVERSIZE, LINK_CAPACITY = 0, 1, 2   # ctr_link.status[0]
+LINK_MAX_SOURCES, LINK_MAX_DESTINATIONS = 30, 64
+
+
+class Link(C.Structure):
+    """``ctr_link`` (include/ctrefine.h): frame-to-frame linking on the device."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('memory', C.c_int32), ('n_levels', C.c_int64),
+        ('n_features', C.c_int64), ('search_range', C.c_double * MAX_NDIM),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('particle', C.c_void_p),
+        ('n_tracks', C.c_void_p), ('status', C.c_void_p),
     ]
 
 

@@ -18,7 +18,8 @@ EXPORTS = ('ctr_abi_version', 'ctr_create', 'ctr_destroy', 'ctr_last_error',
            'ctr_plan_create', 'ctr_plan_destroy', 'ctr_refine_batch_device',
            'ctr_frame_max_device', 'ctr_synchronize', 'ctr_last_kernel_ms',
            'ctr_find_clusters', 'ctr_engine_wait_stream', 'ctr_stream_wait_engine',
-           'ctr_draw_frames_device', 'ctr_locate_maxima_device', 'ctr_characterize_device', 'ctr_query_done', 'ctr_ipc_alloc', 'ctr_ipc_open',
+           'ctr_draw_frames_device', 'ctr_locate_maxima_device', 'ctr_characterize_device', 'ctr_link_device',
+           'ctr_query_done', 'ctr_ipc_alloc', 'ctr_ipc_open',
            'ctr_ipc_probe', 'ctr_ipc_read', 'ctr_ipc_close', 'ctr_ipc_free')
 
 _lib = None
@@ -113,6 +114,9 @@ def load():
         if hasattr(lib, 'ctr_characterize_device'):   # (absent from libraries built before it existed)
             lib.ctr_characterize_device.argtypes = [C.c_void_p, P(_abi.Characterize), C.c_void_p]
             lib.ctr_characterize_device.restype = C.c_int
+        if hasattr(lib, 'ctr_link_device'):   # (absent from libraries built before it existed)
+            lib.ctr_link_device.argtypes = [C.c_void_p, P(_abi.Link), C.c_void_p]
+            lib.ctr_link_device.restype = C.c_int
         lib.ctr_query_done.argtypes = [C.c_void_p]
         lib.ctr_query_done.restype = C.c_int
         lib.ctr_ipc_alloc.argtypes = [C.c_void_p, C.c_int64, P(C.c_void_p), C.c_void_p]
@@ -231,6 +235,11 @@ class Engine(object):
         """``ctr_characterize_device``: ``desc`` is an ``_abi.Characterize`` with device pointers."""
         self._check(self._lib.ctr_characterize_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
                     'ctr_characterize_device')
+
+    def link_device(self, desc, stream=None):
+        """``ctr_link_device``: ``desc`` is an ``_abi.Link`` with device pointers."""
+        self._check(self._lib.ctr_link_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
+                    'ctr_link_device')
 
     def query_done(self):
         """True when the last ``refine_batch_device`` call of this engine has finished on the

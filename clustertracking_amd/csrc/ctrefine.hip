@@ -110,6 +110,10 @@ struct ctr_handle {
   hipStream_t side[NSIDE] = {};
   hipEvent_t ev_fork = nullptr, ev_gate = nullptr, ev_order = nullptr, ev_join[NSIDE] = {};
   int* d_counter = nullptr;       // work counters of the small-kernel launches
+  // ctr_link_device: grow-only scratch and the end of the last call (calls share the scratch)
+  void* d_link = nullptr;
+  size_t d_link_bytes = 0;
+  hipEvent_t ev_link = nullptr;
 };
 
 namespace {
@@ -458,6 +462,8 @@ void ctr_destroy(ctr_handle* h) {
   if (h->ev_done) (void)hipEventDestroy(h->ev_done);
   for (auto& ev : h->ev_join) if (ev) (void)hipEventDestroy(ev);
   if (h->d_counter) (void)hipFree(h->d_counter);
+  if (h->d_link) (void)hipFree(h->d_link);
+  if (h->ev_link) (void)hipEventDestroy(h->ev_link);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1011,6 +1017,28 @@ int ctr_characterize_device(ctr_handle* h, const ctr_characterize* c, void* hip_
   HIP_TRY(h, hipSetDevice(h->device));
   rc = ctr_characterize_launch(c, true, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
   if (rc != CTR_OK) return fail(h, rc, std::string("ctr_characterize_device: ") + msg);
+  return CTR_OK;
+}
+
+int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream) {
+  // the descriptor first, as ctr_characterize_device
+  const char* msg = "";
+  size_t need = 0;
+  int rc = ctr_link_launch(l, nullptr, &need, nullptr, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_link_device: ") + msg);
+  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_link_device: null handle");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  if (!h->ev_link) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_link, hipEventDisableTiming));
+  else HIP_TRY(h, hipStreamWaitEvent(s, h->ev_link, 0));
+  if (need > h->d_link_bytes) {
+    if (h->d_link) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->d_link); h->d_link = nullptr; h->d_link_bytes = 0; }
+    if (hipMalloc(&h->d_link, need) != hipSuccess) return fail(h, CTR_ERR_NOMEM, "ctr_link_device: cannot allocate the scratch on the device");
+    h->d_link_bytes = need;
+  }
+  rc = ctr_link_launch(l, h->d_link, nullptr, s, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_link_device: ") + msg);
+  HIP_TRY(h, hipEventRecord(h->ev_link, s));
   return CTR_OK;
 }
 

@@ -1,0 +1,104 @@
+// tu_link.hip -- frame-to-frame linking (ctr_link_device; link_kernels.h).
+// Distances are compared with the host linker's: no floating-point contraction in this unit.
+#pragma clang fp contract(off)
+
+#include <cmath>
+#include <cstdint>
+
+#include "kargs.h"
+
+namespace {
+
+#include "device_common.h"
+#include "link_kernels.h"
+
+constexpr size_t LNK_ALIGN = 256;
+
+size_t carve(size_t& at, size_t bytes) {
+  const size_t here = at;
+  at += (bytes + LNK_ALIGN - 1) / LNK_ALIGN * LNK_ALIGN;
+  return here;
+}
+
+// lays the scratch arrays out from `base` (nullptr: only the size is wanted)
+size_t layout(LinkArgs& a, char* base, long long n, int ndim, long long n_levels) {
+  size_t at = 0;
+  const size_t N = (size_t)(n > 0 ? n : 1), L = (size_t)n_levels + 1;
+  // the words that every call zeroes come first, in one block
+  a.used = (int*)(base + carve(at, N * sizeof(int)));
+  a.nbirth = (int*)(base + carve(at, L * sizeof(int)));
+  const size_t zeroed = at;
+  a.spos = (double*)(base + carve(at, N * ndim * sizeof(double)));
+  a.cand_d2 = (double*)(base + carve(at, N * LNK_MAXC * sizeof(double)));
+  a.cand_row = (int*)(base + carve(at, N * LNK_MAXC * sizeof(int)));
+  int** per_row[] = {&a.ncand, &a.link, &a.lab_d, &a.lab_s, &a.cnt_s, &a.head_d, &a.head_s,
+                     &a.next_d, &a.next_s, &a.roots, &a.rank, &a.anc};
+  for (int** p : per_row) *p = (int*)(base + carve(at, N * sizeof(int)));
+  a.base = (long long*)(base + carve(at, L * sizeof(long long)));
+  if (!base) return at;
+  return zeroed;
+}
+
+template <int ND>
+void run(const LinkArgs& a, hipStream_t s) {
+  const unsigned rows = (unsigned)((a.n + LNK_THREADS - 1) / LNK_THREADS);
+  hipLaunchKernelGGL(link_prep_kernel<ND>, dim3(rows), dim3(LNK_THREADS), 0, s, a);
+  const int last = a.n_levels;
+  if (last > 1) {
+    if (a.memory == 0) {
+      hipLaunchKernelGGL(link_cand_kernel<ND>, dim3(rows), dim3(LNK_THREADS), 0, s, a, 1, last);
+      hipLaunchKernelGGL(link_solve_kernel, dim3((unsigned)(last - 1)), dim3(LNK_THREADS), 0, s, a, 1);
+    } else {
+      // level t reads the `used` flags level t - 1 wrote: queued level by level.  The host does
+      // not know the levels' sizes (frame_offset is on the device): a fixed grid strides over them
+      const unsigned per_level = rows < 64u ? rows : 64u;
+      for (int t = 1; t < last; ++t) {
+        hipLaunchKernelGGL(link_cand_kernel<ND>, dim3(per_level), dim3(LNK_THREADS), 0, s, a, t, t + 1);
+        hipLaunchKernelGGL(link_solve_kernel, dim3(1), dim3(LNK_THREADS), 0, s, a, t);
+      }
+    }
+  }
+  hipLaunchKernelGGL(link_rank_kernel<ND>, dim3(rows), dim3(LNK_THREADS), 0, s, a);
+  hipLaunchKernelGGL(link_scan_kernel, dim3(1), dim3(LNK_THREADS), 0, s, a);
+  for (long long reach = 1; reach < a.n_levels - 1; reach *= 2)
+    hipLaunchKernelGGL(link_jump_kernel, dim3(rows), dim3(LNK_THREADS), 0, s, a);
+  hipLaunchKernelGGL(link_ids_kernel, dim3(rows), dim3(LNK_THREADS), 0, s, a);
+}
+
+}  // namespace
+
+int ctr_link_launch(const ctr_link* l, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg) {
+  *msg = "";
+  if (!l) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
+  if (l->ndim != 2 && l->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
+  if (l->n_levels < 0 || l->n_features < 0) { *msg = "negative counts"; return CTR_ERR_INVALID; }
+  if (l->memory < 0) { *msg = "memory must be >= 0"; return CTR_ERR_INVALID; }
+  for (int d = 0; d < l->ndim; ++d)
+    if (!(l->search_range[d] > 0.) || std::isinf(l->search_range[d])) { *msg = "search_range must be a positive number"; return CTR_ERR_INVALID; }
+  if (l->n_features > 0x7ffffff0LL || l->n_levels > 0x7ffffff0LL) { *msg = "too many features or levels for one call"; return CTR_ERR_INVALID; }
+  if (l->n_features > 0 && (l->n_levels < 1 || !l->pos || !l->frame_offset)) { *msg = "features without levels, pos or frame_offset"; return CTR_ERR_INVALID; }
+  if (l->n_features > 0 && (!l->particle || !l->n_tracks || !l->status)) { *msg = "null output"; return CTR_ERR_INVALID; }
+  LinkArgs a = {};
+  if (scratch_bytes) *scratch_bytes = layout(a, nullptr, l->n_features, l->ndim, l->n_levels);
+  if (!scratch) return CTR_OK;
+  if (l->status && hipMemsetAsync(l->status, 0, 4 * sizeof(int32_t), s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
+  if (l->n_tracks && hipMemsetAsync(l->n_tracks, 0, sizeof(int64_t), s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
+  if (l->n_features == 0) return CTR_OK;
+  const size_t zeroed = layout(a, (char*)scratch, l->n_features, l->ndim, l->n_levels);
+  if (hipMemsetAsync(scratch, 0, zeroed, s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
+  a.ndim = l->ndim;
+  a.memory = l->memory < l->n_levels ? (int)l->memory : (int)l->n_levels;   // a longer memory reaches no further
+  a.n_levels = (int)l->n_levels;
+  a.n = l->n_features;
+  a.pos = l->pos;
+  a.off = (const long long*)l->frame_offset;
+  for (int d = 0; d < 3; ++d) a.sr[d] = d < l->ndim ? l->search_range[d] : 1.;
+  a.particle = (long long*)l->particle;
+  a.n_tracks = (long long*)l->n_tracks;
+  a.status = l->status;
+  if (l->ndim == 2) run<2>(a, s);
+  else run<3>(a, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { *msg = hipGetErrorString(e); return CTR_ERR_DEVICE; }
+  return CTR_OK;
+}

@@ -19,6 +19,9 @@ restates, vectorised per frame pair:
   position (``_sort_key_spl_dpl``, ``find_link.py:379-383,701-712``);
 * unmatched old features stay candidates for ``memory`` more frames at their
   last position (``find_link.py:594-610,716-732``).
+
+The host path above is the default.  ``engine='device'`` (and :func:`link_arrays`) runs the same
+rule on the MI355X (``ctr_link_device``); there is no fallback from it.
 """
 import numpy as np
 from scipy.optimize import linear_sum_assignment
@@ -26,6 +29,7 @@ from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 from scipy.spatial import cKDTree
 
+from . import _abi, _lib
 from .utils import guess_pos_columns, validate_tuple
 
 MAX_NEIGHBORS = 10      # find_link.py:586
@@ -68,14 +72,106 @@ def _assign(n_src, n_dst, cand_src, cand_dst, cand_d):
     return link
 
 
-def link_levels(levels, search_range, memory=0):
+def _check_engine(engine):
+    if engine not in ('host', 'device'):
+        raise ValueError("engine must be 'host' or 'device', not %r" % (engine,))
+
+
+def link_arrays(pos, frame_offset, search_range, memory=0, device=0, _on_device=False):
+    """Track ids of a level-sorted position table on the MI355X (``ctr_link_device``): the rule
+    of :func:`link_levels`, the optimum of every sub-network from an exact assignment solver.
+
+    pos: [N, ndim] float64, ndarray or a torch tensor on cuda:``device``; frame_offset: [T + 1]
+    int64, rows ``[off[t], off[t + 1])`` are level t (the tensors of a preceding locate go in as
+    they are).  Returns int64 ids [N] as an ndarray (``_on_device``, internal: as the tensor).
+    Raises :class:`SubnetOversizeException` for a sub-network of more than 30 sources and
+    ``EngineError`` for one of more than 64 destinations (the solver's capacity), or when there
+    is no library or no GPU."""
+    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
+    import torch
+    dev = torch.device('cuda', device)
+    if int(memory) != memory or memory < 0:
+        raise ValueError("memory must be a non-negative integer")
+    with torch.cuda.device(dev):
+        if isinstance(pos, torch.Tensor):
+            if pos.device != dev or pos.dtype != torch.float64:
+                raise ValueError("a position tensor is float64 on cuda:%d" % device)
+            pos_t = pos.contiguous()
+        else:
+            arr = np.ascontiguousarray(pos, dtype=np.float64)
+            if arr.ndim != 2:
+                arr = arr.reshape(-1, len(np.atleast_1d(search_range)))
+            pos_t = torch.from_numpy(arr).to(dev)
+        if pos_t.dim() != 2 or pos_t.shape[1] not in (2, 3):
+            raise ValueError("pos must be [N, 2] or [N, 3]")
+        n, ndim = int(pos_t.shape[0]), int(pos_t.shape[1])
+        sr = validate_tuple(search_range, ndim)
+        if not all(np.isfinite(s) and s > 0 for s in sr):
+            raise ValueError("search_range must be positive")
+        if isinstance(frame_offset, torch.Tensor):
+            if frame_offset.device != dev or frame_offset.dtype != torch.int64 or frame_offset.dim() != 1:
+                raise ValueError("a frame_offset tensor is int64 [T + 1] on cuda:%d" % device)
+            off_t = frame_offset.contiguous()
+        else:
+            off = np.ascontiguousarray(frame_offset, dtype=np.int64).reshape(-1)
+            if len(off) and (off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0)):
+                raise ValueError("frame_offset must rise from 0 to the number of features")
+            off_t = torch.from_numpy(off).to(dev)
+        n_levels = max(int(off_t.numel()) - 1, 0)
+        if n and not n_levels:
+            raise ValueError("features without levels")
+        particle = torch.empty(n, dtype=torch.int64, device=dev)
+        if n == 0:          # nothing to launch (and an empty tensor has no address to pass)
+            return particle if _on_device else particle.cpu().numpy()
+        n_tracks = torch.empty(1, dtype=torch.int64, device=dev)
+        status = torch.empty(4, dtype=torch.int32, device=dev)
+        d = _abi.Link()
+        d.ndim, d.memory, d.n_levels, d.n_features = ndim, int(memory), n_levels, n
+        for a in range(ndim):
+            d.search_range[a] = float(sr[a])
+        d.pos, d.frame_offset = pos_t.data_ptr(), off_t.data_ptr()
+        d.particle, d.n_tracks, d.status = particle.data_ptr(), n_tracks.data_ptr(), status.data_ptr()
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            eng.link_device(d, cur.cuda_stream)
+        else:   # legacy default stream: the engine's stream, ordered by events on the device
+            eng.engine_wait_stream(0)
+            eng.link_device(d, 0)
+            eng.stream_wait_engine(0)
+        code, level, size, _ = (int(v) for v in status.cpu())   # the one synchronisation of the call
+    if code == _abi.LINK_OVERSIZE:
+        raise SubnetOversizeException("Subnetwork contains %d points (level %d)" % (size, level))
+    if code == _abi.LINK_CAPACITY:
+        raise _lib.EngineError("ctr_link_device: a sub-network of level %d has %d destinations, the "
+                               "device solver takes %d (CTR_ERR_UNSUPPORTED)"
+                               % (level, size, _abi.LINK_MAX_DESTINATIONS))
+    if code != _abi.LINK_OK:
+        raise _lib.EngineError("ctr_link_device: unknown status %d" % code)
+    return particle if _on_device else particle.cpu().numpy()
+
+
+def _link_levels_device(levels, ndim, search_range, memory, device):
+    counts = [len(c) for c in levels]
+    offs = np.r_[0, np.cumsum(counts)].astype(np.int64)
+    pos = (np.concatenate([c.reshape(-1, ndim) for c in levels]) if levels else np.zeros((0, ndim)))
+    ids = link_arrays(pos, offs, search_range, memory, device)
+    return [ids[a:b] for a, b in zip(offs[:-1], offs[1:])]
+
+
+def link_levels(levels, search_range, memory=0, engine='host', device=0):
     """Link a sequence of coordinate arrays ``[n_t, ndim]`` (one per frame).
-    Returns a list of integer id arrays aligned with the input."""
+    Returns a list of integer id arrays aligned with the input.  ``engine='device'``: on the
+    MI355X through :func:`link_arrays` (no fallback: ``EngineError`` without a GPU)."""
+    _check_engine(engine)
     levels = [np.asarray(c, dtype=np.float64) for c in levels]
     if len(levels) == 0:
+        if engine == 'device':
+            _lib.default_engine(device)
         return []
     ndim = levels[0].shape[1] if levels[0].ndim == 2 else len(np.atleast_1d(search_range))
     sr = np.asarray(validate_tuple(search_range, ndim), dtype=np.float64)
+    if engine == 'device':
+        return _link_levels_device(levels, ndim, tuple(sr), memory, device)
     next_id = 0
     ids_out = []
     # sources of the next level: previous level + remembered lost features
@@ -128,8 +224,10 @@ def link_levels(levels, search_range, memory=0):
     return ids_out
 
 
-def link(f, search_range, memory=0, pos_columns=None, t_column='frame'):
-    """Return a copy of ``f`` (sorted by frame) with a ``particle`` column."""
+def link(f, search_range, memory=0, pos_columns=None, t_column='frame', engine='host', device=0):
+    """Return a copy of ``f`` (sorted by frame) with a ``particle`` column.  ``engine='device'``
+    links on the MI355X (:func:`link_arrays`); the host path is the default."""
+    _check_engine(engine)
     if pos_columns is None:
         pos_columns = guess_pos_columns(f)
     result = f.sort_values(t_column, kind='stable').copy()
@@ -137,6 +235,6 @@ def link(f, search_range, memory=0, pos_columns=None, t_column='frame'):
     pos = result[pos_columns].values
     uniq, starts = np.unique(frames, return_index=True)
     stops = np.r_[starts[1:], len(frames)]
-    ids = link_levels([pos[a:b] for a, b in zip(starts, stops)], search_range, memory)
+    ids = link_levels([pos[a:b] for a, b in zip(starts, stops)], search_range, memory, engine, device)
     result['particle'] = np.concatenate(ids) if len(ids) else np.zeros(0, dtype=np.int64)
     return result

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CTR_ABI_VERSION 7
+#define CTR_ABI_VERSION 8
 #define CTR_MAX_NDIM 3
 #define CTR_MAX_PARAMS 12 /* background, signal, <=3 positions, <=3 sizes, profile parameters (ring, disc: 1;
                               inv_series_<N>: N + 1, as many as fit: N <= 6 in 2D isotropic, <= 3 in 3D anisotropic) */
@@ -364,6 +364,53 @@ typedef struct ctr_characterize {
   double* size;                /* [N] (isotropic) or [N, ndim] out */
 } ctr_characterize;
 int ctr_characterize_device(ctr_handle* h, const ctr_characterize* c, void* hip_stream);
+
+/* Frame-to-frame linking on the device: the rule of the reference's Linker (Crocker-Grier with
+ * sub-network resolution and memory, find_link.py:579-733), what link.link_levels
+ * does on the host.  Rows [frame_offset[t], frame_offset[t+1]) of `pos` are the features of level t.
+ * Per level t >= 1, sources = the rows of level t - 1 followed by the remembered rows,
+ * destinations = the rows of level t, all positions divided per axis by search_range:
+ *   candidates: for every destination its up to 10 nearest sources at Euclidean distance
+ *     <= 1 + 1e-7 (float64, no contraction); which source is kept when the 10th and 11th are at
+ *     exactly the same distance is undefined, as in the reference;
+ *   sub-networks: connected components of the candidate graph;
+ *   inside a sub-network: the set of links (each source and each destination at most once, along
+ *     candidates only) that minimises sum(d^2) + 1 per unlinked source + 1 per missing link, i.e.
+ *     maximises sum(2 - d^2); an exact assignment solver, not the reference's order-dependent
+ *     recursion.  More than CTR_LINK_MAX_SOURCES sources in a sub-network that is not 1 x 1 is the
+ *     reference's SubnetOversizeException: status CTR_LINK_OVERSIZE.  More than
+ *     CTR_LINK_MAX_DESTINATIONS destinations is beyond the solver (what CTR_ERR_UNSUPPORTED is for
+ *     a synchronous call): status CTR_LINK_CAPACITY;
+ *   ids: level 0 gets 0 .. n - 1 in row order; a linked destination takes its source's id; the
+ *     unlinked destinations of a level start tracks, numbered from the running count in
+ *     lexicographic order of their unscaled position (equal positions in row order);
+ *   memory: an unlinked source of level t - 1 is remembered at its last position and stays a
+ *     source for `memory` more levels.
+ * status[0] = CTR_LINK_*, and for a non-zero one status[1] = the level and status[2] = the size
+ * (sources or destinations) it was seen at; status[3] = 0.  With a non-zero status `particle` and
+ * `n_tracks` are not a result.  The call zeroes the status itself.
+ * The features of a level may be any number that fits in memory (the candidate search of a level
+ * costs its destinations times its sources).  Scratch belongs to the handle: calls of one handle
+ * are ordered on the device whatever streams they are given.
+ * The descriptor is checked before the handle, as for ctr_characterize_device.
+ * Device pointers; asynchronous on `hip_stream` (NULL = the handle's stream): read status after
+ * synchronising. */
+enum { CTR_LINK_OK = 0, CTR_LINK_OVERSIZE = 1, CTR_LINK_CAPACITY = 2 };
+#define CTR_LINK_MAX_SOURCES 30
+#define CTR_LINK_MAX_DESTINATIONS 64
+typedef struct ctr_link {
+  int32_t ndim;                /* 2 or 3 */
+  int32_t memory;              /* >= 0 */
+  int64_t n_levels;
+  int64_t n_features;          /* N */
+  double search_range[CTR_MAX_NDIM]; /* per axis, > 0 */
+  const double* pos;           /* [N, ndim] (z,) y, x; rows sorted by level */
+  const int64_t* frame_offset; /* [n_levels + 1] (what ctr_locate writes) */
+  int64_t* particle;           /* [N] out: track ids */
+  int64_t* n_tracks;           /* [1] out */
+  int32_t* status;             /* [4] out */
+} ctr_link;
+int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream);
 
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
