@@ -131,6 +131,21 @@ class Characterize(C.Structure):
     ]
 
 
+PRE_LOWPASS, PRE_BANDPASS, PRE_PREPROCESS, PRE_SCALE = 0, 1, 2, 3   # ctr_preprocess.mode
+PRE_AUTO, PRE_BAND_PLANE, PRE_TWICE = 0, 1, 2                        # ctr_preprocess.strategy
+
+
+class Preprocess(C.Structure):
+    """``ctr_preprocess`` (include/ctrefine.h): bandpass, lowpass and rescaling of whole frames."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('frame_dtype', C.c_int32), ('n_frames', C.c_int64),
+        ('shape', C.c_int64 * MAX_NDIM), ('mode', C.c_int32), ('strategy', C.c_int32),
+        ('n_taps', C.c_int32 * MAX_NDIM), ('box', C.c_int32 * MAX_NDIM),
+        ('taps', C.c_void_p * MAX_NDIM), ('threshold', C.c_double),
+        ('frames', C.c_void_p), ('out', C.c_void_p), ('scale_factor', C.c_void_p),
+    ]
+
+
 LINK_OK, LINK_OVERSIZE, LINK_CAPACITY = 0, 1, 2   # ctr_link.status[0]
 LINK_MAX_SOURCES, LINK_MAX_DESTINATIONS = 30, 64
 

@@ -19,6 +19,7 @@ EXPORTS = ('ctr_abi_version', 'ctr_create', 'ctr_destroy', 'ctr_last_error',
            'ctr_frame_max_device', 'ctr_synchronize', 'ctr_last_kernel_ms',
            'ctr_find_clusters', 'ctr_engine_wait_stream', 'ctr_stream_wait_engine',
            'ctr_draw_frames_device', 'ctr_locate_maxima_device', 'ctr_characterize_device', 'ctr_link_device',
+           'ctr_preprocess_device',
            'ctr_query_done', 'ctr_ipc_alloc', 'ctr_ipc_open',
            'ctr_ipc_probe', 'ctr_ipc_read', 'ctr_ipc_close', 'ctr_ipc_free')
 
@@ -117,6 +118,9 @@ def load():
         if hasattr(lib, 'ctr_link_device'):   # (absent from libraries built before it existed)
             lib.ctr_link_device.argtypes = [C.c_void_p, P(_abi.Link), C.c_void_p]
             lib.ctr_link_device.restype = C.c_int
+        if hasattr(lib, 'ctr_preprocess_device'):   # (an addition to ABI 8: absent from earlier builds of it)
+            lib.ctr_preprocess_device.argtypes = [C.c_void_p, P(_abi.Preprocess), C.c_void_p]
+            lib.ctr_preprocess_device.restype = C.c_int
         lib.ctr_query_done.argtypes = [C.c_void_p]
         lib.ctr_query_done.restype = C.c_int
         lib.ctr_ipc_alloc.argtypes = [C.c_void_p, C.c_int64, P(C.c_void_p), C.c_void_p]
@@ -240,6 +244,15 @@ class Engine(object):
         """``ctr_link_device``: ``desc`` is an ``_abi.Link`` with device pointers."""
         self._check(self._lib.ctr_link_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
                     'ctr_link_device')
+
+    def preprocess_device(self, desc, stream=None):
+        """``ctr_preprocess_device``: ``desc`` is an ``_abi.Preprocess`` with device pointers."""
+        if not hasattr(self._lib, 'ctr_preprocess_device'):
+            raise EngineError("libctrefine.so does not export ctr_preprocess_device: rebuild it")
+        rc = self._lib.ctr_preprocess_device(self._h, C.byref(desc), C.c_void_p(stream or 0))
+        if rc == _abi.ERR_UNSUPPORTED:      # taps or a box beyond the LDS tile (DESIGN.md 7b)
+            raise EngineError("ctr_preprocess_device: %s" % (self._lib.ctr_last_error(self._h) or b'').decode())
+        self._check(rc, 'ctr_preprocess_device')
 
     def query_done(self):
         """True when the last ``refine_batch_device`` call of this engine has finished on the

@@ -1020,6 +1020,18 @@ int ctr_characterize_device(ctr_handle* h, const ctr_characterize* c, void* hip_
   return CTR_OK;
 }
 
+int ctr_preprocess_device(ctr_handle* h, const ctr_preprocess* p, void* hip_stream) {
+  // the descriptor first, as ctr_characterize_device
+  const char* msg = "";
+  int rc = ctr_preprocess_launch(p, false, nullptr, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_preprocess_device: ") + msg);
+  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_preprocess_device: null handle");
+  HIP_TRY(h, hipSetDevice(h->device));
+  rc = ctr_preprocess_launch(p, true, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_preprocess_device: ") + msg);
+  return CTR_OK;
+}
+
 int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream) {
   // the descriptor first, as ctr_characterize_device
   const char* msg = "";

@@ -124,6 +124,9 @@ int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // feature characterisation (tu_characterize.hip, characterize_kernels.h): checks the descriptor
 // and, with launch_it, queues the kernel on `s`.  CTR_OK or an error code with a static message.
 int ctr_characterize_launch(const ctr_characterize* c, bool launch_it, hipStream_t s, const char** msg);
+// preprocessing (tu_preprocess.hip, preprocess_kernels.h): checks the descriptor and, with
+// launch_it, queues the kernels on `s`.  CTR_OK or an error code with a static message.
+int ctr_preprocess_launch(const ctr_preprocess* p, bool launch_it, hipStream_t s, const char** msg);
 // linking (tu_link.hip, link_kernels.h): checks the descriptor, reports the scratch it needs in
 // *scratch_bytes and, with a scratch block, queues the whole pipeline on `s`.
 int ctr_link_launch(const ctr_link* l, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg);

@@ -226,19 +226,33 @@ def _device_frames(frames, device, dtype):
 
 
 def locate_arrays(frames, separation, percentile=64, margin=None, precise=True, device=0,
-                  dtype=None, capacity=None, _on_device=False):
+                  dtype=None, capacity=None, _on_device=False, noise_size=None, smoothing_size=None,
+                  threshold=None):
     """The device pass behind :func:`locate_maxima`: (positions int32 [N, ndim] in frame order,
     frame_offset int64 [T + 1], per-frame threshold float64 [T]) as NumPy arrays.
     ``capacity``: rows to reserve at first; a larger buffer is taken when the frames hold more.
-    (``_on_device``, internal: the three as torch tensors on the device, preceded by the frames'
-    tensor and pixel type -- what :func:`locate` hands to :func:`characterize_arrays`.)"""
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    t, pix = _device_frames(frames, device, dtype)
-    ndim = t.dim() - 1
+    ``noise_size``, ``smoothing_size``, ``threshold``: see :func:`locate_maxima`.
+    (``_on_device``, internal: the three as torch tensors on the device, preceded by the RAW
+    frames' tensor and pixel type -- what :func:`locate` hands to :func:`characterize_arrays`.)"""
+    if not hasattr(frames, 'shape'):
+        frames = np.asarray(frames)
+    ndim = len(frames.shape) - 1
     if ndim not in (2, 3):
         raise ValueError("frames must be [T, (z,) y, x]")
     separation = validate_tuple(separation, ndim)
+    if noise_size is not None:
+        from . import preprocessing
+        if smoothing_size is None:
+            smoothing_size = separation     # find_link.py:921
+        preprocessing.check_sizes(noise_size, smoothing_size, ndim)
+    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
+    import torch
+    raw_t, raw_pix = _device_frames(frames, device, dtype)
+    if noise_size is None:
+        t, pix = raw_t, raw_pix
+    else:       # find_link.py:957-959: the maxima are those of the preprocessed frames
+        t, _, pix = preprocessing.preprocess_arrays(raw_t, noise_size, smoothing_size, threshold, device, raw_pix,
+                                                    _on_device=True)
     if margin is None:
         margin = tuple(int(s / 2) for s in separation)
     margin = validate_tuple(margin, ndim)
@@ -281,20 +295,27 @@ def locate_arrays(frames, separation, percentile=64, margin=None, precise=True, 
                 break
             capacity = n        # more maxima than rows: run again with room for all of them
         if _on_device:
-            return t, pix, pos[:n], offset, thr[:n_frames]
+            return raw_t, raw_pix, pos[:n], offset, thr[:n_frames]
         return (pos[:n].cpu().numpy(), offset.cpu().numpy(), thr[:n_frames].cpu().numpy())
 
 
 def locate_maxima(frames, separation, percentile=64, margin=None, precise=True, device=0,
-                  dtype=None):
+                  dtype=None, noise_size=None, smoothing_size=None, threshold=None):
     """Local maxima of every frame of a block by the rule of reference ``grey_dilation``,
     on the MI355X.
 
     frames: ndarray [T, (z,) y, x] or a torch tensor already on cuda:``device`` (for example
     ``device.draw_frames`` output); ``dtype=np.uint16`` reads an int16 tensor as unsigned.
     Returns a DataFrame with the position columns ((z,) y, x; float64) and ``frame``, rows in
-    frame order and, within a frame, in the order :func:`grey_dilation` returns them."""
-    pos, offset, _ = locate_arrays(frames, separation, percentile, margin, precise, device, dtype)
+    frame order and, within a frame, in the order :func:`grey_dilation` returns them.
+
+    ``noise_size`` given: every frame first goes through ``preprocessing.preprocess`` on the
+    device (bandpass with ``noise_size`` and ``smoothing_size``, default ``separation``, then
+    rescaled into the integer type) as in the reference's ``find_link`` (find_link.py:957-959),
+    and the maxima are those of the preprocessed frames.  ``noise_size=None`` (the default here)
+    takes the frames as they are; the reference's default is ``noise_size=1``."""
+    pos, offset, _ = locate_arrays(frames, separation, percentile, margin, precise, device, dtype,
+                                   noise_size=noise_size, smoothing_size=smoothing_size, threshold=threshold)
     ndim = pos.shape[1]
     cols = ['z', 'y', 'x'][3 - ndim:]
     result = pd.DataFrame(pos.astype(np.float64), columns=cols)
@@ -435,7 +456,7 @@ def characterize(coords, image, radius, isotropic=True, scale_factor=None, devic
 
 
 def locate(frames, separation, diameter=None, minmass=0, percentile=64, margin=None, precise=True,
-           device=0, dtype=None):
+           device=0, dtype=None, noise_size=None, smoothing_size=None, threshold=None):
     """Features of a block of frames with their mass, signal and size: :func:`locate_maxima`,
     then :func:`characterize_arrays` with the positions still on the device, then the rows with
     ``mass >= minmass`` (reference ``find_link``, find_link.py:927-971, without the relocation).
@@ -444,7 +465,12 @@ def locate(frames, separation, diameter=None, minmass=0, percentile=64, margin=N
     the sizes are per axis when a diameter is given and anisotropic, and ``margin`` defaults to
     ``max(diameter // 2, separation // 2 - 1)`` per axis.  Returns a DataFrame with the columns
     (z,) y, x, mass, signal, size (or size_z, size_y, size_x), frame, rows as
-    :func:`locate_maxima` orders them; these are the start values ``refine_leastsq`` wants."""
+    :func:`locate_maxima` orders them; these are the start values ``refine_leastsq`` wants.
+
+    ``noise_size``, ``smoothing_size``, ``threshold``: as for :func:`locate_maxima`, the maxima
+    come from the preprocessed frames, which never leave the device; mass, signal and size come
+    from the RAW frames with a scale factor of 1 (find_link.py:967,994).  The default
+    ``noise_size=None`` skips the preprocessing, where the reference's ``find_link`` defaults to 1."""
     if not hasattr(frames, 'shape'):
         frames = np.asarray(frames)
     shape = tuple(frames.shape)
@@ -462,9 +488,13 @@ def locate(frames, separation, diameter=None, minmass=0, percentile=64, margin=N
     if any(n <= 2 * m for n, m in zip(shape[1:], margin)):
         raise ValueError("the margin %s leaves nothing of frames of shape %s: use a smaller diameter or "
                          "separation" % (margin, shape[1:]))
+    if noise_size is not None:
+        from . import preprocessing
+        preprocessing.check_sizes(noise_size, separation if smoothing_size is None else smoothing_size, ndim)
     _lib.default_engine(device)     # EngineError without a library or a GPU
     t, pix, pos, offset, _ = locate_arrays(frames, separation, percentile, margin, precise, device, dtype,
-                                           _on_device=True)
+                                           _on_device=True, noise_size=noise_size, smoothing_size=smoothing_size,
+                                           threshold=threshold)
     mass, signal, size = _characterize_device(t, pos, offset, radius, isotropic, 1., device, pix)
     result = pd.DataFrame(pos.cpu().numpy().astype(np.float64), columns=['z', 'y', 'x'][3 - ndim:])
     result['mass'] = mass.cpu().numpy()

@@ -365,6 +365,54 @@ typedef struct ctr_characterize {
 } ctr_characterize;
 int ctr_characterize_device(ctr_handle* h, const ctr_characterize* c, void* hip_stream);
 
+/* Preprocessing of whole frames on the device: the reference's lowpass and preprocess
+ * (preprocessing.py:13-75) with trackpy's bandpass, scalefactor_to_gamut and scale_to_gamut
+ * (DESIGN.md 7b), what runs in front of ctr_locate_maxima_device on raw video.  Per frame:
+ *   Gaussian: float64 copy of the frame, then per axis in order correlate1d with the taps of that
+ *     axis (n_taps = 2 lw + 1, SciPy's symmetric order: centre tap, then the pairs
+ *     (x[i - k] + x[i + k]) * w[lw - k] from k = lw down to 1), zero beyond the frame, every
+ *     operation rounded to float64 once.  The taps are the caller's (NumPy's exp, not libm's); a
+ *     single tap of 1 leaves the axis as it is.
+ *   background: copy of the frame IN THE PIXEL TYPE, then per axis in order a box of box[a] (odd)
+ *     over edge-clamped indices: integer pixels trunc(S / box) with S the exact window sum (one
+ *     float64 division, C cast), float pixels the float64 window sum divided and rounded to the
+ *     pixel type.  A box of 1 leaves the axis as it is.
+ *   CTR_PRE_LOWPASS:    out float64 = Gaussian > threshold ? Gaussian : 0
+ *   CTR_PRE_BANDPASS:   out float64 = band >= threshold ? band : 0, band = Gaussian - background
+ *   CTR_PRE_PREPROCESS: scale_factor = max of the integer type / max of that band over the frame
+ *     (one float64 division), out = (integer type)(scale_factor * max(band, 0)), a truncating
+ *     cast.  The integer type is the pixel type, uint8 for float frames.  A frame whose band has
+ *     no pixel above zero is written as zeros, with scale_factor +inf when its maximum is 0.
+ *   CTR_PRE_SCALE:      float frames only, no filter: scale_factor = 255 / max of the frame,
+ *     out = (uint8)(scale_factor * max(pixel, 0)).
+ * Integer frames: every result equals NumPy / SciPy's bit for bit.  Float frames: the background
+ * sums its window in a fixed order, SciPy keeps a running sum, so results agree to rounding.
+ * NaN or infinite pixels have no defined result.
+ * strategy (CTR_PRE_PREPROCESS): how the maximum is known before the first pixel is written:
+ *   CTR_PRE_BAND_PLANE keeps the float64 band in a workspace plane and rescales it,
+ *   CTR_PRE_TWICE runs the stencil twice (maximum, then output); CTR_PRE_AUTO picks.  Same result.
+ * The halo of a tile lives in LDS: taps or boxes whose tile exceeds 64 KiB give CTR_ERR_UNSUPPORTED.
+ * The descriptor is checked before the handle, as for ctr_characterize_device.
+ * Device pointers, taps included; asynchronous on `hip_stream` (NULL = the handle's stream). */
+enum { CTR_PRE_LOWPASS = 0, CTR_PRE_BANDPASS = 1, CTR_PRE_PREPROCESS = 2, CTR_PRE_SCALE = 3 };
+enum { CTR_PRE_AUTO = 0, CTR_PRE_BAND_PLANE = 1, CTR_PRE_TWICE = 2 };
+typedef struct ctr_preprocess {
+  int32_t ndim;                /* 2 or 3 */
+  int32_t frame_dtype;         /* CTR_DTYPE_* */
+  int64_t n_frames;
+  int64_t shape[CTR_MAX_NDIM]; /* (z,) y, x */
+  int32_t mode;                /* CTR_PRE_LOWPASS .. CTR_PRE_SCALE */
+  int32_t strategy;            /* CTR_PRE_AUTO .. CTR_PRE_TWICE */
+  int32_t n_taps[CTR_MAX_NDIM];    /* per axis, odd, >= 1 */
+  int32_t box[CTR_MAX_NDIM];       /* per axis, odd, >= 1 (bandpass, preprocess) */
+  const double* taps[CTR_MAX_NDIM];/* per axis [n_taps[a]], on the device */
+  double threshold;
+  const void* frames;          /* [n_frames, *shape] */
+  void* out;                   /* [n_frames, *shape] out: float64, or the integer type */
+  double* scale_factor;        /* [n_frames] out (preprocess, scale), else NULL */
+} ctr_preprocess;
+int ctr_preprocess_device(ctr_handle* h, const ctr_preprocess* p, void* hip_stream);
+
 /* Frame-to-frame linking on the device: the rule of the reference's Linker (Crocker-Grier with
  * sub-network resolution and memory, find_link.py:579-733), what link.link_levels
  * does on the host.  Rows [frame_offset[t], frame_offset[t+1]) of `pos` are the features of level t.
