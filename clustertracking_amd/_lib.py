@@ -171,11 +171,15 @@ class Engine(object):
 
     __del__ = close
 
-    def _check(self, rc, what):
+    def _check(self, rc, what, too_large=False):
+        """``too_large``: CTR_ERR_UNSUPPORTED of this entry point means a size beyond the device
+        path (an LDS tile over 64 KiB), not a missing feature: ``EngineError``."""
         if rc != _abi.OK:
             msg = (self._lib.ctr_last_error(self._h) or b'').decode()
             if rc == _abi.ERR_INVALID:
                 raise ValueError("%s: %s" % (what, msg))
+            if rc == _abi.ERR_UNSUPPORTED and too_large:
+                raise EngineError("%s: %s" % (what, msg))
             if rc == _abi.ERR_UNSUPPORTED:
                 raise NotImplementedError("%s: %s" % (what, msg))
             raise EngineError("%s failed (%d): %s" % (what, rc, msg))
@@ -233,7 +237,7 @@ class Engine(object):
     def locate_maxima_device(self, loc, stream=None):
         """``ctr_locate_maxima_device``: ``loc`` is an ``_abi.Locate`` with device pointers."""
         self._check(self._lib.ctr_locate_maxima_device(self._h, C.byref(loc), C.c_void_p(stream or 0)),
-                    'ctr_locate_maxima_device')
+                    'ctr_locate_maxima_device', too_large=True)
 
     def characterize_device(self, desc, stream=None):
         """``ctr_characterize_device``: ``desc`` is an ``_abi.Characterize`` with device pointers."""
@@ -249,10 +253,8 @@ class Engine(object):
         """``ctr_preprocess_device``: ``desc`` is an ``_abi.Preprocess`` with device pointers."""
         if not hasattr(self._lib, 'ctr_preprocess_device'):
             raise EngineError("libctrefine.so does not export ctr_preprocess_device: rebuild it")
-        rc = self._lib.ctr_preprocess_device(self._h, C.byref(desc), C.c_void_p(stream or 0))
-        if rc == _abi.ERR_UNSUPPORTED:      # taps or a box beyond the LDS tile (DESIGN.md 7b)
-            raise EngineError("ctr_preprocess_device: %s" % (self._lib.ctr_last_error(self._h) or b'').decode())
-        self._check(rc, 'ctr_preprocess_device')
+        self._check(self._lib.ctr_preprocess_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
+                    'ctr_preprocess_device', too_large=True)
 
     def query_done(self):
         """True when the last ``refine_batch_device`` call of this engine has finished on the

@@ -232,6 +232,7 @@ def locate_arrays(frames, separation, percentile=64, margin=None, precise=True, 
     frame_offset int64 [T + 1], per-frame threshold float64 [T]) as NumPy arrays.
     ``capacity``: rows to reserve at first; a larger buffer is taken when the frames hold more.
     ``noise_size``, ``smoothing_size``, ``threshold``: see :func:`locate_maxima`.
+    ``EngineError``: a separation whose box needs an LDS tile over 64 KiB.
     (``_on_device``, internal: the three as torch tensors on the device, preceded by the RAW
     frames' tensor and pixel type -- what :func:`locate` hands to :func:`characterize_arrays`.)"""
     if not hasattr(frames, 'shape'):
@@ -313,7 +314,9 @@ def locate_maxima(frames, separation, percentile=64, margin=None, precise=True, 
     device (bandpass with ``noise_size`` and ``smoothing_size``, default ``separation``, then
     rescaled into the integer type) as in the reference's ``find_link`` (find_link.py:957-959),
     and the maxima are those of the preprocessed frames.  ``noise_size=None`` (the default here)
-    takes the frames as they are; the reference's default is ``noise_size=1``."""
+    takes the frames as they are; the reference's default is ``noise_size=1``.
+    Raises ``EngineError`` for a separation whose box needs an LDS tile over 64 KiB (2D: a box
+    above 200 pixels for 1-byte, 128 for 2-byte, 79 for 4-byte, 46 for float64 pixels)."""
     pos, offset, _ = locate_arrays(frames, separation, percentile, margin, precise, device, dtype,
                                    noise_size=noise_size, smoothing_size=smoothing_size, threshold=threshold)
     ndim = pos.shape[1]

@@ -71,9 +71,10 @@ def assert_same_ids(levels, sr, memory, got, want):
             last_g[p] = last_w[p] = lv[j]
 
 
-def largest_subnet_sources(levels, sr):
-    """largest number of sources in one sub-network (memory 0), on the host"""
-    best = 0
+def largest_subnet_sources(levels, sr, destinations=False):
+    """largest number of sources in one sub-network (memory 0), on the host; ``destinations``:
+    (sources, destinations) of the sub-network with the most sources + destinations"""
+    best, both = 0, (0, 0)
     for a, b in zip(levels[:-1], levels[1:]):
         if not len(a) or not len(b):
             continue
@@ -87,7 +88,11 @@ def largest_subnet_sources(levels, sr):
         _, comp = connected_components(g, directed=False)
         per = np.bincount(comp[np.unique(src)])
         best = max(best, int(per.max()))
-    return best
+        per_d = np.bincount(comp[np.unique(dst) + len(a)], minlength=len(per))
+        k = int(np.argmax(per + per_d[:len(per)]))
+        if per[k] + per_d[k] > sum(both):
+            both = (int(per[k]), int(per_d[k]))
+    return both if destinations else best
 
 
 @pytest.mark.parametrize('z,name', FIXTURES, ids=[f[1] for f in FIXTURES])
