@@ -114,6 +114,24 @@ __global__ void mark_kernel(const KArgs k, int code) {
 // reference's ids depend on Python set order); the PARTITION is the reference's.
 constexpr int FC_THREADS = 256;
 
+// The scaled squared distance as cKDTree sums it: in axis order, every product rounded before it
+// is added.  Fused into the addition, d * d is not rounded, and a pair at a scaled distance of
+// exactly 1 -- integer positions at a Pythagorean offset of an integer separation, what locate
+// returns -- lands on the other side of `<= 1` ((12/13)^2 + (5/13)^2 is 1.0000000000000002 by
+// the rule and 1.0 fused).  Same guard as in_mask_exact (device_common.h).
+template <int ND>
+__device__ __forceinline__ double scaled_dist2(const double (&p)[ND], const double* __restrict__ q) {
+#pragma clang fp contract(off)
+  double d2 = 0.;
+#pragma unroll
+  for (int a = 0; a < ND; ++a) {
+    const double d = p[a] - q[a];
+    const double dd = d * d;
+    d2 = d2 + dd;
+  }
+  return d2;
+}
+
 template <int ND>
 __global__ void __launch_bounds__(FC_THREADS) find_clusters_kernel(const double* __restrict__ pos,
                                                                    const int32_t* __restrict__ frame_offset,
@@ -139,13 +157,7 @@ __global__ void __launch_bounds__(FC_THREADS) find_clusters_kernel(const double*
       const int mine = __hip_atomic_load(&label[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       int m = mine;
       for (int j = r0; j < r1; ++j) {
-        double d2 = 0.;
-#pragma unroll
-        for (int a = 0; a < ND; ++a) {
-          const double d = p[a] - spos[(size_t)j * ND + a];
-          d2 += d * d;
-        }
-        if (d2 <= 1.) {
+        if (scaled_dist2<ND>(p, spos + (size_t)j * ND) <= 1.) {
           const int lj = __hip_atomic_load(&label[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           m = lj < m ? lj : m;
         }
@@ -168,7 +180,12 @@ __global__ void __launch_bounds__(FC_THREADS) find_clusters_kernel(const double*
 // Streams the frame block once: 16 B per lane per load, one ordered-u64 atomicMax
 // per workgroup.  HBM-bound.
 
+// Order-preserving map of a double to a u64.  A NaN has to win every maximum (NumPy's max
+// propagates it), and by its bits only a NaN with the sign bit clear does: one with the sign bit
+// set -- what 0 * inf, inf - inf and 0 / 0 give on x86 -- would come out below -inf and be lost,
+// together with the maximum its lane had found.  So every NaN is encoded as the positive quiet NaN.
 __device__ __forceinline__ unsigned long long enc_f64(double x) {
+  if (x != x) return 0xfff8000000000000ull;   // = enc of 0x7ff8000000000000, above +inf
   unsigned long long b = (unsigned long long)__double_as_longlong(x);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
