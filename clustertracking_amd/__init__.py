@@ -12,7 +12,7 @@ from .find import (find_clusters, grey_dilation, locate_maxima, percentile_thres
 from .preprocessing import lowpass, bandpass, preprocess
 from .fitfunc import FitFunctions
 from .utils import ArrayReader, RefineException
-from . import constraints, artificial, link, preprocessing
+from . import constraints, artificial, link, motion, preprocessing
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -21,7 +21,7 @@ __all__ = ['refine_leastsq', 'find_clusters', 'grey_dilation', 'locate_maxima',
            'characterize', 'characterize_arrays', 'locate', 'lowpass', 'bandpass', 'preprocess', 'preprocessing',
            'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'link_arrays', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',
-           'write_back']
+           'write_back', 'motion']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

@@ -160,6 +160,25 @@ class Link(C.Structure):
     ]
 
 
+class Orientation(C.Structure):
+    """``ctr_orientation`` (include/ctrefine.h): orientation of tracked clusters on the device."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('cluster_size', C.c_int32), ('n_tracks', C.c_int64),
+        ('n_frames', C.c_int64), ('mpp', C.c_double), ('weights', C.c_double * 4),
+        ('pos', C.c_void_p), ('angles', C.c_void_p), ('com', C.c_void_p), ('bases', C.c_void_p),
+    ]
+
+
+class Diffusion(C.Structure):
+    """``ctr_diffusion`` (include/ctrefine.h): diffusion tensor of tracked clusters on the device."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('n_perm', C.c_int32), ('n_tracks', C.c_int64),
+        ('n_frames', C.c_int64), ('n_lags', C.c_int64), ('fps', C.c_double),
+        ('lags', C.c_void_p), ('positions', C.c_void_p), ('bases', C.c_void_p),
+        ('tensor', C.c_void_p), ('n_samples', C.c_void_p),
+    ]
+
+
 def make_problem(ndim, isotropic, modes, radius, constraint=None, max_iter=10,
                  max_shift=1., max_rms_dev=1., residual_factor=100000.,
                  solver_maxiter=100, xtol=0., ftol=0., noise_size=None, threshold=None,

@@ -19,7 +19,7 @@ EXPORTS = ('ctr_abi_version', 'ctr_create', 'ctr_destroy', 'ctr_last_error',
            'ctr_frame_max_device', 'ctr_synchronize', 'ctr_last_kernel_ms',
            'ctr_find_clusters', 'ctr_engine_wait_stream', 'ctr_stream_wait_engine',
            'ctr_draw_frames_device', 'ctr_locate_maxima_device', 'ctr_characterize_device', 'ctr_link_device',
-           'ctr_preprocess_device',
+           'ctr_preprocess_device', 'ctr_orientation_device', 'ctr_diffusion_device',
            'ctr_query_done', 'ctr_ipc_alloc', 'ctr_ipc_open',
            'ctr_ipc_probe', 'ctr_ipc_read', 'ctr_ipc_close', 'ctr_ipc_free')
 
@@ -121,6 +121,11 @@ def load():
         if hasattr(lib, 'ctr_preprocess_device'):   # (an addition to ABI 8: absent from earlier builds of it)
             lib.ctr_preprocess_device.argtypes = [C.c_void_p, P(_abi.Preprocess), C.c_void_p]
             lib.ctr_preprocess_device.restype = C.c_int
+        if hasattr(lib, 'ctr_orientation_device'):   # (additions to ABI 8: absent from earlier builds of it)
+            lib.ctr_orientation_device.argtypes = [C.c_void_p, P(_abi.Orientation), C.c_void_p]
+            lib.ctr_orientation_device.restype = C.c_int
+            lib.ctr_diffusion_device.argtypes = [C.c_void_p, P(_abi.Diffusion), C.c_void_p]
+            lib.ctr_diffusion_device.restype = C.c_int
         lib.ctr_query_done.argtypes = [C.c_void_p]
         lib.ctr_query_done.restype = C.c_int
         lib.ctr_ipc_alloc.argtypes = [C.c_void_p, C.c_int64, P(C.c_void_p), C.c_void_p]
@@ -255,6 +260,20 @@ class Engine(object):
             raise EngineError("libctrefine.so does not export ctr_preprocess_device: rebuild it")
         self._check(self._lib.ctr_preprocess_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
                     'ctr_preprocess_device', too_large=True)
+
+    def orientation_device(self, desc, stream=None):
+        """``ctr_orientation_device``: ``desc`` is an ``_abi.Orientation`` with device pointers."""
+        if not hasattr(self._lib, 'ctr_orientation_device'):
+            raise EngineError("libctrefine.so does not export ctr_orientation_device: rebuild it")
+        self._check(self._lib.ctr_orientation_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
+                    'ctr_orientation_device')
+
+    def diffusion_device(self, desc, stream=None):
+        """``ctr_diffusion_device``: ``desc`` is an ``_abi.Diffusion`` with device pointers."""
+        if not hasattr(self._lib, 'ctr_diffusion_device'):
+            raise EngineError("libctrefine.so does not export ctr_diffusion_device: rebuild it")
+        self._check(self._lib.ctr_diffusion_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
+                    'ctr_diffusion_device')
 
     def query_done(self):
         """True when the last ``refine_batch_device`` call of this engine has finished on the

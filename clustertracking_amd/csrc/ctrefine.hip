@@ -114,6 +114,10 @@ struct ctr_handle {
   void* d_link = nullptr;
   size_t d_link_bytes = 0;
   hipEvent_t ev_link = nullptr;
+  // ctr_diffusion_device: the same for its partial sums
+  void* d_motion = nullptr;
+  size_t d_motion_bytes = 0;
+  hipEvent_t ev_motion = nullptr;
 };
 
 namespace {
@@ -464,6 +468,8 @@ void ctr_destroy(ctr_handle* h) {
   if (h->d_counter) (void)hipFree(h->d_counter);
   if (h->d_link) (void)hipFree(h->d_link);
   if (h->ev_link) (void)hipEventDestroy(h->ev_link);
+  if (h->d_motion) (void)hipFree(h->d_motion);
+  if (h->ev_motion) (void)hipEventDestroy(h->ev_motion);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1051,6 +1057,40 @@ int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream) {
   rc = ctr_link_launch(l, h->d_link, nullptr, s, &msg);
   if (rc != CTR_OK) return fail(h, rc, std::string("ctr_link_device: ") + msg);
   HIP_TRY(h, hipEventRecord(h->ev_link, s));
+  return CTR_OK;
+}
+
+int ctr_orientation_device(ctr_handle* h, const ctr_orientation* o, void* hip_stream) {
+  // the descriptor first, as ctr_characterize_device
+  const char* msg = "";
+  int rc = ctr_orientation_launch(o, false, nullptr, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_orientation_device: ") + msg);
+  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_orientation_device: null handle");
+  HIP_TRY(h, hipSetDevice(h->device));
+  rc = ctr_orientation_launch(o, true, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_orientation_device: ") + msg);
+  return CTR_OK;
+}
+
+int ctr_diffusion_device(ctr_handle* h, const ctr_diffusion* d, void* hip_stream) {
+  // the descriptor first, as ctr_characterize_device; the scratch as ctr_link_device
+  const char* msg = "";
+  size_t need = 0;
+  int rc = ctr_diffusion_launch(d, nullptr, &need, nullptr, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_device: ") + msg);
+  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_diffusion_device: null handle");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  if (!h->ev_motion) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_motion, hipEventDisableTiming));
+  else HIP_TRY(h, hipStreamWaitEvent(s, h->ev_motion, 0));
+  if (need > h->d_motion_bytes) {
+    if (h->d_motion) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->d_motion); h->d_motion = nullptr; h->d_motion_bytes = 0; }
+    if (hipMalloc(&h->d_motion, need) != hipSuccess) return fail(h, CTR_ERR_NOMEM, "ctr_diffusion_device: cannot allocate the partial sums on the device");
+    h->d_motion_bytes = need;
+  }
+  rc = ctr_diffusion_launch(d, h->d_motion, nullptr, s, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_device: ") + msg);
+  HIP_TRY(h, hipEventRecord(h->ev_motion, s));
   return CTR_OK;
 }
 

@@ -130,5 +130,9 @@ int ctr_preprocess_launch(const ctr_preprocess* p, bool launch_it, hipStream_t s
 // linking (tu_link.hip, link_kernels.h): checks the descriptor, reports the scratch it needs in
 // *scratch_bytes and, with a scratch block, queues the whole pipeline on `s`.
 int ctr_link_launch(const ctr_link* l, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg);
+// orientation and diffusion tensor (tu_motion.hip, motion_kernels.h): as the two above -- the
+// orientation has no scratch, the diffusion tensor reports the bytes of its partial sums.
+int ctr_orientation_launch(const ctr_orientation* o, bool launch_it, hipStream_t s, const char** msg);
+int ctr_diffusion_launch(const ctr_diffusion* d, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

@@ -460,6 +460,74 @@ typedef struct ctr_link {
 } ctr_link;
 int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream);
 
+/* Orientation of tracked clusters on the device: the rule of the reference's motion.orientation_df
+ * (motion.py:40-162), the step behind ctr_link_device.  `pos` holds, per track and
+ * frame, the features of the cluster in the order of their `particle`; a frame in which the cluster
+ * is not complete is NaN (any non-finite coordinate marks the frame as missing).  Per frame:
+ *   coordinates: pos * mpp, reversed to x, y(, z);
+ *   permutations: P = 2, 6, 12 for cluster_size 2, 3, 4, the reference's tables in its order
+ *     (motion.py:137-145).  The weights are NOT permuted with the coordinates: permutation p has the
+ *     centre of mass com_p = sum_i(weights[i] c[perm_p[i]]) / sum(weights);
+ *   2D (sizes 2, 3): x = unit(c[perm_p[0]] - com_p) padded with 0, z = (0, 0, 1), y = unit(z x x);
+ *   3D: z = unit(c[perm_p[0]] - com_p);
+ *     size 3: x = unit(z x (c[perm_p[1]] - com_p));  size 4: x = unit(z x (c[perm_p[2]] - c[perm_p[1]]));
+ *     size 2: x = unit(R(z, angle) ([1, 0, 0] x z)) with R the rotation matrix of motion.py:3-16 and
+ *       angle = angles[t, p, f], in radians (the reference draws 2 pi np.random.random() here);
+ *     y = unit(z x x);
+ *   bases[t, p, f] = rows x, y, z; a basis with a non-finite entry (coincident features, a collinear
+ *     trimer, a dimer along [1, 0, 0]) is written as nine NaN; the reference's check_orthonormality
+ *     is not reproduced;
+ *   com[t, f] = the centre of mass of the LAST permutation, padded with 0 in 2D.
+ * A missing frame gives NaN com and bases.  cluster_size 1 and the 2D tetramer are CTR_ERR_UNSUPPORTED,
+ * a 3D dimer without angles CTR_ERR_INVALID.
+ * The descriptor is checked before the handle, as for ctr_characterize_device.
+ * Device pointers; asynchronous on `hip_stream` (NULL = the handle's stream). */
+typedef struct ctr_orientation {
+  int32_t ndim;            /* 2 or 3 */
+  int32_t cluster_size;    /* 2..4 as allowed above */
+  int64_t n_tracks, n_frames;
+  double  mpp;
+  double  weights[4];      /* sizes**ndim, computed by the caller */
+  const double* pos;       /* [T, F, cluster_size, ndim] (z,) y, x in px; NaN = missing */
+  const double* angles;    /* [T, P, F] or NULL (required for 3D dimers) */
+  double* com;             /* [T, F, 3] out */
+  double* bases;           /* [T, P, F, 3, 3] out */
+} ctr_orientation;
+int ctr_orientation_device(ctr_handle* h, const ctr_orientation* o, void* hip_stream);
+
+/* Diffusion tensor of tracked clusters on the device: the rule of the reference's
+ * motion.diffusion_tensor (motion.py:165-198) for every track and every lag of a sweep
+ * in one call.  Per track t, lag k, permutation p and frame b with b + k < n_frames:
+ *   translation = bases[t, p, b] (positions[t, b + k] - positions[t, b]),
+ *   rotation    = 0.5 sum_i e_i x (bases[t, p, b] bases[t, p, b + k, i]),
+ *   x = (translation, rotation); a row with a non-finite component is dropped; the rows of all
+ *   permutations are pooled:
+ *   tensor[t, k] = mean(x x^T) * 0.5 / (k / fps); ndim 2 keeps the components [0, 1, 5] (3 x 3), ndim
+ *   3 all six (6 x 6); n_samples[t, k] = rows that entered the mean; none (also k >= n_frames or
+ *   k < 1): a NaN tensor and 0.
+ * The frames of a (track, permutation) are cut into tiles of 256 whatever the lags are; a workgroup
+ * stages its tile and the halo behind it in LDS (as many frames as 64 KiB hold), loops
+ * over the lags and writes one partial sum per (track, lag, permutation, tile); a later frame beyond
+ * the staged halo is read from global memory.  A second kernel adds the partials of a (track, lag)
+ * in the order permutation, tile.  No floating-point atomics: the result of a (track, lag) is the
+ * same bytes whatever else the call holds.
+ * Scratch (the partials) belongs to the handle: calls of one handle are ordered on the device
+ * whatever streams they are given.
+ * The descriptor is checked before the handle, as for ctr_characterize_device.
+ * Device pointers, lags included; asynchronous on `hip_stream` (NULL = the handle's stream). */
+typedef struct ctr_diffusion {
+  int32_t ndim;            /* 2 -> 3x3, 3 -> 6x6 */
+  int32_t n_perm;
+  int64_t n_tracks, n_frames, n_lags;
+  double  fps;
+  const int64_t* lags;     /* [n_lags], each >= 1 (validated on the host side of the wrapper) */
+  const double* positions; /* [T, F, 3] */
+  const double* bases;     /* [T, P, F, 3, 3] */
+  double*  tensor;         /* [T, n_lags, D, D] out */
+  int64_t* n_samples;      /* [T, n_lags] out: rows that entered the mean */
+} ctr_diffusion;
+int ctr_diffusion_device(ctr_handle* h, const ctr_diffusion* d, void* hip_stream);
+
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
  * several batches in flight hand finished batches on (e.g. to the result gather) from the host
