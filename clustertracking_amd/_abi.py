@@ -160,6 +160,27 @@ class Link(C.Structure):
     ]
 
 
+RELOCATE_OK, RELOCATE_CAPACITY, RELOCATE_BAD_FRAME = 0, 1, 2   # ctr_relocate.status[q]
+RELOCATE_MAX_MAXIMA, RELOCATE_MAX_BACKGROUND, RELOCATE_TILE_BYTES = 256, 512, 32768
+
+
+class Relocate(C.Structure):
+    """``ctr_relocate`` (include/ctrefine.h): relocation candidates of lost features on the device."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('frame_dtype', C.c_int32), ('n_frames', C.c_int64),
+        ('shape', C.c_int64 * MAX_NDIM), ('radius', C.c_int64 * MAX_NDIM),
+        ('separation', C.c_double * MAX_NDIM), ('search_range', C.c_double * MAX_NDIM),
+        ('isotropic', C.c_int32), ('max_candidates', C.c_int32),
+        ('minmass', C.c_double), ('scale_factor', C.c_double),
+        ('frames', C.c_void_p), ('threshold', C.c_void_p),
+        ('n_known', C.c_int64), ('known_pos', C.c_void_p), ('known_offset', C.c_void_p),
+        ('n_queries', C.c_int64), ('query_frame', C.c_void_p), ('source_offset', C.c_void_p),
+        ('source_pos', C.c_void_p),
+        ('n_found', C.c_void_p), ('cand_pos', C.c_void_p), ('mass', C.c_void_p),
+        ('signal', C.c_void_p), ('size', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
 class Orientation(C.Structure):
     """``ctr_orientation`` (include/ctrefine.h): orientation of tracked clusters on the device."""
     _fields_ = [

@@ -20,6 +20,7 @@ EXPORTS = ('ctr_abi_version', 'ctr_create', 'ctr_destroy', 'ctr_last_error',
            'ctr_find_clusters', 'ctr_engine_wait_stream', 'ctr_stream_wait_engine',
            'ctr_draw_frames_device', 'ctr_locate_maxima_device', 'ctr_characterize_device', 'ctr_link_device',
            'ctr_preprocess_device', 'ctr_orientation_device', 'ctr_diffusion_device',
+           'ctr_relocate_device', 'ctr_relocate_plan',
            'ctr_query_done', 'ctr_ipc_alloc', 'ctr_ipc_open',
            'ctr_ipc_probe', 'ctr_ipc_read', 'ctr_ipc_close', 'ctr_ipc_free')
 
@@ -126,6 +127,11 @@ def load():
             lib.ctr_orientation_device.restype = C.c_int
             lib.ctr_diffusion_device.argtypes = [C.c_void_p, P(_abi.Diffusion), C.c_void_p]
             lib.ctr_diffusion_device.restype = C.c_int
+        if hasattr(lib, 'ctr_relocate_device'):   # (additions to ABI 8: absent from earlier builds of it)
+            lib.ctr_relocate_device.argtypes = [C.c_void_p, P(_abi.Relocate), C.c_void_p]
+            lib.ctr_relocate_device.restype = C.c_int
+            lib.ctr_relocate_plan.argtypes = [P(_abi.Relocate), P(C.c_int64), P(C.c_int64)]
+            lib.ctr_relocate_plan.restype = C.c_int
         lib.ctr_query_done.argtypes = [C.c_void_p]
         lib.ctr_query_done.restype = C.c_int
         lib.ctr_ipc_alloc.argtypes = [C.c_void_p, C.c_int64, P(C.c_void_p), C.c_void_p]
@@ -153,6 +159,18 @@ def cluster_kernel(problem, n_features):
     if rc != _abi.OK:
         raise ValueError("ctr_cluster_kernel: invalid problem or n_features (%d)" % rc)
     return out
+
+
+def relocate_plan(desc):
+    """(pixels of the LDS tile, dynamic LDS bytes) of a ``ctr_relocate_device`` launch
+    (``ctr_relocate_plan``, no device needed); ``ValueError`` / ``NotImplementedError`` as the call itself."""
+    lib = load()
+    tile, lds = C.c_int64(), C.c_int64()
+    rc = lib.ctr_relocate_plan(C.byref(desc), C.byref(tile), C.byref(lds))
+    if rc != _abi.OK:
+        msg = (lib.ctr_last_error(None) or b'').decode()
+        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
+    return tile.value, lds.value
 
 
 class Engine(object):
@@ -274,6 +292,13 @@ class Engine(object):
             raise EngineError("libctrefine.so does not export ctr_diffusion_device: rebuild it")
         self._check(self._lib.ctr_diffusion_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
                     'ctr_diffusion_device')
+
+    def relocate_device(self, desc, stream=None):
+        """``ctr_relocate_device``: ``desc`` is an ``_abi.Relocate`` with device pointers."""
+        if not hasattr(self._lib, 'ctr_relocate_device'):
+            raise EngineError("libctrefine.so does not export ctr_relocate_device: rebuild it")
+        self._check(self._lib.ctr_relocate_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
+                    'ctr_relocate_device')
 
     def query_done(self):
         """True when the last ``refine_batch_device`` call of this engine has finished on the

@@ -114,24 +114,8 @@ __global__ void mark_kernel(const KArgs k, int code) {
 // reference's ids depend on Python set order); the PARTITION is the reference's.
 constexpr int FC_THREADS = 256;
 
-// The scaled squared distance as cKDTree sums it: in axis order, every product rounded before it
-// is added.  Fused into the addition, d * d is not rounded, and a pair at a scaled distance of
-// exactly 1 -- integer positions at a Pythagorean offset of an integer separation, what locate
-// returns -- lands on the other side of `<= 1` ((12/13)^2 + (5/13)^2 is 1.0000000000000002 by
-// the rule and 1.0 fused).  Same guard as in_mask_exact (device_common.h).
-template <int ND>
-__device__ __forceinline__ double scaled_dist2(const double (&p)[ND], const double* __restrict__ q) {
-#pragma clang fp contract(off)
-  double d2 = 0.;
-#pragma unroll
-  for (int a = 0; a < ND; ++a) {
-    const double d = p[a] - q[a];
-    const double dd = d * d;
-    d2 = d2 + dd;
-  }
-  return d2;
-}
-
+// (scaled_dist2, the no-contraction distance of the pair test, lives in device_common.h: the
+// relocation kernels share it)
 template <int ND>
 __global__ void __launch_bounds__(FC_THREADS) find_clusters_kernel(const double* __restrict__ pos,
                                                                    const int32_t* __restrict__ frame_offset,

@@ -1060,6 +1060,28 @@ int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream) {
   return CTR_OK;
 }
 
+int ctr_relocate_device(ctr_handle* h, const ctr_relocate* r, void* hip_stream) {
+  // the descriptor first, as ctr_characterize_device; the kernel needs no scratch
+  const char* msg = "";
+  int rc = ctr_relocate_launch(r, true, false, nullptr, nullptr, nullptr, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_relocate_device: ") + msg);
+  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_relocate_device: null handle");
+  HIP_TRY(h, hipSetDevice(h->device));
+  rc = ctr_relocate_launch(r, true, true, hip_stream ? (hipStream_t)hip_stream : h->stream, nullptr, nullptr, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_relocate_device: ") + msg);
+  return CTR_OK;
+}
+
+int ctr_relocate_plan(const ctr_relocate* r, int64_t* tile_pixels, int64_t* lds_bytes) {
+  const char* msg = "";
+  long long tile = 0, lds = 0;
+  const int rc = ctr_relocate_launch(r, false, false, nullptr, &tile, &lds, &msg);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_relocate_plan: ") + msg);
+  if (tile_pixels) *tile_pixels = tile;
+  if (lds_bytes) *lds_bytes = lds;
+  return CTR_OK;
+}
+
 int ctr_orientation_device(ctr_handle* h, const ctr_orientation* o, void* hip_stream) {
   // the descriptor first, as ctr_characterize_device
   const char* msg = "";

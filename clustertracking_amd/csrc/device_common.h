@@ -184,9 +184,11 @@ __device__ __forceinline__ int tri(int i) { return (i * (i + 1)) >> 1; }
 
 // ---- masks (refine.py:43-44) --------------------------------------------------
 
-template <int ND>
-__device__ __forceinline__ bool in_mask_exact(const int (&idx)[ND], const double (&rel)[ND],
-                                              const int (&radius)[ND]) {
+// sum(((idx - rel) / radius)^2) as NumPy evaluates it (masks.py:89,92): a division, a product and
+// a sum in axis order, each rounded once.  R: int (mask radius) or double (a separation).
+template <int ND, typename R>
+__device__ __forceinline__ double ellipse_sum(const int (&idx)[ND], const double (&rel)[ND],
+                                              const R (&radius)[ND]) {
 #pragma clang fp contract(off)
   double s = 0.;
 #pragma unroll
@@ -195,7 +197,13 @@ __device__ __forceinline__ bool in_mask_exact(const int (&idx)[ND], const double
     double t2 = t * t;
     s = s + t2;
   }
-  return s <= 1.;
+  return s;
+}
+
+template <int ND>
+__device__ __forceinline__ bool in_mask_exact(const int (&idx)[ND], const double (&rel)[ND],
+                                              const int (&radius)[ND]) {
+  return ellipse_sum<ND, int>(idx, rel, radius) <= 1.;
 }
 
 // Cheap test first; the IEEE-division form only where the two could disagree.
@@ -210,6 +218,24 @@ __device__ __forceinline__ bool in_mask(const int (&idx)[ND], const double (&rel
   }
   if (fabs(s - 1.) > 1e-9) return s < 1.;
   return in_mask_exact<ND>(idx, rel, radius);
+}
+
+// The scaled squared distance as cKDTree sums it: in axis order, every product rounded before it
+// is added.  Fused into the addition, d * d is not rounded, and a pair at a scaled distance of
+// exactly 1 -- integer positions at a Pythagorean offset of an integer separation, what locate
+// returns -- lands on the other side of `<= 1` ((12/13)^2 + (5/13)^2 is 1.0000000000000002 by
+// the rule and 1.0 fused).  Same guard as in_mask_exact.
+template <int ND>
+__device__ __forceinline__ double scaled_dist2(const double (&p)[ND], const double* __restrict__ q) {
+#pragma clang fp contract(off)
+  double d2 = 0.;
+#pragma unroll
+  for (int a = 0; a < ND; ++a) {
+    const double d = p[a] - q[a];
+    const double dd = d * d;
+    d2 = d2 + dd;
+  }
+  return d2;
 }
 
 __device__ __forceinline__ double Msym(const double* Mp, int i, int j) {

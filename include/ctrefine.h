@@ -460,6 +460,102 @@ typedef struct ctr_link {
 } ctr_link;
 int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream);
 
+/* Relocation candidates of lost features on the device: the rule of the reference's
+ * FindLinker.get_relocate_candidates (find_link.py:811-867), the look-again step that
+ * makes find_link more than locate followed by link.  The loop around it (shortage per sub-network,
+ * claimed candidates added to the hash, the sub-network solved again) is the caller's.
+ * Derived once per call, as FindLinker.__init__ derives them: box = int(2 separation / sqrt(ndim))
+ * per axis (0 filters like 1), slice_radius = int(search_range + radius + 1),
+ * bg_radius = slice_radius + radius + 1, max_dist = max(bg_radius / search_range).
+ * A query q is a frame t = query_frame[q] and the sources source_pos[source_offset[q] ..
+ * source_offset[q + 1]) (any float64, also beyond the frame); the known features of frame t are
+ * rows [known_offset[t], known_offset[t + 1]) of known_pos.  Per query:
+ *   box: the sources rounded half to even; those beyond the frame by more than slice_radius on an
+ *     axis are dropped (masks._in_bounds); origin = max(0, min - slice_radius), end =
+ *     min(shape, max + slice_radius + 1); none left = no candidates.  Below, a source is
+ *     rel = s - origin and a known feature k - origin (one float64 subtraction each), a pixel its
+ *     integer index p in the box;
+ *   visible: sum(((p - rel) / slice_radius)^2) <= 1 for any source, the dropped ones included
+ *     (masks.py:89; axis order, no contraction);
+ *   background: the known features with sum((k / search_range - s / search_range)^2) <=
+ *     max_dist * max_dist for any source (frame coordinates, the division first); a visible pixel is
+ *     hidden where sum(((p - (k - origin)) / separation)^2) < 1 for any of them (strict);
+ *   m(p) = the pixel, in its own type, where visible and not hidden, else 0 -- also beyond the box;
+ *   maxima: m(p) equals the maximum of m over the dilation box around p (offsets
+ *     -((n-1)/2) .. n/2, 0 beyond the box) and m(p) > threshold[t], both as ctr_locate compares
+ *     (float32 frames against the float32 threshold); a NaN threshold = no candidates;
+ *   reach: all search_range equal: sum((p - rel)^2) <= search_range^2 for any source, otherwise
+ *     sum((p / search_range - rel / search_range)^2) <= 1 (find_link.py:25-41);
+ *   drop close: as ctr_locate's `precise` on the maxima within reach, positions in box coordinates:
+ *     of two closer than separation (scaled distance <= 1 - 1e-7) the one lower in the order (m,
+ *     sum of p / separation, C-order position) goes, all pairs decided at once;
+ *   mass, signal, size of every survivor by the rule of ctr_characterize_device ON m (radius,
+ *     isotropic, scale_factor; the window is padded with 0 beyond the box, not beyond the frame);
+ *   the rows with mass >= minmass, by mass descending; equal masses in C order of position (the
+ *     reference: an unstable sort of a set's iteration order).  Positions in frame coordinates.
+ * The reference's three early exits (box sums to 0 before or after masking, every m below the
+ * threshold) change nothing for frames without negative pixels, where a sum of 0 means all zeros and
+ * the threshold of ctr_locate is positive; for frames with negative pixels the result is the rule
+ * above WITHOUT the two sum exits (not compared with the reference).
+ * Ties: every `<=` above on exact float64 equality decides as written.  They equal cKDTree's
+ * decisions on the constructed ties of tests/test_relocate_rule.py.
+ * Outputs per query: n_found = rows after the minmass cut (may exceed max_candidates = K); rows
+ * [0, min(n_found, K)) of cand_pos / mass / signal / size; the rows behind them are -1 / NaN.
+ * status[q]: CTR_RELOCATE_OK; CTR_RELOCATE_CAPACITY for more than CTR_LINK_MAX_SOURCES sources, more
+ * than CTR_RELOCATE_MAX_MAXIMA raw maxima in the box (before reach; a saturated plateau) or more than
+ * CTR_RELOCATE_MAX_BACKGROUND background features; CTR_RELOCATE_BAD_FRAME for a query_frame outside
+ * [0, n_frames) -- reported by the device, not clamped (the host cannot read it).  With a non-zero
+ * status n_found[q] is 0 and the rows of q are -1 / NaN; other queries are unaffected.
+ * One workgroup per query; m is staged in an LDS tile that holds a one-source box or the thinnest
+ * slab of a frame-wide box, whichever is larger, up to CTR_RELOCATE_TILE_BYTES (an untuned choice);
+ * a larger box is walked in slabs along axis 0 with the dilation box as halo, and a box so wide that
+ * not even one slab fits (box[0] x its other axes > tile: sources spread over a wide frame or a 3D
+ * stack) is not staged at all: m is recomputed from the frame in global memory, slower, same result.
+ * The frame's size never refuses a call.  No scratch, no floating-point atomics: a query gives the
+ * same bytes alone and in any batch.
+ * source_offset and known_offset are the caller's and are trusted, like every other offset table of
+ * this header: they must rise within [0, S] and [0, n_known] (S is not passed; the known range is
+ * kept inside the table, nothing else is checked).
+ * ctr_relocate_plan reports the tile (pixels) and the LDS bytes of a launch without a device; it
+ * checks the scalars of the descriptor only.
+ * The descriptor is checked before the handle, as for ctr_characterize_device.
+ * Device pointers; asynchronous on `hip_stream` (NULL = the handle's stream): read status after
+ * synchronising. */
+enum { CTR_RELOCATE_OK = 0, CTR_RELOCATE_CAPACITY = 1, CTR_RELOCATE_BAD_FRAME = 2 };
+#define CTR_RELOCATE_MAX_MAXIMA 256
+#define CTR_RELOCATE_MAX_BACKGROUND 512
+#define CTR_RELOCATE_TILE_BYTES 32768
+typedef struct ctr_relocate {
+  int32_t ndim;                /* 2 or 3 */
+  int32_t frame_dtype;         /* CTR_DTYPE_* */
+  int64_t n_frames;
+  int64_t shape[CTR_MAX_NDIM]; /* (z,) y, x */
+  int64_t radius[CTR_MAX_NDIM];        /* per axis, >= 0: diameter // 2 */
+  double separation[CTR_MAX_NDIM];     /* per axis, > 0 */
+  double search_range[CTR_MAX_NDIM];   /* per axis, > 0 */
+  int32_t isotropic;           /* != 0: one size per candidate */
+  int32_t max_candidates;      /* K >= 1: rows per query */
+  double minmass;
+  double scale_factor;         /* divides mass and signal; not 0 */
+  const void* frames;          /* [n_frames, *shape] */
+  const double* threshold;     /* [n_frames]: what ctr_locate.threshold holds; NaN = no candidates */
+  int64_t n_known;             /* M */
+  const double* known_pos;     /* [M, ndim] (z,) y, x */
+  const int64_t* known_offset; /* [n_frames + 1] */
+  int64_t n_queries;           /* Q */
+  const int64_t* query_frame;  /* [Q] */
+  const int64_t* source_offset;/* [Q + 1] */
+  const double* source_pos;    /* [S, ndim] */
+  int32_t* n_found;            /* [Q] out */
+  int32_t* cand_pos;           /* [Q, K, ndim] out */
+  double* mass;                /* [Q, K] out */
+  double* signal;              /* [Q, K] out */
+  double* size;                /* [Q, K] (isotropic) or [Q, K, ndim] out */
+  int32_t* status;             /* [Q] out: CTR_RELOCATE_* */
+} ctr_relocate;
+int ctr_relocate_device(ctr_handle* h, const ctr_relocate* r, void* hip_stream);
+int ctr_relocate_plan(const ctr_relocate* r, int64_t* tile_pixels, int64_t* lds_bytes);
+
 /* Orientation of tracked clusters on the device: the rule of the reference's motion.orientation_df
  * (motion.py:40-162), the step behind ctr_link_device.  `pos` holds, per track and
  * frame, the features of the cluster in the order of their `particle`; a frame in which the cluster
