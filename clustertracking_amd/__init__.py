@@ -13,7 +13,8 @@ from .preprocessing import lowpass, bandpass, preprocess
 from .relocate import relocate_arrays, relocate_candidates
 from .fitfunc import FitFunctions
 from .utils import ArrayReader, RefineException
-from . import constraints, artificial, link, motion, preprocessing
+from . import constraints, artificial, link, motion, motion_ci, preprocessing
+from .motion_ci import diffusion_tensor_ci, bootstrap_indices
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -22,7 +23,7 @@ __all__ = ['refine_leastsq', 'find_clusters', 'grey_dilation', 'locate_maxima',
            'characterize', 'characterize_arrays', 'locate', 'relocate_arrays', 'relocate_candidates', 'lowpass', 'bandpass', 'preprocess', 'preprocessing',
            'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'link_arrays', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',
-           'write_back', 'motion']
+           'write_back', 'motion', 'motion_ci', 'diffusion_tensor_ci', 'bootstrap_indices']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

@@ -200,6 +200,25 @@ class Diffusion(C.Structure):
     ]
 
 
+CI_BCA, CI_PI = 0, 1                                           # ctr_diffusion_ci.method
+DIFFUSION_CI_MAX_SAMPLES, DIFFUSION_CI_MAX_ALPHA = 16384, 8
+DIFFUSION_CI_LDS_BYTES, DIFFUSION_CI_SCRATCH_BYTES = 65536, 268435456
+
+
+class DiffusionCI(C.Structure):
+    """``ctr_diffusion_ci`` (include/ctrefine.h): bootstrap interval of the diffusion tensor on the device."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('n_perm', C.c_int32), ('n_tracks', C.c_int64),
+        ('n_frames', C.c_int64), ('n_lags', C.c_int64), ('fps', C.c_double),
+        ('lags', C.c_void_p), ('positions', C.c_void_p), ('bases', C.c_void_p),
+        ('n_samples', C.c_int64), ('seed', C.c_uint64), ('method', C.c_int32), ('n_alpha', C.c_int32),
+        ('z_alpha', C.c_double * DIFFUSION_CI_MAX_ALPHA), ('alphas', C.c_double * DIFFUSION_CI_MAX_ALPHA),
+        ('pool_tracks', C.c_int32),
+        ('interval', C.c_void_p), ('tensor', C.c_void_p), ('n_rows', C.c_void_p),
+        ('z0', C.c_void_p), ('accel', C.c_void_p), ('ranks', C.c_void_p),
+    ]
+
+
 def make_problem(ndim, isotropic, modes, radius, constraint=None, max_iter=10,
                  max_shift=1., max_rms_dev=1., residual_factor=100000.,
                  solver_maxiter=100, xtol=0., ftol=0., noise_size=None, threshold=None,

@@ -20,7 +20,7 @@ EXPORTS = ('ctr_abi_version', 'ctr_create', 'ctr_destroy', 'ctr_last_error',
            'ctr_find_clusters', 'ctr_engine_wait_stream', 'ctr_stream_wait_engine',
            'ctr_draw_frames_device', 'ctr_locate_maxima_device', 'ctr_characterize_device', 'ctr_link_device',
            'ctr_preprocess_device', 'ctr_orientation_device', 'ctr_diffusion_device',
-           'ctr_relocate_device', 'ctr_relocate_plan',
+           'ctr_relocate_device', 'ctr_relocate_plan', 'ctr_diffusion_ci_device', 'ctr_diffusion_ci_plan',
            'ctr_query_done', 'ctr_ipc_alloc', 'ctr_ipc_open',
            'ctr_ipc_probe', 'ctr_ipc_read', 'ctr_ipc_close', 'ctr_ipc_free')
 
@@ -132,6 +132,11 @@ def load():
             lib.ctr_relocate_device.restype = C.c_int
             lib.ctr_relocate_plan.argtypes = [P(_abi.Relocate), P(C.c_int64), P(C.c_int64)]
             lib.ctr_relocate_plan.restype = C.c_int
+        if hasattr(lib, 'ctr_diffusion_ci_device'):   # (additions to ABI 8: absent from earlier builds of it)
+            lib.ctr_diffusion_ci_device.argtypes = [C.c_void_p, P(_abi.DiffusionCI), C.c_void_p]
+            lib.ctr_diffusion_ci_device.restype = C.c_int
+            lib.ctr_diffusion_ci_plan.argtypes = [P(_abi.DiffusionCI), P(C.c_int32), P(C.c_int64), P(C.c_int64), P(C.c_int64)]
+            lib.ctr_diffusion_ci_plan.restype = C.c_int
         lib.ctr_query_done.argtypes = [C.c_void_p]
         lib.ctr_query_done.restype = C.c_int
         lib.ctr_ipc_alloc.argtypes = [C.c_void_p, C.c_int64, P(C.c_void_p), C.c_void_p]
@@ -171,6 +176,21 @@ def relocate_plan(desc):
         msg = (lib.ctr_last_error(None) or b'').decode()
         raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
     return tile.value, lds.value
+
+
+def diffusion_ci_plan(desc):
+    """The launch decision of ``ctr_diffusion_ci_device`` (``ctr_diffusion_ci_plan``, no device needed):
+    ``(rows_in_lds, lds_bytes, scratch_bytes, pairs_per_chunk)``; ``ValueError`` /
+    ``NotImplementedError`` as the call itself."""
+    lib = load()
+    if not hasattr(lib, 'ctr_diffusion_ci_plan'):
+        raise EngineError("libctrefine.so does not export ctr_diffusion_ci_plan: rebuild it")
+    in_lds, lds, scratch, chunk = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+    rc = lib.ctr_diffusion_ci_plan(C.byref(desc), C.byref(in_lds), C.byref(lds), C.byref(scratch), C.byref(chunk))
+    if rc != _abi.OK:
+        msg = (lib.ctr_last_error(None) or b'').decode()
+        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
+    return bool(in_lds.value), lds.value, scratch.value, chunk.value
 
 
 class Engine(object):
@@ -292,6 +312,13 @@ class Engine(object):
             raise EngineError("libctrefine.so does not export ctr_diffusion_device: rebuild it")
         self._check(self._lib.ctr_diffusion_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
                     'ctr_diffusion_device')
+
+    def diffusion_ci_device(self, desc, stream=None):
+        """``ctr_diffusion_ci_device``: ``desc`` is an ``_abi.DiffusionCI`` with device pointers."""
+        if not hasattr(self._lib, 'ctr_diffusion_ci_device'):
+            raise EngineError("libctrefine.so does not export ctr_diffusion_ci_device: rebuild it")
+        self._check(self._lib.ctr_diffusion_ci_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
+                    'ctr_diffusion_ci_device')
 
     def relocate_device(self, desc, stream=None):
         """``ctr_relocate_device``: ``desc`` is an ``_abi.Relocate`` with device pointers."""

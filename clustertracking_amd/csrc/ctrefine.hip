@@ -114,7 +114,7 @@ struct ctr_handle {
   void* d_link = nullptr;
   size_t d_link_bytes = 0;
   hipEvent_t ev_link = nullptr;
-  // ctr_diffusion_device: the same for its partial sums
+  // ctr_diffusion_device and ctr_diffusion_ci_device: the same for their partial sums, rows and statistics
   void* d_motion = nullptr;
   size_t d_motion_bytes = 0;
   hipEvent_t ev_motion = nullptr;
@@ -1113,6 +1113,43 @@ int ctr_diffusion_device(ctr_handle* h, const ctr_diffusion* d, void* hip_stream
   rc = ctr_diffusion_launch(d, h->d_motion, nullptr, s, &msg);
   if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_device: ") + msg);
   HIP_TRY(h, hipEventRecord(h->ev_motion, s));
+  return CTR_OK;
+}
+
+int ctr_diffusion_ci_device(ctr_handle* h, const ctr_diffusion_ci* d, void* hip_stream) {
+  // the descriptor first, as ctr_characterize_device; the scratch is ctr_diffusion_device's, and so is the order of the calls
+  const char* msg = "";
+  ctr_ci_plan plan = {};
+  int rc = ctr_diffusion_ci_launch(d, true, nullptr, nullptr, &plan, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_ci_device: ") + msg);
+  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_diffusion_ci_device: null handle");
+  if (plan.pairs_per_chunk == 0) return CTR_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  if (!h->ev_motion) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_motion, hipEventDisableTiming));
+  else HIP_TRY(h, hipStreamWaitEvent(s, h->ev_motion, 0));
+  const size_t need = (size_t)plan.scratch_bytes + 256;
+  if (need > h->d_motion_bytes) {
+    if (h->d_motion) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->d_motion); h->d_motion = nullptr; h->d_motion_bytes = 0; }
+    if (hipMalloc(&h->d_motion, need) != hipSuccess) return fail(h, CTR_ERR_NOMEM, "ctr_diffusion_ci_device: cannot allocate the scratch on the device");
+    h->d_motion_bytes = need;
+  }
+  rc = ctr_diffusion_ci_launch(d, true, h->d_motion, s, nullptr, &msg);
+  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_ci_device: ") + msg);
+  HIP_TRY(h, hipEventRecord(h->ev_motion, s));
+  return CTR_OK;
+}
+
+int ctr_diffusion_ci_plan(const ctr_diffusion_ci* d, int32_t* rows_in_lds, int64_t* lds_bytes, int64_t* scratch_bytes,
+                          int64_t* pairs_per_chunk) {
+  const char* msg = "";
+  ctr_ci_plan plan = {};
+  const int rc = ctr_diffusion_ci_launch(d, false, nullptr, nullptr, &plan, &msg);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_diffusion_ci_plan: ") + msg);
+  if (rows_in_lds) *rows_in_lds = plan.rows_in_lds;
+  if (lds_bytes) *lds_bytes = plan.lds_bytes;
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  if (pairs_per_chunk) *pairs_per_chunk = plan.pairs_per_chunk;
   return CTR_OK;
 }
 

@@ -74,6 +74,14 @@ __device__ double lowpass_pixel(const void* frame, int dtype, const long* fshape
   return t > threshold ? t : 0.;
 }
 
+// the finaliser of splitmix64 (synth_kernels.h: the frame generator; motion_ci_kernels.h: the
+// counter-based resampling indices)
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 __device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);

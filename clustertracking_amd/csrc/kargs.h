@@ -134,6 +134,15 @@ int ctr_link_launch(const ctr_link* l, void* scratch, size_t* scratch_bytes, hip
 // orientation has no scratch, the diffusion tensor reports the bytes of its partial sums.
 int ctr_orientation_launch(const ctr_orientation* o, bool launch_it, hipStream_t s, const char** msg);
 int ctr_diffusion_launch(const ctr_diffusion* d, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg);
+// bootstrap interval of the diffusion tensor (tu_motion_ci.hip, motion_ci_kernels.h): checks the
+// descriptor (the scalars alone with pointers == false), reports the launch decision in *plan and,
+// with a scratch block of plan->scratch_bytes, queues every chunk on `s`.
+struct ctr_ci_plan {
+  int rows_in_lds;
+  long long lds_bytes, scratch_bytes, pairs_per_chunk;
+};
+int ctr_diffusion_ci_launch(const ctr_diffusion_ci* d, bool pointers, void* scratch, hipStream_t s, ctr_ci_plan* plan,
+                            const char** msg);
 // relocation candidates (tu_relocate.hip, relocate_kernels.h): checks the descriptor (the scalars
 // alone with pointers == false), reports the plan and, with launch_it, queues the kernel on `s`.
 int ctr_relocate_launch(const ctr_relocate* r, bool pointers, bool launch_it, hipStream_t s, long long* tile_pixels,

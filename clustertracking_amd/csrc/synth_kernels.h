@@ -79,10 +79,7 @@ __global__ void __launch_bounds__(SYN_THREADS) draw_features_kernel(const SynthA
 }
 
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long& x) {
-  unsigned long long z = (x += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
+  return mix64(x += 0x9E3779B97F4A7C15ull);     // device_common.h
 }
 __device__ __forceinline__ double uniform01(unsigned long long& st) {
   return (double)(splitmix64(st) >> 11) * (1. / 9007199254740992.);

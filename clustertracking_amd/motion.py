@@ -18,9 +18,11 @@ The rule is the reference's, restated (``include/ctrefine.h`` has it in full, DE
   call takes every track and a whole sweep of lags, and a lag beyond the video gives a NaN tensor
   and count 0 instead of a warning.
 
-``diffusion_tensor_ci`` (the reference's bootstrap interval) is not taken over: it needs
-``scikits.bootstrap``, which this package does not depend on.  There is no CPU fallback: without
-the library or a GPU the calls raise ``EngineError``; argument errors are raised before that.
+The reference's ``diffusion_tensor_ci`` (``motion.py:201-216``), the bootstrap interval of that tensor,
+is :func:`clustertracking_amd.motion_ci.diffusion_tensor_ci`, a module of its own.
+
+There is no CPU fallback: without the library or a GPU the calls raise ``EngineError``; argument
+errors are raised before that.
 """
 import sys
 

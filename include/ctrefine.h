@@ -624,6 +624,81 @@ typedef struct ctr_diffusion {
 } ctr_diffusion;
 int ctr_diffusion_device(ctr_handle* h, const ctr_diffusion* d, void* hip_stream);
 
+/* Bootstrap confidence interval of the diffusion tensor on the device: the reference's
+ * motion.diffusion_tensor_ci (motion.py:201-216), which calls scikits.bootstrap.ci on the pooled
+ * displacement rows.  That package's ci is restated here from its published source; parity with the
+ * package itself is not pinned.  For every pair = (track, lag) -- with pool_tracks every
+ * lag, over the rows of all tracks -- of a call:
+ *   rows: x[n, D], the rows of ctr_diffusion_device in the order (track,) permutation, frame, those
+ *     with a non-finite component dropped; ndim 2 keeps the components [0, 1, 5] (D = 3), ndim 3 all
+ *     six (D = 6);
+ *   statistic: stat(x) = mean_k(x_k x_k^T) * 0.5 / (lag / fps), D x D; ostat = stat(x) (`tensor`);
+ *   resamples b = 0 .. B - 1 (B = n_samples): s_b = stat(x[idx[b, :]]), idx[b, k] for k = 0 .. n - 1
+ *     drawn with replacement by a counter-based generator that depends on (seed, b, k, n) alone:
+ *       r = mix64(mix64(seed) + ((b << 32) + k + 1) * 0x9E3779B97F4A7C15 mod 2^64),
+ *       idx[b, k] = floor(r n / 2^64)   (the high half of the 128-bit product),
+ *     mix64 the finaliser of splitmix64: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *     z *= 0x94D049BB133111EB; z ^= z >> 31.  The products of a resample are added in the order of k;
+ *   sort: every entry (i, j) of s is sorted over b, ascending;
+ *   method CTR_CI_PI (percentile): avals = alphas;
+ *   method CTR_CI_BCA: z0 = Phi^-1(#{b: s_b < ostat} / B) (-inf / +inf where no / every resample lies
+ *     below); the acceleration a = sum(d^3) / (6 sum(d^2)^1.5) with d_k = p_k - mean(p), p_k =
+ *     x_ki x_kj -- the jackknife form sum((jm - j_k)^3) / (6 sum((jm - j_k)^2)^1.5) of the package,
+ *     j_k = stat(x without row k), of which jm - j_k is a positive multiple of d_k;
+ *     zs = z0 + z_alpha; avals = Phi(z0 + zs / (1 - a zs)); z_alpha = Phi^-1(alphas) is the caller's;
+ *   rank = round_half_even((B - 1) avals), 0 where avals is NaN (0 / 0 in a, z0 infinite), as the
+ *     package's nan_to_num; interval[q, i, j] = sorted s[rank[q, i, j], i, j].
+ * z0 and a are written for both methods.  A pair without rows (also lag >= n_frames or lag < 1) gives
+ * a NaN interval, tensor, z0 and a, ranks 0 and n_rows 0.
+ * The launch decision (ctr_diffusion_ci_plan reports it without a handle or a device; it checks the
+ * scalars of the descriptor only) follows n_max = n_perm n_frames (times n_tracks when pooled), the
+ * host-known bound on n, never n itself:
+ *   rows_in_lds: n_max rows fit into CTR_DIFFUSION_CI_LDS_BYTES (8 D n_max <= it): a workgroup of 512
+ *     resamples stages the rows of its pair in LDS once (lds_bytes = 8 D n_max) and gathers from there;
+ *     otherwise (lds_bytes 0) the rows are gathered from the scratch in global memory;
+ *   the scratch of a pair: 8 (D n_max + D (D + 1) / 2 B + 1) bytes -- rows, the distinct entries of
+ *     the statistics, n; pairs_per_chunk = min(pairs, CTR_DIFFUSION_CI_SCRATCH_BYTES / that), and
+ *     scratch_bytes = pairs_per_chunk times that.  A call with more pairs is processed in chunks on
+ *     the stream, without a host synchronisation; a single pair that does not fit is
+ *     CTR_ERR_UNSUPPORTED, and so is n_samples > CTR_DIFFUSION_CI_MAX_SAMPLES (an entry's statistics
+ *     are sorted in the LDS of one workgroup: 128 KiB).
+ * No floating-point atomics, no sum across lanes in a resample: a pair gives the same bytes alone, in
+ * a batch, in a sweep and in any chunking.  The scratch is ctr_diffusion_device's and belongs to the
+ * handle: calls of one handle are ordered on the device whatever streams they are given.
+ * tensor, n_rows, z0, accel and ranks may be NULL.  The descriptor is checked before the handle, as
+ * for ctr_characterize_device.  Device pointers, lags included; asynchronous on `hip_stream`
+ * (NULL = the handle's stream). */
+enum { CTR_CI_BCA = 0, CTR_CI_PI = 1 };
+#define CTR_DIFFUSION_CI_MAX_SAMPLES 16384
+#define CTR_DIFFUSION_CI_MAX_ALPHA 8
+#define CTR_DIFFUSION_CI_LDS_BYTES 65536
+#define CTR_DIFFUSION_CI_SCRATCH_BYTES 268435456
+typedef struct ctr_diffusion_ci {
+  int32_t ndim;            /* 2 -> 3x3, 3 -> 6x6 */
+  int32_t n_perm;
+  int64_t n_tracks, n_frames, n_lags;
+  double  fps;
+  const int64_t* lags;     /* [n_lags] */
+  const double* positions; /* [T, F, 3] */
+  const double* bases;     /* [T, P, F, 3, 3] */
+  int64_t  n_samples;      /* B in [1, CTR_DIFFUSION_CI_MAX_SAMPLES] */
+  uint64_t seed;
+  int32_t  method;         /* CTR_CI_BCA or CTR_CI_PI */
+  int32_t  n_alpha;        /* K in [1, CTR_DIFFUSION_CI_MAX_ALPHA] */
+  double   z_alpha[CTR_DIFFUSION_CI_MAX_ALPHA];  /* Phi^-1(alphas), taken on the host (CTR_CI_BCA) */
+  double   alphas[CTR_DIFFUSION_CI_MAX_ALPHA];   /* probabilities */
+  int32_t  pool_tracks;    /* != 0: one interval per lag over the rows of all tracks (Np = n_lags, else T n_lags) */
+  double*  interval;       /* [Np, K, D, D] out */
+  double*  tensor;         /* [Np, D, D] out: ostat */
+  int64_t* n_rows;         /* [Np] out: n */
+  double*  z0;             /* [Np, D, D] out */
+  double*  accel;          /* [Np, D, D] out: a */
+  int64_t* ranks;          /* [Np, K, D, D] out */
+} ctr_diffusion_ci;
+int ctr_diffusion_ci_device(ctr_handle* h, const ctr_diffusion_ci* d, void* hip_stream);
+int ctr_diffusion_ci_plan(const ctr_diffusion_ci* d, int32_t* rows_in_lds, int64_t* lds_bytes, int64_t* scratch_bytes,
+                          int64_t* pairs_per_chunk);
+
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
  * several batches in flight hand finished batches on (e.g. to the result gather) from the host
