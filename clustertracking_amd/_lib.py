@@ -12,17 +12,55 @@ from . import _abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CTREFINE_LIB') or os.path.join(_HERE, 'csrc', 'libctrefine.so')
 
-# every symbol include/ctrefine.h declares
-EXPORTS = ('ctr_abi_version', 'ctr_create', 'ctr_destroy', 'ctr_last_error',
-           'ctr_validate_problem', 'ctr_cluster_n_vars', 'ctr_cluster_kernel', 'ctr_refine_batch',
-           'ctr_plan_create', 'ctr_plan_destroy', 'ctr_refine_batch_device',
-           'ctr_frame_max_device', 'ctr_synchronize', 'ctr_last_kernel_ms',
-           'ctr_find_clusters', 'ctr_engine_wait_stream', 'ctr_stream_wait_engine',
-           'ctr_draw_frames_device', 'ctr_locate_maxima_device', 'ctr_characterize_device', 'ctr_link_device',
-           'ctr_preprocess_device', 'ctr_orientation_device', 'ctr_diffusion_device',
-           'ctr_relocate_device', 'ctr_relocate_plan', 'ctr_diffusion_ci_device', 'ctr_diffusion_ci_plan',
-           'ctr_query_done', 'ctr_ipc_alloc', 'ctr_ipc_open',
-           'ctr_ipc_probe', 'ctr_ipc_read', 'ctr_ipc_close', 'ctr_ipc_free')
+_P = C.POINTER
+_H = _S = C.c_void_p      # an engine handle; a raw stream handle
+
+
+def _stage(desc):
+    return (C.c_int, [_H, _P(desc), _S])
+
+
+# every symbol include/ctrefine.h declares: (restype, argtypes)
+SIGNATURES = {
+    'ctr_abi_version': (C.c_int, []),
+    'ctr_create': (C.c_int, [_P(C.c_void_p), C.c_int]),
+    'ctr_destroy': (None, [_H]),
+    'ctr_last_error': (C.c_char_p, [_H]),
+    'ctr_validate_problem': (C.c_int, [_P(_abi.Problem), C.c_char_p, C.c_int]),
+    'ctr_cluster_n_vars': (C.c_int, [_P(_abi.Problem), C.c_int]),
+    'ctr_cluster_kernel': (C.c_int, [_P(_abi.Problem), C.c_int64, _P(_abi.KernelChoice)]),
+    'ctr_refine_batch': (C.c_int, [_H, _P(_abi.Problem), _P(_abi.Batch)]),
+    'ctr_plan_create': (C.c_int, [_H, _P(_abi.Problem), C.c_int64, C.c_void_p, _P(C.c_void_p)]),
+    'ctr_plan_destroy': (None, [C.c_void_p]),
+    'ctr_refine_batch_device': (C.c_int, [_H, C.c_void_p, _P(_abi.Batch), _S]),
+    'ctr_frame_max_device': (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, _S]),
+    'ctr_synchronize': (C.c_int, [_H, _S]),
+    'ctr_last_kernel_ms': (C.c_int, [_H, _P(C.c_double), _P(C.c_double)]),
+    'ctr_find_clusters': (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    'ctr_engine_wait_stream': (C.c_int, [_H, _S]),
+    'ctr_stream_wait_engine': (C.c_int, [_H, _S]),
+    'ctr_draw_frames_device': (C.c_int, [_H, _P(_abi.Synth), C.c_void_p, _S]),
+    'ctr_locate_maxima_device': _stage(_abi.Locate),
+    'ctr_characterize_device': _stage(_abi.Characterize),
+    'ctr_link_device': _stage(_abi.Link),
+    'ctr_preprocess_device': _stage(_abi.Preprocess),
+    'ctr_orientation_device': _stage(_abi.Orientation),
+    'ctr_diffusion_device': _stage(_abi.Diffusion),
+    'ctr_relocate_device': _stage(_abi.Relocate),
+    'ctr_relocate_plan': (C.c_int, [_P(_abi.Relocate), _P(C.c_int64), _P(C.c_int64)]),
+    'ctr_diffusion_ci_device': _stage(_abi.DiffusionCI),
+    'ctr_diffusion_ci_plan': (C.c_int, [_P(_abi.DiffusionCI), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
+                                        _P(C.c_int64)]),
+    'ctr_query_done': (C.c_int, [_H]),
+    'ctr_ipc_alloc': (C.c_int, [_H, C.c_int64, _P(C.c_void_p), C.c_void_p]),
+    'ctr_ipc_open': (C.c_int, [_H, C.c_void_p, _P(C.c_void_p)]),
+    'ctr_ipc_probe': (C.c_int, [_H, C.c_void_p, C.c_int64]),
+    'ctr_ipc_read': (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64]),
+    'ctr_ipc_close': (C.c_int, [_H, C.c_void_p]),
+    'ctr_ipc_free': (C.c_int, [_H, C.c_void_p]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 _lib = None
 _lock = threading.Lock()
@@ -70,88 +108,14 @@ def load():
                 "`make -C clustertracking_amd/csrc`. There is no CPU fallback."
                 % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        P = C.POINTER
-        lib.ctr_abi_version.restype = C.c_int
-        lib.ctr_create.argtypes = [P(C.c_void_p), C.c_int]
-        lib.ctr_create.restype = C.c_int
-        lib.ctr_destroy.argtypes = [C.c_void_p]
-        lib.ctr_destroy.restype = None
-        lib.ctr_last_error.argtypes = [C.c_void_p]
-        lib.ctr_last_error.restype = C.c_char_p
-        lib.ctr_validate_problem.argtypes = [P(_abi.Problem), C.c_char_p, C.c_int]
-        lib.ctr_validate_problem.restype = C.c_int
-        lib.ctr_cluster_n_vars.argtypes = [P(_abi.Problem), C.c_int]
-        lib.ctr_cluster_n_vars.restype = C.c_int
-        lib.ctr_cluster_kernel.argtypes = [P(_abi.Problem), C.c_int64, P(_abi.KernelChoice)]
-        lib.ctr_cluster_kernel.restype = C.c_int
-        lib.ctr_refine_batch.argtypes = [C.c_void_p, P(_abi.Problem), P(_abi.Batch)]
-        lib.ctr_refine_batch.restype = C.c_int
-        lib.ctr_plan_create.argtypes = [C.c_void_p, P(_abi.Problem), C.c_int64,
-                                        C.c_void_p, P(C.c_void_p)]
-        lib.ctr_plan_create.restype = C.c_int
-        lib.ctr_plan_destroy.argtypes = [C.c_void_p]
-        lib.ctr_plan_destroy.restype = None
-        lib.ctr_refine_batch_device.argtypes = [C.c_void_p, C.c_void_p,
-                                                P(_abi.Batch), C.c_void_p]
-        lib.ctr_refine_batch_device.restype = C.c_int
-        lib.ctr_frame_max_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32,
-                                             C.c_int64, C.c_int64, C.c_void_p,
-                                             C.c_void_p]
-        lib.ctr_frame_max_device.restype = C.c_int
-        if hasattr(lib, 'ctr_find_clusters'):   # absent only in older diagnostic builds
-            lib.ctr_find_clusters.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-            lib.ctr_find_clusters.restype = C.c_int
-        lib.ctr_synchronize.argtypes = [C.c_void_p, C.c_void_p]
-        lib.ctr_synchronize.restype = C.c_int
-        for name in ('ctr_engine_wait_stream', 'ctr_stream_wait_engine'):
-            if hasattr(lib, name):   # (absent from libraries built before they existed)
-                getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p]
-                getattr(lib, name).restype = C.c_int
-        lib.ctr_draw_frames_device.argtypes = [C.c_void_p, P(_abi.Synth), C.c_void_p, C.c_void_p]
-        lib.ctr_draw_frames_device.restype = C.c_int
-        if hasattr(lib, 'ctr_locate_maxima_device'):   # (absent from libraries built before it existed)
-            lib.ctr_locate_maxima_device.argtypes = [C.c_void_p, P(_abi.Locate), C.c_void_p]
-            lib.ctr_locate_maxima_device.restype = C.c_int
-        if hasattr(lib, 'ctr_characterize_device'):   # (absent from libraries built before it existed)
-            lib.ctr_characterize_device.argtypes = [C.c_void_p, P(_abi.Characterize), C.c_void_p]
-            lib.ctr_characterize_device.restype = C.c_int
-        if hasattr(lib, 'ctr_link_device'):   # (absent from libraries built before it existed)
-            lib.ctr_link_device.argtypes = [C.c_void_p, P(_abi.Link), C.c_void_p]
-            lib.ctr_link_device.restype = C.c_int
-        if hasattr(lib, 'ctr_preprocess_device'):   # (an addition to ABI 8: absent from earlier builds of it)
-            lib.ctr_preprocess_device.argtypes = [C.c_void_p, P(_abi.Preprocess), C.c_void_p]
-            lib.ctr_preprocess_device.restype = C.c_int
-        if hasattr(lib, 'ctr_orientation_device'):   # (additions to ABI 8: absent from earlier builds of it)
-            lib.ctr_orientation_device.argtypes = [C.c_void_p, P(_abi.Orientation), C.c_void_p]
-            lib.ctr_orientation_device.restype = C.c_int
-            lib.ctr_diffusion_device.argtypes = [C.c_void_p, P(_abi.Diffusion), C.c_void_p]
-            lib.ctr_diffusion_device.restype = C.c_int
-        if hasattr(lib, 'ctr_relocate_device'):   # (additions to ABI 8: absent from earlier builds of it)
-            lib.ctr_relocate_device.argtypes = [C.c_void_p, P(_abi.Relocate), C.c_void_p]
-            lib.ctr_relocate_device.restype = C.c_int
-            lib.ctr_relocate_plan.argtypes = [P(_abi.Relocate), P(C.c_int64), P(C.c_int64)]
-            lib.ctr_relocate_plan.restype = C.c_int
-        if hasattr(lib, 'ctr_diffusion_ci_device'):   # (additions to ABI 8: absent from earlier builds of it)
-            lib.ctr_diffusion_ci_device.argtypes = [C.c_void_p, P(_abi.DiffusionCI), C.c_void_p]
-            lib.ctr_diffusion_ci_device.restype = C.c_int
-            lib.ctr_diffusion_ci_plan.argtypes = [P(_abi.DiffusionCI), P(C.c_int32), P(C.c_int64), P(C.c_int64), P(C.c_int64)]
-            lib.ctr_diffusion_ci_plan.restype = C.c_int
-        lib.ctr_query_done.argtypes = [C.c_void_p]
-        lib.ctr_query_done.restype = C.c_int
-        lib.ctr_ipc_alloc.argtypes = [C.c_void_p, C.c_int64, P(C.c_void_p), C.c_void_p]
-        lib.ctr_ipc_open.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p)]
-        lib.ctr_ipc_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-        lib.ctr_ipc_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-        lib.ctr_ipc_close.argtypes = [C.c_void_p, C.c_void_p]
-        lib.ctr_ipc_free.argtypes = [C.c_void_p, C.c_void_p]
-        for fn in (lib.ctr_ipc_alloc, lib.ctr_ipc_open, lib.ctr_ipc_probe, lib.ctr_ipc_read,
-                   lib.ctr_ipc_close, lib.ctr_ipc_free):
-            fn.restype = C.c_int
-        lib.ctr_last_kernel_ms.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double)]
-        lib.ctr_last_kernel_ms.restype = C.c_int
-        if lib.ctr_abi_version() != _abi.ABI_VERSION:
+        if hasattr(lib, 'ctr_abi_version') and lib.ctr_abi_version() != _abi.ABI_VERSION:
             raise EngineError("libctrefine.so ABI version mismatch")
+        missing = [name for name in EXPORTS if not hasattr(lib, name)]
+        if missing:
+            raise EngineError("%s does not export %s: rebuild it" % (LIB_PATH, ', '.join(missing)))
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return lib
 
@@ -183,8 +147,6 @@ def diffusion_ci_plan(desc):
     ``(rows_in_lds, lds_bytes, scratch_bytes, pairs_per_chunk)``; ``ValueError`` /
     ``NotImplementedError`` as the call itself."""
     lib = load()
-    if not hasattr(lib, 'ctr_diffusion_ci_plan'):
-        raise EngineError("libctrefine.so does not export ctr_diffusion_ci_plan: rebuild it")
     in_lds, lds, scratch, chunk = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
     rc = lib.ctr_diffusion_ci_plan(C.byref(desc), C.byref(in_lds), C.byref(lds), C.byref(scratch), C.byref(chunk))
     if rc != _abi.OK:
@@ -277,56 +239,6 @@ class Engine(object):
         self._check(self._lib.ctr_draw_frames_device(self._h, C.byref(synth), C.c_void_p(frames_ptr),
                                                      C.c_void_p(stream or 0)), 'ctr_draw_frames_device')
 
-    def locate_maxima_device(self, loc, stream=None):
-        """``ctr_locate_maxima_device``: ``loc`` is an ``_abi.Locate`` with device pointers."""
-        self._check(self._lib.ctr_locate_maxima_device(self._h, C.byref(loc), C.c_void_p(stream or 0)),
-                    'ctr_locate_maxima_device', too_large=True)
-
-    def characterize_device(self, desc, stream=None):
-        """``ctr_characterize_device``: ``desc`` is an ``_abi.Characterize`` with device pointers."""
-        self._check(self._lib.ctr_characterize_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
-                    'ctr_characterize_device')
-
-    def link_device(self, desc, stream=None):
-        """``ctr_link_device``: ``desc`` is an ``_abi.Link`` with device pointers."""
-        self._check(self._lib.ctr_link_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
-                    'ctr_link_device')
-
-    def preprocess_device(self, desc, stream=None):
-        """``ctr_preprocess_device``: ``desc`` is an ``_abi.Preprocess`` with device pointers."""
-        if not hasattr(self._lib, 'ctr_preprocess_device'):
-            raise EngineError("libctrefine.so does not export ctr_preprocess_device: rebuild it")
-        self._check(self._lib.ctr_preprocess_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
-                    'ctr_preprocess_device', too_large=True)
-
-    def orientation_device(self, desc, stream=None):
-        """``ctr_orientation_device``: ``desc`` is an ``_abi.Orientation`` with device pointers."""
-        if not hasattr(self._lib, 'ctr_orientation_device'):
-            raise EngineError("libctrefine.so does not export ctr_orientation_device: rebuild it")
-        self._check(self._lib.ctr_orientation_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
-                    'ctr_orientation_device')
-
-    def diffusion_device(self, desc, stream=None):
-        """``ctr_diffusion_device``: ``desc`` is an ``_abi.Diffusion`` with device pointers."""
-        if not hasattr(self._lib, 'ctr_diffusion_device'):
-            raise EngineError("libctrefine.so does not export ctr_diffusion_device: rebuild it")
-        self._check(self._lib.ctr_diffusion_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
-                    'ctr_diffusion_device')
-
-    def diffusion_ci_device(self, desc, stream=None):
-        """``ctr_diffusion_ci_device``: ``desc`` is an ``_abi.DiffusionCI`` with device pointers."""
-        if not hasattr(self._lib, 'ctr_diffusion_ci_device'):
-            raise EngineError("libctrefine.so does not export ctr_diffusion_ci_device: rebuild it")
-        self._check(self._lib.ctr_diffusion_ci_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
-                    'ctr_diffusion_ci_device')
-
-    def relocate_device(self, desc, stream=None):
-        """``ctr_relocate_device``: ``desc`` is an ``_abi.Relocate`` with device pointers."""
-        if not hasattr(self._lib, 'ctr_relocate_device'):
-            raise EngineError("libctrefine.so does not export ctr_relocate_device: rebuild it")
-        self._check(self._lib.ctr_relocate_device(self._h, C.byref(desc), C.c_void_p(stream or 0)),
-                    'ctr_relocate_device')
-
     def query_done(self):
         """True when the last ``refine_batch_device`` call of this engine has finished on the
         device (``ctr_query_done``; never blocks)."""
@@ -383,11 +295,45 @@ class Engine(object):
         self._check(self._lib.ctr_stream_wait_engine(self._h, C.c_void_p(stream or 0)),
                     'ctr_stream_wait_engine')
 
+    def on_current_stream(self, call, *args, dev):
+        """``call(*args, stream)`` in order with torch's current stream on ``dev``: on that stream,
+        or, where that is the legacy default stream (handle 0, which to the engine means its own
+        stream), on the engine's stream, ordered with the default stream by events on the device."""
+        import torch
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if stream:
+            call(*args, stream)
+        else:
+            self.engine_wait_stream(0)
+            call(*args, 0)
+            self.stream_wait_engine(0)
+
     def last_kernel_ms(self):
         a, b = C.c_double(), C.c_double()
         self._check(self._lib.ctr_last_kernel_ms(self._h, C.byref(a), C.byref(b)),
                     'ctr_last_kernel_ms')
         return a.value, b.value
+
+
+def _stage_method(symbol, too_large):
+    def method(self, desc, stream=None):
+        self._check(getattr(self._lib, symbol)(self._h, C.byref(desc), C.c_void_p(stream or 0)),
+                    symbol, too_large=too_large)
+    method.__doc__ = "``%s``: ``desc`` is its ``_abi`` descriptor with device pointers." % symbol
+    return method
+
+
+# the stage calls ``Engine.<name>(desc, stream=None)``: (name, symbol, too_large of Engine._check)
+for _name, _symbol, _too_large in (
+        ('locate_maxima_device', 'ctr_locate_maxima_device', True),
+        ('characterize_device', 'ctr_characterize_device', False),
+        ('link_device', 'ctr_link_device', False),
+        ('preprocess_device', 'ctr_preprocess_device', True),
+        ('orientation_device', 'ctr_orientation_device', False),
+        ('diffusion_device', 'ctr_diffusion_device', False),
+        ('diffusion_ci_device', 'ctr_diffusion_ci_device', False),
+        ('relocate_device', 'ctr_relocate_device', False)):
+    setattr(Engine, _name, _stage_method(_symbol, _too_large))
 
 
 class Plan(object):

@@ -91,18 +91,22 @@ struct ctr_plan {
   int lp_half[3] = {0, 0, 0};
 };
 
+// a grow-only block of device memory of a handle (reserve).  event: the end of the last call that
+// used it, where calls on several streams share the block (run_stage); null elsewhere
+struct Scratch {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  hipEvent_t event = nullptr;
+};
+
 struct ctr_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool ev_valid = false;
   std::string err;
-  // grow-only device scratch
-  void* d_buf = nullptr;
-  size_t d_buf_bytes = 0;
-  unsigned long long* d_enc = nullptr;
-  double* d_fmax = nullptr;
-  int64_t fmax_cap = 0;
+  // host-buffer calls; the frame maxima as the kernels encode them and as doubles
+  Scratch buf, enc, fmax;
   // the kernel of every cell of the dispatch: [CTR_KFAM_*][ndim-2][iso][slot] (kernel_of); an
   // unreachable cell is null.  attr_set: its dynamic LDS limit is set (table_kernel)
   struct { KernelInfo k; bool attr_set; } kernels[NFAM][2][2][NSLOT] = {};
@@ -110,14 +114,8 @@ struct ctr_handle {
   hipStream_t side[NSIDE] = {};
   hipEvent_t ev_fork = nullptr, ev_gate = nullptr, ev_order = nullptr, ev_join[NSIDE] = {};
   int* d_counter = nullptr;       // work counters of the small-kernel launches
-  // ctr_link_device: grow-only scratch and the end of the last call (calls share the scratch)
-  void* d_link = nullptr;
-  size_t d_link_bytes = 0;
-  hipEvent_t ev_link = nullptr;
-  // ctr_diffusion_device and ctr_diffusion_ci_device: the same for their partial sums, rows and statistics
-  void* d_motion = nullptr;
-  size_t d_motion_bytes = 0;
-  hipEvent_t ev_motion = nullptr;
+  // ctr_link_device; ctr_diffusion_device and ctr_diffusion_ci_device (partial sums, rows, statistics)
+  Scratch link, motion;
 };
 
 namespace {
@@ -224,14 +222,51 @@ size_t host_dtype_size(int dtype) {
   }
 }
 
+// at least `need` bytes in sc.  A block that grows is replaced once the device is idle: a kernel
+// of an earlier call, on whichever stream, may still use the old one.
+int reserve(ctr_handle* h, Scratch& sc, size_t need, const char* or_else) {
+  if (need <= sc.bytes) return CTR_OK;
+  if (sc.ptr) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(sc.ptr); sc.ptr = nullptr; sc.bytes = 0; }
+  if (hipMalloc(&sc.ptr, need) != hipSuccess) { sc.ptr = nullptr; return fail(h, CTR_ERR_NOMEM, or_else); }
+  sc.bytes = need;
+  return CTR_OK;
+}
+
 int ensure_fmax(ctr_handle* h, int64_t n_frames) {
-  if (n_frames <= h->fmax_cap) return CTR_OK;
-  if (h->d_enc) { (void)hipFree(h->d_enc); h->d_enc = nullptr; }
-  if (h->d_fmax) { (void)hipFree(h->d_fmax); h->d_fmax = nullptr; }
-  h->fmax_cap = 0;
-  HIP_TRY(h, hipMalloc((void**)&h->d_enc, sizeof(unsigned long long) * (size_t)n_frames));
-  HIP_TRY(h, hipMalloc((void**)&h->d_fmax, sizeof(double) * (size_t)n_frames));
-  h->fmax_cap = n_frames;
+  const int rc = reserve(h, h->enc, sizeof(unsigned long long) * (size_t)n_frames, "cannot allocate the frame maxima on the device");
+  return rc ? rc : reserve(h, h->fmax, sizeof(double) * (size_t)n_frames, "cannot allocate the frame maxima on the device");
+}
+
+// What every ctr_<stage>_device call does around its stage unit (kargs.h: StageRun).  The
+// descriptor is checked before the handle is touched: a bad one is reported (through
+// ctr_last_error of a null handle) even where there is no device to make a handle on.  scratch:
+// the block of the handle that the stage uses, or null; calls that share a block run one after
+// the other on the device, in the order of the calls, whichever their streams.  A stage with
+// scratch that asks for no byte has nothing to launch.
+template <class D, class... Extra>
+int run_stage(const char* name, ctr_handle* h, Scratch ctr_handle::*scratch, const D* d, void* hip_stream,
+              int (*launch)(const D*, StageRun*, const char**, Extra*...)) {
+  const char* msg = "";
+  auto failed = [&](int rc, const char* why) { return fail(h, rc, std::string(name) + ": " + why); };
+  StageRun run = {STAGE_CHECK, nullptr, nullptr, 0};
+  int rc = launch(d, &run, &msg, (Extra*)nullptr...);
+  if (rc != CTR_OK) return failed(rc, msg);
+  if (!h) return failed(CTR_ERR_INVALID, "null handle");
+  if (scratch && run.scratch_bytes == 0) return CTR_OK;   // nothing to launch: the device is not touched
+  HIP_TRY(h, hipSetDevice(h->device));
+  run.mode = STAGE_LAUNCH;
+  run.stream = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  Scratch* sc = scratch ? &(h->*scratch) : nullptr;
+  if (sc) {
+    if (!sc->event) HIP_TRY(h, hipEventCreateWithFlags(&sc->event, hipEventDisableTiming));
+    else HIP_TRY(h, hipStreamWaitEvent(run.stream, sc->event, 0));
+    rc = reserve(h, *sc, run.scratch_bytes, "cannot allocate the scratch on the device");
+    if (rc != CTR_OK) return failed(rc, h->err.c_str());
+    run.scratch = sc->ptr;
+  }
+  rc = launch(d, &run, &msg, (Extra*)nullptr...);
+  if (rc != CTR_OK) return failed(rc, msg);
+  if (sc) HIP_TRY(h, hipEventRecord(sc->event, run.stream));
   return CTR_OK;
 }
 
@@ -244,13 +279,13 @@ int launch_frame_max(ctr_handle* h, const void* frames, int dtype, int64_t n_fra
   if (rc) return rc;
   const size_t chunk_elems = FM_CHUNK_BYTES / isz;
   const int chunks = (int)(((size_t)frame_elems + chunk_elems - 1) / chunk_elems);
-  HIP_TRY(h, hipMemsetAsync(h->d_enc, 0, sizeof(unsigned long long) * (size_t)n_frames, s));
+  HIP_TRY(h, hipMemsetAsync(h->enc.ptr, 0, sizeof(unsigned long long) * (size_t)n_frames, s));
   const long long grid = (long long)n_frames * chunks;
   if (grid > 0x7fffffffLL) return fail(h, CTR_ERR_INVALID, "frame block too large for one launch");
   hipLaunchKernelGGL(frame_max_kernel, dim3((unsigned)grid), dim3(FM_THREADS), 0, s, frames, dtype,
-                     (size_t)frame_elems, chunks, chunk_elems, h->d_enc);
+                     (size_t)frame_elems, chunks, chunk_elems, (unsigned long long*)h->enc.ptr);
   hipLaunchKernelGGL(frame_max_decode_kernel, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, s,
-                     h->d_enc, out, n_frames);
+                     (const unsigned long long*)h->enc.ptr, out, n_frames);
   HIP_TRY(h, hipGetLastError());
   return CTR_OK;
 }
@@ -455,9 +490,10 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->d_buf) (void)hipFree(h->d_buf);
-  if (h->d_enc) (void)hipFree(h->d_enc);
-  if (h->d_fmax) (void)hipFree(h->d_fmax);
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion}) {
+    if (sc->ptr) (void)hipFree(sc->ptr);
+    if (sc->event) (void)hipEventDestroy(sc->event);
+  }
   for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& st : h->side) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -466,10 +502,6 @@ void ctr_destroy(ctr_handle* h) {
   if (h->ev_done) (void)hipEventDestroy(h->ev_done);
   for (auto& ev : h->ev_join) if (ev) (void)hipEventDestroy(ev);
   if (h->d_counter) (void)hipFree(h->d_counter);
-  if (h->d_link) (void)hipFree(h->d_link);
-  if (h->ev_link) (void)hipEventDestroy(h->ev_link);
-  if (h->d_motion) (void)hipFree(h->d_motion);
-  if (h->ev_motion) (void)hipEventDestroy(h->ev_motion);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -623,7 +655,7 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
   HIP_TRY(h, hipEventRecord(h->ev[0], s));
   int rc = ensure_fmax(h, b->n_frames > 0 ? b->n_frames : 1);
   if (rc) return rc;
-  rc = launch_frame_max(h, b->frames, b->frame_dtype, b->n_frames, frame_elems, h->d_fmax, s);
+  rc = launch_frame_max(h, b->frames, b->frame_dtype, b->n_frames, frame_elems, (double*)h->fmax.ptr, s);
   if (rc) return rc;
   HIP_TRY(h, hipEventRecord(h->ev[1], s));
 
@@ -649,7 +681,7 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
   k.n_rounds = b->n_rounds;
   k.n_iter = b->n_iter;
   k.params_std = b->params_std;
-  k.fmax = h->d_fmax;
+  k.fmax = (const double*)h->fmax.ptr;
   k.lp_w = plan->lowpass ? plan->d_lp_w : nullptr;
   k.cg_tol2_far = LARGE_CG_TOL2_FAR;
   k.cg_tol2_near = LARGE_CG_TOL2_NEAR;
@@ -926,12 +958,8 @@ int ctr_find_clusters(ctr_handle* h, int32_t ndim, const double* pos, const int3
   const size_t sz_pos = al(sizeof(double) * (size_t)N * ndim), sz_fo = al(sizeof(int32_t) * (size_t)(n_frames + 1));
   const size_t sz_i = al(sizeof(int32_t) * (size_t)N);
   const size_t total = 2 * sz_pos + sz_fo + 3 * sz_i;
-  if (total > h->d_buf_bytes) {
-    if (h->d_buf) { (void)hipFree(h->d_buf); h->d_buf = nullptr; h->d_buf_bytes = 0; }
-    if (hipMalloc(&h->d_buf, total) != hipSuccess) return fail(h, CTR_ERR_NOMEM, "cannot allocate device memory");
-    h->d_buf_bytes = total;
-  }
-  char* q = (char*)h->d_buf;
+  if (int rc = reserve(h, h->buf, total, "cannot allocate device memory")) return rc;
+  char* q = (char*)h->buf.ptr;
   double* d_pos = (double*)q; q += sz_pos;
   double* d_spos = (double*)q; q += sz_pos;
   int32_t* d_fo = (int32_t*)q; q += sz_fo;
@@ -1014,68 +1042,26 @@ int ctr_locate_maxima_device(ctr_handle* h, const ctr_locate* l, void* hip_strea
 }
 
 int ctr_characterize_device(ctr_handle* h, const ctr_characterize* c, void* hip_stream) {
-  // the descriptor is checked before the handle is touched: a bad one is reported (through
-  // ctr_last_error of a null handle) even where there is no device to make a handle on
-  const char* msg = "";
-  int rc = ctr_characterize_launch(c, false, nullptr, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_characterize_device: ") + msg);
-  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_characterize_device: null handle");
-  HIP_TRY(h, hipSetDevice(h->device));
-  rc = ctr_characterize_launch(c, true, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_characterize_device: ") + msg);
-  return CTR_OK;
+  return run_stage("ctr_characterize_device", h, nullptr, c, hip_stream, ctr_characterize_launch);
 }
 
 int ctr_preprocess_device(ctr_handle* h, const ctr_preprocess* p, void* hip_stream) {
-  // the descriptor first, as ctr_characterize_device
-  const char* msg = "";
-  int rc = ctr_preprocess_launch(p, false, nullptr, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_preprocess_device: ") + msg);
-  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_preprocess_device: null handle");
-  HIP_TRY(h, hipSetDevice(h->device));
-  rc = ctr_preprocess_launch(p, true, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_preprocess_device: ") + msg);
-  return CTR_OK;
+  return run_stage("ctr_preprocess_device", h, nullptr, p, hip_stream, ctr_preprocess_launch);
 }
 
 int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream) {
-  // the descriptor first, as ctr_characterize_device
-  const char* msg = "";
-  size_t need = 0;
-  int rc = ctr_link_launch(l, nullptr, &need, nullptr, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_link_device: ") + msg);
-  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_link_device: null handle");
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  if (!h->ev_link) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_link, hipEventDisableTiming));
-  else HIP_TRY(h, hipStreamWaitEvent(s, h->ev_link, 0));
-  if (need > h->d_link_bytes) {
-    if (h->d_link) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->d_link); h->d_link = nullptr; h->d_link_bytes = 0; }
-    if (hipMalloc(&h->d_link, need) != hipSuccess) return fail(h, CTR_ERR_NOMEM, "ctr_link_device: cannot allocate the scratch on the device");
-    h->d_link_bytes = need;
-  }
-  rc = ctr_link_launch(l, h->d_link, nullptr, s, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_link_device: ") + msg);
-  HIP_TRY(h, hipEventRecord(h->ev_link, s));
-  return CTR_OK;
+  return run_stage("ctr_link_device", h, &ctr_handle::link, l, hip_stream, ctr_link_launch);
 }
 
 int ctr_relocate_device(ctr_handle* h, const ctr_relocate* r, void* hip_stream) {
-  // the descriptor first, as ctr_characterize_device; the kernel needs no scratch
-  const char* msg = "";
-  int rc = ctr_relocate_launch(r, true, false, nullptr, nullptr, nullptr, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_relocate_device: ") + msg);
-  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_relocate_device: null handle");
-  HIP_TRY(h, hipSetDevice(h->device));
-  rc = ctr_relocate_launch(r, true, true, hip_stream ? (hipStream_t)hip_stream : h->stream, nullptr, nullptr, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_relocate_device: ") + msg);
-  return CTR_OK;
+  return run_stage("ctr_relocate_device", h, nullptr, r, hip_stream, ctr_relocate_launch);
 }
 
 int ctr_relocate_plan(const ctr_relocate* r, int64_t* tile_pixels, int64_t* lds_bytes) {
   const char* msg = "";
   long long tile = 0, lds = 0;
-  const int rc = ctr_relocate_launch(r, false, false, nullptr, &tile, &lds, &msg);
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  const int rc = ctr_relocate_launch(r, &run, &msg, &tile, &lds);
   if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_relocate_plan: ") + msg);
   if (tile_pixels) *tile_pixels = tile;
   if (lds_bytes) *lds_bytes = lds;
@@ -1083,68 +1069,24 @@ int ctr_relocate_plan(const ctr_relocate* r, int64_t* tile_pixels, int64_t* lds_
 }
 
 int ctr_orientation_device(ctr_handle* h, const ctr_orientation* o, void* hip_stream) {
-  // the descriptor first, as ctr_characterize_device
-  const char* msg = "";
-  int rc = ctr_orientation_launch(o, false, nullptr, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_orientation_device: ") + msg);
-  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_orientation_device: null handle");
-  HIP_TRY(h, hipSetDevice(h->device));
-  rc = ctr_orientation_launch(o, true, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_orientation_device: ") + msg);
-  return CTR_OK;
+  return run_stage("ctr_orientation_device", h, nullptr, o, hip_stream, ctr_orientation_launch);
 }
 
 int ctr_diffusion_device(ctr_handle* h, const ctr_diffusion* d, void* hip_stream) {
-  // the descriptor first, as ctr_characterize_device; the scratch as ctr_link_device
-  const char* msg = "";
-  size_t need = 0;
-  int rc = ctr_diffusion_launch(d, nullptr, &need, nullptr, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_device: ") + msg);
-  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_diffusion_device: null handle");
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  if (!h->ev_motion) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_motion, hipEventDisableTiming));
-  else HIP_TRY(h, hipStreamWaitEvent(s, h->ev_motion, 0));
-  if (need > h->d_motion_bytes) {
-    if (h->d_motion) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->d_motion); h->d_motion = nullptr; h->d_motion_bytes = 0; }
-    if (hipMalloc(&h->d_motion, need) != hipSuccess) return fail(h, CTR_ERR_NOMEM, "ctr_diffusion_device: cannot allocate the partial sums on the device");
-    h->d_motion_bytes = need;
-  }
-  rc = ctr_diffusion_launch(d, h->d_motion, nullptr, s, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_device: ") + msg);
-  HIP_TRY(h, hipEventRecord(h->ev_motion, s));
-  return CTR_OK;
+  return run_stage("ctr_diffusion_device", h, &ctr_handle::motion, d, hip_stream, ctr_diffusion_launch);
 }
 
 int ctr_diffusion_ci_device(ctr_handle* h, const ctr_diffusion_ci* d, void* hip_stream) {
-  // the descriptor first, as ctr_characterize_device; the scratch is ctr_diffusion_device's, and so is the order of the calls
-  const char* msg = "";
-  ctr_ci_plan plan = {};
-  int rc = ctr_diffusion_ci_launch(d, true, nullptr, nullptr, &plan, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_ci_device: ") + msg);
-  if (!h) return fail(h, CTR_ERR_INVALID, "ctr_diffusion_ci_device: null handle");
-  if (plan.pairs_per_chunk == 0) return CTR_OK;
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  if (!h->ev_motion) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_motion, hipEventDisableTiming));
-  else HIP_TRY(h, hipStreamWaitEvent(s, h->ev_motion, 0));
-  const size_t need = (size_t)plan.scratch_bytes + 256;
-  if (need > h->d_motion_bytes) {
-    if (h->d_motion) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->d_motion); h->d_motion = nullptr; h->d_motion_bytes = 0; }
-    if (hipMalloc(&h->d_motion, need) != hipSuccess) return fail(h, CTR_ERR_NOMEM, "ctr_diffusion_ci_device: cannot allocate the scratch on the device");
-    h->d_motion_bytes = need;
-  }
-  rc = ctr_diffusion_ci_launch(d, true, h->d_motion, s, nullptr, &msg);
-  if (rc != CTR_OK) return fail(h, rc, std::string("ctr_diffusion_ci_device: ") + msg);
-  HIP_TRY(h, hipEventRecord(h->ev_motion, s));
-  return CTR_OK;
+  // the scratch is ctr_diffusion_device's, and so is the order of the calls
+  return run_stage("ctr_diffusion_ci_device", h, &ctr_handle::motion, d, hip_stream, ctr_diffusion_ci_launch);
 }
 
 int ctr_diffusion_ci_plan(const ctr_diffusion_ci* d, int32_t* rows_in_lds, int64_t* lds_bytes, int64_t* scratch_bytes,
                           int64_t* pairs_per_chunk) {
   const char* msg = "";
   ctr_ci_plan plan = {};
-  const int rc = ctr_diffusion_ci_launch(d, false, nullptr, nullptr, &plan, &msg);
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  const int rc = ctr_diffusion_ci_launch(d, &run, &msg, &plan);
   if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_diffusion_ci_plan: ") + msg);
   if (rows_in_lds) *rows_in_lds = plan.rows_in_lds;
   if (lds_bytes) *lds_bytes = plan.lds_bytes;
@@ -1230,12 +1172,9 @@ int ctr_refine_batch(ctr_handle* h, const ctr_problem* p, const ctr_batch* b) {
   const size_t sz_par = al(sizeof(double) * (size_t)N * np);
   const size_t sz_c = al(sizeof(double) * (size_t)C), sz_ci = al(sizeof(int32_t) * (size_t)C);
   const size_t total = sz_frames + sz_fi + sz_fo + (b->params_std ? 5 : 4) * sz_par + sz_c + 3 * sz_ci;
-  if (total > h->d_buf_bytes) {
-    if (h->d_buf) { (void)hipFree(h->d_buf); h->d_buf = nullptr; h->d_buf_bytes = 0; }
-    if (hipMalloc(&h->d_buf, total) != hipSuccess) return fail(h, CTR_ERR_NOMEM, "cannot allocate device memory for the batch");
-    h->d_buf_bytes = total;
-  }
-  char* q = (char*)h->d_buf;
+  rc = reserve(h, h->buf, total, "cannot allocate device memory for the batch");
+  if (rc) return rc;
+  char* q = (char*)h->buf.ptr;
   ctr_batch d = *b;
   auto take = [&](size_t n) { char* r = q; q += n; return r; };
   char* d_frames = take(sz_frames);

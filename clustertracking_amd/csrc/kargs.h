@@ -121,31 +121,39 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // feature location (tu_locate.hip, locate_kernels.h): checks the descriptor and queues the whole
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
-// feature characterisation (tu_characterize.hip, characterize_kernels.h): checks the descriptor
-// and, with launch_it, queues the kernel on `s`.  CTR_OK or an error code with a static message.
-int ctr_characterize_launch(const ctr_characterize* c, bool launch_it, hipStream_t s, const char** msg);
-// preprocessing (tu_preprocess.hip, preprocess_kernels.h): checks the descriptor and, with
-// launch_it, queues the kernels on `s`.  CTR_OK or an error code with a static message.
-int ctr_preprocess_launch(const ctr_preprocess* p, bool launch_it, hipStream_t s, const char** msg);
-// linking (tu_link.hip, link_kernels.h): checks the descriptor, reports the scratch it needs in
-// *scratch_bytes and, with a scratch block, queues the whole pipeline on `s`.
-int ctr_link_launch(const ctr_link* l, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg);
-// orientation and diffusion tensor (tu_motion.hip, motion_kernels.h): as the two above -- the
-// orientation has no scratch, the diffusion tensor reports the bytes of its partial sums.
-int ctr_orientation_launch(const ctr_orientation* o, bool launch_it, hipStream_t s, const char** msg);
-int ctr_diffusion_launch(const ctr_diffusion* d, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg);
-// bootstrap interval of the diffusion tensor (tu_motion_ci.hip, motion_ci_kernels.h): checks the
-// descriptor (the scalars alone with pointers == false), reports the launch decision in *plan and,
-// with a scratch block of plan->scratch_bytes, queues every chunk on `s`.
+// The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate)
+// share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
+// checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
+// STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
+// message in *msg.  Their callers are run_stage (ctrefine.hip), for every ctr_<stage>_device, and
+// the two ctr_*_plan queries.
+enum StageMode {
+  STAGE_CHECK_SCALARS,   // the scalars alone, no pointer is looked at (ctr_*_plan); a stage whose
+                         // launch decision needs no such form checks everything
+  STAGE_CHECK,           // the whole descriptor
+  STAGE_LAUNCH,          // ... and queue the kernels
+};
+struct StageRun {
+  StageMode mode;
+  hipStream_t stream;    // STAGE_LAUNCH
+  void* scratch;         // STAGE_LAUNCH: a block of scratch_bytes, for a stage that asked for any
+  size_t scratch_bytes;  // out; the caller starts it at 0, a stage without scratch leaves it; 0 from a
+                         // stage with scratch: nothing to launch
+};
+int ctr_characterize_launch(const ctr_characterize* c, StageRun* stage, const char** msg);   // characterize_kernels.h
+int ctr_preprocess_launch(const ctr_preprocess* p, StageRun* stage, const char** msg);       // preprocess_kernels.h
+int ctr_link_launch(const ctr_link* l, StageRun* stage, const char** msg);                   // link_kernels.h; scratch
+int ctr_orientation_launch(const ctr_orientation* o, StageRun* stage, const char** msg);     // motion_kernels.h
+int ctr_diffusion_launch(const ctr_diffusion* d, StageRun* stage, const char** msg);         // ... scratch: its partial sums
+// bootstrap interval of the diffusion tensor (motion_ci_kernels.h; scratch): the launch decision
+// goes to *plan (may be null), scratch_bytes there without the alignment slack of stage->scratch_bytes
 struct ctr_ci_plan {
   int rows_in_lds;
   long long lds_bytes, scratch_bytes, pairs_per_chunk;
 };
-int ctr_diffusion_ci_launch(const ctr_diffusion_ci* d, bool pointers, void* scratch, hipStream_t s, ctr_ci_plan* plan,
-                            const char** msg);
-// relocation candidates (tu_relocate.hip, relocate_kernels.h): checks the descriptor (the scalars
-// alone with pointers == false), reports the plan and, with launch_it, queues the kernel on `s`.
-int ctr_relocate_launch(const ctr_relocate* r, bool pointers, bool launch_it, hipStream_t s, long long* tile_pixels,
-                        long long* lds_bytes, const char** msg);
+int ctr_diffusion_ci_launch(const ctr_diffusion_ci* d, StageRun* stage, const char** msg, ctr_ci_plan* plan);
+// relocation candidates (relocate_kernels.h): the plan goes to *tile_pixels, *lds_bytes (may be null)
+int ctr_relocate_launch(const ctr_relocate* r, StageRun* stage, const char** msg, long long* tile_pixels,
+                        long long* lds_bytes);
 
 #endif  // CTREFINE_KARGS_H

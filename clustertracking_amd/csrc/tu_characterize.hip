@@ -37,7 +37,7 @@ void launch_nd(int ndim, const ChrArgs& a, long long vol, hipStream_t s) {
 
 }  // namespace
 
-int ctr_characterize_launch(const ctr_characterize* c, bool launch_it, hipStream_t s, const char** msg) {
+int ctr_characterize_launch(const ctr_characterize* c, StageRun* stage, const char** msg) {
   *msg = "";
   if (!c) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
   if (c->ndim != 2 && c->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
@@ -62,7 +62,8 @@ int ctr_characterize_launch(const ctr_characterize* c, bool launch_it, hipStream
   if (c->n_frames > 0x7fffffffLL || c->n_features > (1LL << 31) * (CHR_THREADS / 64) - 1) { *msg = "too many frames or features for one call"; return CTR_ERR_INVALID; }
   if (c->n_features > 0 && (c->n_frames < 1 || !c->frames || !c->frame_offset)) { *msg = "features without frames or frame_offset"; return CTR_ERR_INVALID; }
   if (c->n_features > 0 && (!c->mass || !c->signal || !c->size)) { *msg = "null output"; return CTR_ERR_INVALID; }
-  if (!launch_it || c->n_features == 0) return CTR_OK;
+  if (stage->mode != STAGE_LAUNCH || c->n_features == 0) return CTR_OK;
+  const hipStream_t s = stage->stream;
   a.frames = c->frames;
   a.frame_elems = E;
   a.n_frames = (int)c->n_frames;

@@ -67,7 +67,7 @@ void run(const LinkArgs& a, hipStream_t s) {
 
 }  // namespace
 
-int ctr_link_launch(const ctr_link* l, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg) {
+int ctr_link_launch(const ctr_link* l, StageRun* stage, const char** msg) {
   *msg = "";
   if (!l) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
   if (l->ndim != 2 && l->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
@@ -79,13 +79,14 @@ int ctr_link_launch(const ctr_link* l, void* scratch, size_t* scratch_bytes, hip
   if (l->n_features > 0 && (l->n_levels < 1 || !l->pos || !l->frame_offset)) { *msg = "features without levels, pos or frame_offset"; return CTR_ERR_INVALID; }
   if (l->n_features > 0 && (!l->particle || !l->n_tracks || !l->status)) { *msg = "null output"; return CTR_ERR_INVALID; }
   LinkArgs a = {};
-  if (scratch_bytes) *scratch_bytes = layout(a, nullptr, l->n_features, l->ndim, l->n_levels);
-  if (!scratch) return CTR_OK;
+  stage->scratch_bytes = layout(a, nullptr, l->n_features, l->ndim, l->n_levels);
+  if (stage->mode != STAGE_LAUNCH) return CTR_OK;
+  const hipStream_t s = stage->stream;
   if (l->status && hipMemsetAsync(l->status, 0, 4 * sizeof(int32_t), s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
   if (l->n_tracks && hipMemsetAsync(l->n_tracks, 0, sizeof(int64_t), s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
   if (l->n_features == 0) return CTR_OK;
-  const size_t zeroed = layout(a, (char*)scratch, l->n_features, l->ndim, l->n_levels);
-  if (hipMemsetAsync(scratch, 0, zeroed, s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
+  const size_t zeroed = layout(a, (char*)stage->scratch, l->n_features, l->ndim, l->n_levels);
+  if (hipMemsetAsync(stage->scratch, 0, zeroed, s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
   a.ndim = l->ndim;
   a.memory = l->memory < l->n_levels ? (int)l->memory : (int)l->n_levels;   // a longer memory reaches no further
   a.n_levels = (int)l->n_levels;

@@ -38,7 +38,7 @@ void launch_orientation(int cs, const OriArgs& a, unsigned grid, hipStream_t s) 
 
 }  // namespace
 
-int ctr_orientation_launch(const ctr_orientation* o, bool launch_it, hipStream_t s, const char** msg) {
+int ctr_orientation_launch(const ctr_orientation* o, StageRun* stage, const char** msg) {
   *msg = "";
   if (!o) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
   if (o->ndim != 2 && o->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
@@ -57,7 +57,8 @@ int ctr_orientation_launch(const ctr_orientation* o, bool launch_it, hipStream_t
   }
   const long long n = o->n_tracks * o->n_frames;
   if (n > 0 && (!o->pos || !o->com || !o->bases)) { *msg = "null input or output"; return CTR_ERR_INVALID; }
-  if (!launch_it || n == 0) return CTR_OK;
+  if (stage->mode != STAGE_LAUNCH || n == 0) return CTR_OK;
+  const hipStream_t s = stage->stream;
   OriArgs a;
   a.T = o->n_tracks;
   a.F = o->n_frames;
@@ -75,7 +76,7 @@ int ctr_orientation_launch(const ctr_orientation* o, bool launch_it, hipStream_t
   return CTR_OK;
 }
 
-int ctr_diffusion_launch(const ctr_diffusion* d, void* scratch, size_t* scratch_bytes, hipStream_t s, const char** msg) {
+int ctr_diffusion_launch(const ctr_diffusion* d, StageRun* stage, const char** msg) {
   *msg = "";
   if (!d) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
   if (d->ndim != 2 && d->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
@@ -95,8 +96,9 @@ int ctr_diffusion_launch(const ctr_diffusion* d, void* scratch, size_t* scratch_
   if (groups > 0 && d->n_lags > (1LL << 40) / MOT_NSUM / groups) { *msg = "partial sums above 8 TiB"; return CTR_ERR_INVALID; }
   if (outs > 0 && (!d->lags || !d->tensor || !d->n_samples)) { *msg = "null lags or output"; return CTR_ERR_INVALID; }
   if (outs > 0 && groups > 0 && (!d->positions || !d->bases)) { *msg = "null input"; return CTR_ERR_INVALID; }
-  if (scratch_bytes) *scratch_bytes = sizeof(double) * (size_t)(groups * d->n_lags * MOT_NSUM) + 256;
-  if (!scratch || outs == 0) return CTR_OK;
+  stage->scratch_bytes = sizeof(double) * (size_t)(groups * d->n_lags * MOT_NSUM) + 256;
+  if (stage->mode != STAGE_LAUNCH || outs == 0) return CTR_OK;
+  const hipStream_t s = stage->stream;
   DifArgs a;
   a.ndim = d->ndim;
   a.n_perm = d->n_perm;
@@ -109,7 +111,7 @@ int ctr_diffusion_launch(const ctr_diffusion* d, void* scratch, size_t* scratch_
   a.lags = (const long long*)d->lags;
   a.positions = d->positions;
   a.bases = d->bases;
-  a.partial = (double*)scratch;
+  a.partial = (double*)stage->scratch;
   a.tensor = d->tensor;
   a.n_samples = (long long*)d->n_samples;
   if (groups > 0)

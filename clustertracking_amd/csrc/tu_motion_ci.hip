@@ -37,8 +37,7 @@ void launch_resample(bool lds, const CiArgs& a, unsigned grid, size_t lds_bytes,
 
 }  // namespace
 
-int ctr_diffusion_ci_launch(const ctr_diffusion_ci* d, bool pointers, void* scratch, hipStream_t s, ctr_ci_plan* plan,
-                            const char** msg) {
+int ctr_diffusion_ci_launch(const ctr_diffusion_ci* d, StageRun* stage, const char** msg, ctr_ci_plan* plan) {
   *msg = "";
   if (!d) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
   if (d->ndim != 2 && d->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
@@ -77,10 +76,12 @@ int ctr_diffusion_ci_launch(const ctr_diffusion_ci* d, bool pointers, void* scra
     return CTR_ERR_UNSUPPORTED;
   }
   if (plan) *plan = p.out;
-  if (!pointers) return CTR_OK;
+  stage->scratch_bytes = p.out.pairs_per_chunk ? (size_t)p.out.scratch_bytes + 256 : 0;   // (0: nothing to resample)
+  if (stage->mode == STAGE_CHECK_SCALARS) return CTR_OK;
   if (p.n_pairs > 0 && (!d->lags || !d->interval)) { *msg = "null lags or interval"; return CTR_ERR_INVALID; }
   if (p.n_pairs > 0 && p.n_max > 0 && d->n_tracks > 0 && (!d->positions || !d->bases)) { *msg = "null input"; return CTR_ERR_INVALID; }
-  if (!scratch || p.n_pairs == 0) return CTR_OK;
+  if (stage->mode != STAGE_LAUNCH || p.n_pairs == 0) return CTR_OK;
+  const hipStream_t s = stage->stream;
 
   CiArgs a;
   a.ndim = d->ndim;
@@ -110,7 +111,7 @@ int ctr_diffusion_ci_launch(const ctr_diffusion_ci* d, bool pointers, void* scra
   a.positions = d->positions;
   a.bases = d->bases;
   const long long c = p.out.pairs_per_chunk;
-  a.rows = (double*)scratch;
+  a.rows = (double*)stage->scratch;
   a.stats = a.rows + c * p.n_max * p.D;
   a.n = (long long*)(a.stats + c * p.NE * a.B);
   a.interval = d->interval;

@@ -112,7 +112,7 @@ int run(const ctr_preprocess* p, const PreGeom& g, bool z_gauss, bool z_box, int
 
 }  // namespace
 
-int ctr_preprocess_launch(const ctr_preprocess* p, bool launch_it, hipStream_t s, const char** msg) {
+int ctr_preprocess_launch(const ctr_preprocess* p, StageRun* stage, const char** msg) {
   *msg = "";
   if (!p) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
   if (p->ndim != 2 && p->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
@@ -170,7 +170,8 @@ int ctr_preprocess_launch(const ctr_preprocess* p, bool launch_it, hipStream_t s
     if ((g.ny + g.ty - 1) / g.ty > 65535) { *msg = "too many rows per frame for one call"; return CTR_ERR_UNSUPPORTED; }
     if ((long long)((g.nx + PRE_TX - 1) / PRE_TX) * p->n_frames * g.nz > 0x7fffffffLL) { *msg = "too many tiles for one call"; return CTR_ERR_UNSUPPORTED; }
   }
-  if (!launch_it || p->n_frames == 0) return CTR_OK;
+  if (stage->mode != STAGE_LAUNCH || p->n_frames == 0) return CTR_OK;
+  const hipStream_t s = stage->stream;
   // by byte count (3 B against 18 B per uint8 pixel through HBM); see the time paragraph of DESIGN.md 7b
   const int strategy = p->strategy == CTR_PRE_AUTO ? CTR_PRE_TWICE : p->strategy;
   switch (p->frame_dtype) {

@@ -30,8 +30,8 @@ void launch_nd(int ndim, const RlArgs& a, size_t lds, hipStream_t s) {
 // query whose box has at most that many pixels in one slab, walks a larger one in slabs and reads
 // one whose thinnest slab does not fit from global memory (relocate_kernels.h);
 // tests/_relocate.py restates all three.
-int ctr_relocate_launch(const ctr_relocate* r, bool pointers, bool launch_it, hipStream_t s, long long* tile_pixels,
-                        long long* lds_bytes, const char** msg) {
+int ctr_relocate_launch(const ctr_relocate* r, StageRun* stage, const char** msg, long long* tile_pixels,
+                        long long* lds_bytes) {
   *msg = "";
   if (!r) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
   if (r->ndim != 2 && r->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
@@ -89,7 +89,7 @@ int ctr_relocate_launch(const ctr_relocate* r, bool pointers, bool launch_it, hi
   const long long lds = (tile * es + 15) & ~15LL;
   if (tile_pixels) *tile_pixels = tile;
   if (lds_bytes) *lds_bytes = lds;
-  if (!pointers) return CTR_OK;
+  if (stage->mode == STAGE_CHECK_SCALARS) return CTR_OK;
   if (r->n_queries > 0x7fffffffLL) { *msg = "too many queries for one call"; return CTR_ERR_INVALID; }
   if (r->n_queries > 0) {
     if (r->n_frames < 1 || !r->frames || !r->threshold || !r->known_offset) { *msg = "queries without frames, threshold or known_offset"; return CTR_ERR_INVALID; }
@@ -97,7 +97,8 @@ int ctr_relocate_launch(const ctr_relocate* r, bool pointers, bool launch_it, hi
     if (!r->query_frame || !r->source_offset) { *msg = "null query_frame or source_offset"; return CTR_ERR_INVALID; }
     if (!r->n_found || !r->cand_pos || !r->mass || !r->signal || !r->size || !r->status) { *msg = "null output"; return CTR_ERR_INVALID; }
   }
-  if (!launch_it || r->n_queries == 0) return CTR_OK;
+  if (stage->mode != STAGE_LAUNCH || r->n_queries == 0) return CTR_OK;
+  const hipStream_t s = stage->stream;
   a.frames = r->frames;
   a.frame_elems = E;
   a.n_frames = r->n_frames;

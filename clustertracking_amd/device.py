@@ -89,19 +89,10 @@ class DeviceBatch(object):
         queued after it sees the results.  ``stream``: a raw hipStream_t handle to use
         instead (non-zero; 0 would mean the engine's own stream, include/ctrefine.h, which
         torch knows nothing about)."""
-        torch = self.torch
         if stream:
             self.engine.refine_batch_device(self.plan, self.struct, stream)
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if cur.cuda_stream != 0:
-            self.engine.refine_batch_device(self.plan, self.struct, cur.cuda_stream)
-            return
-        # torch is on the legacy default stream (handle 0): the engine runs on its own stream,
-        # ordered with the default stream by events on the device
-        self.engine.engine_wait_stream(0)
-        self.engine.refine_batch_device(self.plan, self.struct, 0)
-        self.engine.stream_wait_engine(0)
+        else:
+            self.engine.on_current_stream(self.engine.refine_batch_device, self.plan, self.struct, dev=self.device)
 
     def download(self):
         """Copy the outputs back into the HostBatch arrays (synchronises)."""

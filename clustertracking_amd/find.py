@@ -283,13 +283,7 @@ def locate_arrays(frames, separation, percentile=64, margin=None, precise=True, 
             pos = torch.empty((max(int(capacity), 1), ndim), dtype=torch.int32, device=dev)
             loc.capacity = int(capacity)
             loc.pos_out = pos.data_ptr()
-            cur = torch.cuda.current_stream(dev)
-            if cur.cuda_stream:
-                eng.locate_maxima_device(loc, cur.cuda_stream)
-            else:   # legacy default stream: the engine's stream, ordered by events on the device
-                eng.engine_wait_stream(0)
-                eng.locate_maxima_device(loc, 0)
-                eng.stream_wait_engine(0)
+            eng.on_current_stream(eng.locate_maxima_device, loc, dev=dev)
             torch.cuda.synchronize(dev)
             n = int(total.item())
             if n <= capacity:
@@ -406,13 +400,7 @@ def _characterize_device(frames, pos, frame_offset, radius, isotropic, scale_fac
         else:
             ch.pos = pos_t.data_ptr()
         ch.mass, ch.signal, ch.size = mass.data_ptr(), signal.data_ptr(), size.data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            eng.characterize_device(ch, cur.cuda_stream)
-        else:   # legacy default stream: the engine's stream, ordered by events on the device
-            eng.engine_wait_stream(0)
-            eng.characterize_device(ch, 0)
-            eng.stream_wait_engine(0)
+        eng.on_current_stream(eng.characterize_device, ch, dev=dev)
         torch.cuda.synchronize(dev)   # the inputs uploaded here live until the kernel has read them
     return mass, signal, size
 

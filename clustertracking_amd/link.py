@@ -131,13 +131,7 @@ def link_arrays(pos, frame_offset, search_range, memory=0, device=0, _on_device=
             d.search_range[a] = float(sr[a])
         d.pos, d.frame_offset = pos_t.data_ptr(), off_t.data_ptr()
         d.particle, d.n_tracks, d.status = particle.data_ptr(), n_tracks.data_ptr(), status.data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            eng.link_device(d, cur.cuda_stream)
-        else:   # legacy default stream: the engine's stream, ordered by events on the device
-            eng.engine_wait_stream(0)
-            eng.link_device(d, 0)
-            eng.stream_wait_engine(0)
+        eng.on_current_stream(eng.link_device, d, dev=dev)
         code, level, size, _ = (int(v) for v in status.cpu())   # the one synchronisation of the call
     if code == _abi.LINK_OVERSIZE:
         raise SubnetOversizeException("Subnetwork contains %d points (level %d)" % (size, level))

@@ -78,18 +78,6 @@ def _to_device(x, dev, dtype, what):
     return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
 
-def _queue(eng, dev, call, desc):
-    """on torch's current stream; the legacy default stream is ordered with the engine's by events"""
-    import torch
-    cur = torch.cuda.current_stream(dev)
-    if cur.cuda_stream:
-        call(desc, cur.cuda_stream)
-    else:
-        eng.engine_wait_stream(0)
-        call(desc, 0)
-        eng.stream_wait_engine(0)
-
-
 def orientation_arrays(pos, cluster_size, ndim, mpp=1., sizes=None, angles=None, device=0):
     """Centre of mass and bases of tracked clusters (``ctr_orientation_device``).
 
@@ -138,7 +126,7 @@ def orientation_arrays(pos, cluster_size, ndim, mpp=1., sizes=None, angles=None,
                 d.weights[k] = float(weights[k])
             d.pos, d.com, d.bases = pos_t.data_ptr(), com.data_ptr(), bases.data_ptr()
             d.angles = ang_t.data_ptr() if needs_angles else None
-            _queue(eng, dev, eng.orientation_device, d)
+            eng.on_current_stream(eng.orientation_device, d, dev=dev)
         if as_tensor:
             return com, bases
         return com.cpu().numpy(), bases.cpu().numpy()
@@ -259,7 +247,7 @@ def diffusion_tensor(positions, orientations, lagtime=1, fps=1., ndim=3, pool_tr
             d.ndim, d.n_perm, d.n_tracks, d.n_frames, d.n_lags, d.fps = ndim, n_perm, n_tracks, n_frames, len(lags), float(fps)
             d.lags, d.positions, d.bases = lag_t.data_ptr(), pos_t.data_ptr() or None, ori_t.data_ptr() or None
             d.tensor, d.n_samples = tensor.data_ptr(), counts.data_ptr()
-            _queue(eng, dev, eng.diffusion_device, d)
+            eng.on_current_stream(eng.diffusion_device, d, dev=dev)
         if tracked and pool_tracks:
             # mean over the pooled rows = count-weighted mean of the per-track means
             w = counts.to(torch.float64)[:, :, None, None]

@@ -19,7 +19,7 @@ import statistics
 import numpy as np
 
 from . import _abi, _lib
-from .motion import _is_tensor, _lag_list, _queue, _to_device
+from .motion import _is_tensor, _lag_list, _to_device
 
 _MASK64 = (1 << 64) - 1
 _GOLDEN = 0x9E3779B97F4A7C15
@@ -156,7 +156,7 @@ def diffusion_tensor_ci(positions, orientations, lagtime=1, fps=1., ndim=3, alph
                 d.alphas[q], d.z_alpha[q] = a, normal.inv_cdf(a)
             d.interval, d.tensor, d.n_rows = interval.data_ptr(), tensor.data_ptr(), counts.data_ptr()
             d.z0, d.accel, d.ranks = z0.data_ptr(), accel.data_ptr(), ranks.data_ptr()
-            _queue(eng, dev, eng.diffusion_ci_device, d)
+            eng.on_current_stream(eng.diffusion_ci_device, d, dev=dev)
         out = [interval, ranks, tensor, z0, accel, counts]
         if not tracked:
             out = [x.reshape(x.shape[1:]) for x in out]

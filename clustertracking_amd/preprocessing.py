@@ -128,13 +128,7 @@ def _run(frames, mode, lshort, llong, threshold, device, dtype, strategy=_abi.PR
         d.frames = t.data_ptr()
         d.out = out.data_ptr()
         d.scale_factor = scale.data_ptr() if scaled else None
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            eng.preprocess_device(d, cur.cuda_stream)
-        else:   # legacy default stream: the engine's stream, ordered by events on the device
-            eng.engine_wait_stream(0)
-            eng.preprocess_device(d, 0)
-            eng.stream_wait_engine(0)
+        eng.on_current_stream(eng.preprocess_device, d, dev=dev)
         # no synchronisation, as for ctr_locate_maxima_device: the call is ordered on the caller's
         # stream, where whatever reads `out` (a copy to the host, the maxima search) is queued too
     return out, out_type, (scale[:n_frames] if scaled else None), t, pix

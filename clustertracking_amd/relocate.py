@@ -131,13 +131,7 @@ def relocate_arrays(frames, threshold, known, known_offset, sources, source_offs
         r.source_pos = src_t.data_ptr()
         r.n_found, r.cand_pos, r.status = n_found.data_ptr(), pos.data_ptr(), status.data_ptr()
         r.mass, r.signal, r.size = mass.data_ptr(), signal.data_ptr(), size.data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            eng.relocate_device(r, cur.cuda_stream)
-        else:   # legacy default stream: the engine's stream, ordered by events on the device
-            eng.engine_wait_stream(0)
-            eng.relocate_device(r, 0)
-            eng.stream_wait_engine(0)
+        eng.on_current_stream(eng.relocate_device, r, dev=dev)
         if _on_device:      # the caller synchronises; the inputs must outlive the kernel
             return (n_found, pos, mass, signal, size, status), (t, thr_t, known_t, koff_t, src_t, soff_t, qf_t)
         torch.cuda.synchronize(dev)   # the inputs uploaded here live until the kernel has read them
