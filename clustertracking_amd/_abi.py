@@ -181,6 +181,29 @@ class Relocate(C.Structure):
     ]
 
 
+FIND_LINK_OK, FIND_LINK_OVERSIZE, FIND_LINK_CAPACITY = 0, 1, 2   # ctr_find_link.status[0]
+FIND_LINK_RELOCATE, FIND_LINK_QUERIES, FIND_LINK_ROWS = 3, 4, 5
+
+
+class FindLink(C.Structure):
+    """``ctr_find_link`` (include/ctrefine.h): find and link with relocation on the device."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('frame_dtype', C.c_int32), ('n_frames', C.c_int64),
+        ('shape', C.c_int64 * MAX_NDIM), ('radius', C.c_int64 * MAX_NDIM),
+        ('separation', C.c_double * MAX_NDIM), ('search_range', C.c_double * MAX_NDIM),
+        ('isotropic', C.c_int32), ('memory', C.c_int32),
+        ('max_queries', C.c_int32), ('max_relocated', C.c_int32),
+        ('minmass', C.c_double), ('scale_factor', C.c_double),
+        ('frames', C.c_void_p), ('threshold', C.c_void_p),
+        ('n_located', C.c_int64), ('pos', C.c_void_p), ('frame_offset', C.c_void_p),
+        ('mass', C.c_void_p), ('signal', C.c_void_p), ('size', C.c_void_p),
+        ('capacity', C.c_int64), ('pos_out', C.c_void_p), ('frame_offset_out', C.c_void_p),
+        ('particle', C.c_void_p), ('mass_out', C.c_void_p), ('signal_out', C.c_void_p),
+        ('size_out', C.c_void_p), ('relocated', C.c_void_p), ('n_tracks', C.c_void_p),
+        ('coupled', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
 class Orientation(C.Structure):
     """``ctr_orientation`` (include/ctrefine.h): orientation of tracked clusters on the device."""
     _fields_ = [

@@ -49,6 +49,7 @@ SIGNATURES = {
     'ctr_diffusion_device': _stage(_abi.Diffusion),
     'ctr_relocate_device': _stage(_abi.Relocate),
     'ctr_relocate_plan': (C.c_int, [_P(_abi.Relocate), _P(C.c_int64), _P(C.c_int64)]),
+    'ctr_find_link_device': _stage(_abi.FindLink),
     'ctr_diffusion_ci_device': _stage(_abi.DiffusionCI),
     'ctr_diffusion_ci_plan': (C.c_int, [_P(_abi.DiffusionCI), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                         _P(C.c_int64)]),
@@ -332,7 +333,8 @@ for _name, _symbol, _too_large in (
         ('orientation_device', 'ctr_orientation_device', False),
         ('diffusion_device', 'ctr_diffusion_device', False),
         ('diffusion_ci_device', 'ctr_diffusion_ci_device', False),
-        ('relocate_device', 'ctr_relocate_device', False)):
+        ('relocate_device', 'ctr_relocate_device', False),
+        ('find_link_device', 'ctr_find_link_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 
 

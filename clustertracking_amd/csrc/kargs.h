@@ -121,7 +121,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // feature location (tu_locate.hip, locate_kernels.h): checks the descriptor and queues the whole
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
-// The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate)
+// The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -155,5 +155,7 @@ int ctr_diffusion_ci_launch(const ctr_diffusion_ci* d, StageRun* stage, const ch
 // relocation candidates (relocate_kernels.h): the plan goes to *tile_pixels, *lds_bytes (may be null)
 int ctr_relocate_launch(const ctr_relocate* r, StageRun* stage, const char** msg, long long* tile_pixels,
                         long long* lds_bytes);
+// find and link with relocation (findlink_kernels.h; scratch): queues ctr_relocate_launch per level
+int ctr_find_link_launch(const ctr_find_link* f, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

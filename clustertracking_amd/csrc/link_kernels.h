@@ -1,5 +1,7 @@
 // link_kernels.h -- frame-to-frame linking on the device (ctr_link_device).
-// Included by tu_link.hip inside its anonymous namespace, after device_common.h.
+// Included by tu_link.hip inside its anonymous namespace, after device_common.h, and by
+// tu_findlink.hip, whose loop (findlink_kernels.h) runs these kernels and the two device functions of
+// link_solve_kernel (lnk_components, lnk_hungarian) on a table that grows by the relocated rows.
 //
 // The rule (reference Linker, find_link.py:579-733, as clustertracking_amd/link.py restates it).
 // Per level t >= 1, destinations = the rows of level t, sources = the rows of the levels
@@ -168,6 +170,119 @@ __global__ __launch_bounds__(LNK_THREADS) void link_cand_kernel(LinkArgs a, int 
   }
 }
 
+// The sub-networks of one level: destinations [d0, d1), source window [w0, w1).  Every thread of the
+// workgroup calls it; s_changed: one word of LDS.  After it lab_d / lab_s hold the label of the
+// component (its smallest destination row; LNK_NONE: a source no destination lists) and cnt_s the
+// destinations that list a source; the last thing it does is a barrier.
+__device__ __forceinline__ void lnk_components(const LinkArgs& a, long long d0, long long d1, long long w0,
+                                               long long w1, int tid, int* s_changed) {
+  // ---- initial state of this level's words
+  for (long long s = w0 + tid; s < w1; s += LNK_THREADS) {
+    lnk_st(&a.lab_s[s], LNK_NONE);
+    lnk_st(&a.cnt_s[s], 0);
+  }
+  for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
+    lnk_st(&a.lab_d[i], (int)i);
+    lnk_st(&a.head_d[i], -1);
+    lnk_st(&a.head_s[i], -1);
+  }
+  __syncthreads();
+  for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
+    const int nc = a.ncand[i];
+    for (int k = 0; k < nc; ++k) atomicAdd(&a.cnt_s[a.cand_row[i * LNK_MAXC + k]], 1);
+  }
+  __syncthreads();
+
+  // ---- components: every edge pulls both ends to the smaller label until a pass changes nothing
+  for (;;) {
+    if (tid == 0) *s_changed = 0;
+    __syncthreads();
+    bool changed = false;
+    for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
+      const int nc = a.ncand[i];
+      if (nc == 0) continue;
+      const int mine = lnk_ld(&a.lab_d[i]);
+      int m = mine;
+      for (int k = 0; k < nc; ++k) {
+        const int l = lnk_ld(&a.lab_s[a.cand_row[i * LNK_MAXC + k]]);
+        m = l < m ? l : m;
+      }
+      for (int k = 0; k < nc; ++k)
+        if (atomicMin(&a.lab_s[a.cand_row[i * LNK_MAXC + k]], m) > m) changed = true;
+      if (m < mine) { lnk_st(&a.lab_d[i], m); changed = true; }
+    }
+    if (changed) *s_changed = 1;
+    __syncthreads();
+    const int again = *s_changed;
+    __syncthreads();
+    if (!again) break;
+  }
+}
+
+// The assignment of one sub-network by one wavefront: shortest augmenting paths (Hungarian), one lane
+// per column.  cost: [ns][LNK_MAX_DST] in LDS, columns 1..nd the destinations, nd+1..nd+ns one "no
+// link" column of cost 0 per source; u [ns + 1], p and way [nd + ns + 1] zeroed by the caller.
+// After it p[c] is the row (1-based source) of column c, 0: none.
+__device__ __forceinline__ void lnk_hungarian(const double* cost, double* u, unsigned char* p, unsigned char* way,
+                                              int ns, int nd, int lane) {
+  const int m = nd + ns;
+  const int c0 = lane + 1, c1 = lane + 65;   // this lane's columns (c1 is always a "no link" one)
+  double v0 = 0., v1 = 0.;
+  for (int i = 1; i <= ns; ++i) {
+    if (lane == 0) p[0] = (unsigned char)i;
+    lnk_wave_sync();
+    int j0 = 0;
+    double mv0 = INFINITY, mv1 = INFINITY;
+    bool us0 = false, us1 = false;
+    for (;;) {
+      if (j0 == c0) us0 = true;
+      if (j0 == c1) us1 = true;
+      const int i0 = p[j0];
+      const double ui0 = u[i0];
+      double delta = INFINITY;
+      int j1 = LNK_NONE;
+      if (c0 <= m && !us0) {
+        const double cst = c0 <= nd ? cost[(i0 - 1) * LNK_MAX_DST + lane] : 0.;
+        const double cur = cst - ui0 - v0;
+        if (cur < mv0) { mv0 = cur; way[c0] = (unsigned char)j0; }
+        delta = mv0; j1 = c0;
+      }
+      if (c1 <= m && !us1) {
+        const double cur = 0. - ui0 - v1;
+        if (cur < mv1) { mv1 = cur; way[c1] = (unsigned char)j0; }
+        if (mv1 < delta) { delta = mv1; j1 = c1; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(delta, o);
+        const int oj = __shfl_xor(j1, o);
+        if (od < delta || (od == delta && oj < j1)) { delta = od; j1 = oj; }
+      }
+      lnk_wave_sync();   // ui0 is read by every lane before a row's u moves
+      if (lane == 0) u[p[0]] += delta;
+      if (c0 <= m) {
+        if (us0) { u[p[c0]] += delta; v0 -= delta; }
+        else mv0 -= delta;
+      }
+      if (c1 <= m) {
+        if (us1) { u[p[c1]] += delta; v1 -= delta; }
+        else mv1 -= delta;
+      }
+      j0 = j1;
+      lnk_wave_sync();
+      if (p[j0] == 0) break;
+    }
+    if (lane == 0) {
+      do {
+        const int j1 = way[j0];
+        p[j0] = p[j1];
+        j0 = j1;
+      } while (j0);
+    }
+    lnk_wave_sync();
+  }
+}
+
 // One workgroup per level t = t_begin + blockIdx.x.
 __global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int t_begin) {
   __shared__ double s_cost[LNK_WAVES][LNK_MAX_SRC * LNK_MAX_DST];
@@ -185,48 +300,8 @@ __global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int
   const long long w0 = a.off[tw > 0 ? tw : 0], w1 = d0;
   if (d0 == d1 || w0 == w1) return;   // no destination or no source: nothing links (uniform)
 
-  // ---- initial state of this level's words
-  for (long long s = w0 + tid; s < w1; s += LNK_THREADS) {
-    lnk_st(&a.lab_s[s], LNK_NONE);
-    lnk_st(&a.cnt_s[s], 0);
-  }
-  for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
-    lnk_st(&a.lab_d[i], (int)i);
-    lnk_st(&a.head_d[i], -1);
-    lnk_st(&a.head_s[i], -1);
-  }
   if (tid == 0) s_nroots = 0;
-  __syncthreads();
-  for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
-    const int nc = a.ncand[i];
-    for (int k = 0; k < nc; ++k) atomicAdd(&a.cnt_s[a.cand_row[i * LNK_MAXC + k]], 1);
-  }
-  __syncthreads();
-
-  // ---- components: every edge pulls both ends to the smaller label until a pass changes nothing
-  for (;;) {
-    if (tid == 0) s_changed = 0;
-    __syncthreads();
-    bool changed = false;
-    for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
-      const int nc = a.ncand[i];
-      if (nc == 0) continue;
-      const int mine = lnk_ld(&a.lab_d[i]);
-      int m = mine;
-      for (int k = 0; k < nc; ++k) {
-        const int l = lnk_ld(&a.lab_s[a.cand_row[i * LNK_MAXC + k]]);
-        m = l < m ? l : m;
-      }
-      for (int k = 0; k < nc; ++k)
-        if (atomicMin(&a.lab_s[a.cand_row[i * LNK_MAXC + k]], m) > m) changed = true;
-      if (m < mine) { lnk_st(&a.lab_d[i], m); changed = true; }
-    }
-    if (changed) s_changed = 1;
-    __syncthreads();
-    const int again = s_changed;
-    __syncthreads();
-    if (!again) break;
-  }
+  lnk_components(a, d0, d1, w0, w1, tid, &s_changed);
 
   // ---- 1 x 1 sub-networks link here; the others are chained to their root
   for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
@@ -297,61 +372,8 @@ __global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int
     }
     lnk_wave_sync();
 
-    const int c0 = lane + 1, c1 = lane + 65;   // this lane's columns (c1 is always a "no link" one)
-    double v0 = 0., v1 = 0.;
-    for (int i = 1; i <= ns; ++i) {
-      if (lane == 0) s_p[w][0] = (unsigned char)i;
-      lnk_wave_sync();
-      int j0 = 0;
-      double mv0 = INFINITY, mv1 = INFINITY;
-      bool us0 = false, us1 = false;
-      for (;;) {
-        if (j0 == c0) us0 = true;
-        if (j0 == c1) us1 = true;
-        const int i0 = s_p[w][j0];
-        const double ui0 = s_u[w][i0];
-        double delta = INFINITY;
-        int j1 = LNK_NONE;
-        if (c0 <= m && !us0) {
-          const double cst = c0 <= nd ? s_cost[w][(i0 - 1) * LNK_MAX_DST + lane] : 0.;
-          const double cur = cst - ui0 - v0;
-          if (cur < mv0) { mv0 = cur; s_way[w][c0] = (unsigned char)j0; }
-          delta = mv0; j1 = c0;
-        }
-        if (c1 <= m && !us1) {
-          const double cur = 0. - ui0 - v1;
-          if (cur < mv1) { mv1 = cur; s_way[w][c1] = (unsigned char)j0; }
-          if (mv1 < delta) { delta = mv1; j1 = c1; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const double od = __shfl_xor(delta, o);
-          const int oj = __shfl_xor(j1, o);
-          if (od < delta || (od == delta && oj < j1)) { delta = od; j1 = oj; }
-        }
-        lnk_wave_sync();   // ui0 is read by every lane before a row's u moves
-        if (lane == 0) s_u[w][s_p[w][0]] += delta;
-        if (c0 <= m) {
-          if (us0) { s_u[w][s_p[w][c0]] += delta; v0 -= delta; }
-          else mv0 -= delta;
-        }
-        if (c1 <= m) {
-          if (us1) { s_u[w][s_p[w][c1]] += delta; v1 -= delta; }
-          else mv1 -= delta;
-        }
-        j0 = j1;
-        lnk_wave_sync();
-        if (s_p[w][j0] == 0) break;
-      }
-      if (lane == 0) {
-        do {
-          const int j1 = s_way[w][j0];
-          s_p[w][j0] = s_p[w][j1];
-          j0 = j1;
-        } while (j0);
-      }
-      lnk_wave_sync();
-    }
+    lnk_hungarian(s_cost[w], s_u[w], s_p[w], s_way[w], ns, nd, lane);
+    const int c0 = lane + 1;
     if (lane < nd) {
       const int r = s_p[w][c0];
       if (r && s_cost[w][(r - 1) * LNK_MAX_DST + lane] < 0.5 * LNK_BIG) {
@@ -436,6 +458,35 @@ __global__ __launch_bounds__(LNK_THREADS) void link_ids_kernel(LinkArgs a) {
     const int root = a.anc[i];
     a.particle[i] = a.base[lnk_level_of(a.off, a.n_levels, root)] + a.rank[root];
   }
+}
+
+// ---- host: the scratch of a call
+constexpr size_t LNK_ALIGN = 256;
+
+inline size_t lnk_carve(size_t& at, size_t bytes) {
+  const size_t here = at;
+  at += (bytes + LNK_ALIGN - 1) / LNK_ALIGN * LNK_ALIGN;
+  return here;
+}
+
+// lays the scratch arrays of LinkArgs out from `base` (nullptr: only the size is wanted; else the
+// bytes at the front that every call zeroes)
+inline size_t lnk_layout(LinkArgs& a, char* base, long long n, int ndim, long long n_levels) {
+  size_t at = 0;
+  const size_t N = (size_t)(n > 0 ? n : 1), L = (size_t)n_levels + 1;
+  // the words that every call zeroes come first, in one block
+  a.used = (int*)(base + lnk_carve(at, N * sizeof(int)));
+  a.nbirth = (int*)(base + lnk_carve(at, L * sizeof(int)));
+  const size_t zeroed = at;
+  a.spos = (double*)(base + lnk_carve(at, N * ndim * sizeof(double)));
+  a.cand_d2 = (double*)(base + lnk_carve(at, N * LNK_MAXC * sizeof(double)));
+  a.cand_row = (int*)(base + lnk_carve(at, N * LNK_MAXC * sizeof(int)));
+  int** per_row[] = {&a.ncand, &a.link, &a.lab_d, &a.lab_s, &a.cnt_s, &a.head_d, &a.head_s,
+                     &a.next_d, &a.next_s, &a.roots, &a.rank, &a.anc};
+  for (int** p : per_row) *p = (int*)(base + lnk_carve(at, N * sizeof(int)));
+  a.base = (long long*)(base + lnk_carve(at, L * sizeof(long long)));
+  if (!base) return at;
+  return zeroed;
 }
 
 #endif  // CTREFINE_LINK_KERNELS_H

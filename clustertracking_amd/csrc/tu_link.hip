@@ -12,33 +12,6 @@ namespace {
 #include "device_common.h"
 #include "link_kernels.h"
 
-constexpr size_t LNK_ALIGN = 256;
-
-size_t carve(size_t& at, size_t bytes) {
-  const size_t here = at;
-  at += (bytes + LNK_ALIGN - 1) / LNK_ALIGN * LNK_ALIGN;
-  return here;
-}
-
-// lays the scratch arrays out from `base` (nullptr: only the size is wanted)
-size_t layout(LinkArgs& a, char* base, long long n, int ndim, long long n_levels) {
-  size_t at = 0;
-  const size_t N = (size_t)(n > 0 ? n : 1), L = (size_t)n_levels + 1;
-  // the words that every call zeroes come first, in one block
-  a.used = (int*)(base + carve(at, N * sizeof(int)));
-  a.nbirth = (int*)(base + carve(at, L * sizeof(int)));
-  const size_t zeroed = at;
-  a.spos = (double*)(base + carve(at, N * ndim * sizeof(double)));
-  a.cand_d2 = (double*)(base + carve(at, N * LNK_MAXC * sizeof(double)));
-  a.cand_row = (int*)(base + carve(at, N * LNK_MAXC * sizeof(int)));
-  int** per_row[] = {&a.ncand, &a.link, &a.lab_d, &a.lab_s, &a.cnt_s, &a.head_d, &a.head_s,
-                     &a.next_d, &a.next_s, &a.roots, &a.rank, &a.anc};
-  for (int** p : per_row) *p = (int*)(base + carve(at, N * sizeof(int)));
-  a.base = (long long*)(base + carve(at, L * sizeof(long long)));
-  if (!base) return at;
-  return zeroed;
-}
-
 template <int ND>
 void run(const LinkArgs& a, hipStream_t s) {
   const unsigned rows = (unsigned)((a.n + LNK_THREADS - 1) / LNK_THREADS);
@@ -79,13 +52,13 @@ int ctr_link_launch(const ctr_link* l, StageRun* stage, const char** msg) {
   if (l->n_features > 0 && (l->n_levels < 1 || !l->pos || !l->frame_offset)) { *msg = "features without levels, pos or frame_offset"; return CTR_ERR_INVALID; }
   if (l->n_features > 0 && (!l->particle || !l->n_tracks || !l->status)) { *msg = "null output"; return CTR_ERR_INVALID; }
   LinkArgs a = {};
-  stage->scratch_bytes = layout(a, nullptr, l->n_features, l->ndim, l->n_levels);
+  stage->scratch_bytes = lnk_layout(a, nullptr, l->n_features, l->ndim, l->n_levels);
   if (stage->mode != STAGE_LAUNCH) return CTR_OK;
   const hipStream_t s = stage->stream;
   if (l->status && hipMemsetAsync(l->status, 0, 4 * sizeof(int32_t), s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
   if (l->n_tracks && hipMemsetAsync(l->n_tracks, 0, sizeof(int64_t), s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
   if (l->n_features == 0) return CTR_OK;
-  const size_t zeroed = layout(a, (char*)stage->scratch, l->n_features, l->ndim, l->n_levels);
+  const size_t zeroed = lnk_layout(a, (char*)stage->scratch, l->n_features, l->ndim, l->n_levels);
   if (hipMemsetAsync(stage->scratch, 0, zeroed, s) != hipSuccess) { *msg = "hipMemsetAsync failed"; return CTR_ERR_DEVICE; }
   a.ndim = l->ndim;
   a.memory = l->memory < l->n_levels ? (int)l->memory : (int)l->n_levels;   // a longer memory reaches no further

@@ -450,8 +450,8 @@ def locate(frames, separation, diameter=None, minmass=0, percentile=64, margin=N
            device=0, dtype=None, noise_size=None, smoothing_size=None, threshold=None):
     """Features of a block of frames with their mass, signal and size: :func:`locate_maxima`,
     then :func:`characterize_arrays` with the positions still on the device, then the rows with
-    ``mass >= minmass`` (reference ``find_link``, find_link.py:927-971, without the relocation loop;
-    its candidate search is ``relocate.relocate_arrays``).
+    ``mass >= minmass`` (reference ``find_link``, find_link.py:927-971, without the relocation loop:
+    that is ``find_link.find_link``, its candidate search ``relocate.relocate_arrays``).
 
     ``diameter`` defaults to ``separation``; the mask radius is ``int(diameter // 2)`` per axis,
     the sizes are per axis when a diameter is given and anisotropic, and ``margin`` defaults to

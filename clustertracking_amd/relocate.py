@@ -6,8 +6,8 @@ When a sub-network has more sources than destinations the reference masks away w
 found around the lost features, takes the local maxima that remain in the processed frame and
 offers them to the linker.  :func:`relocate_arrays` answers a batch of such queries in one call,
 :func:`relocate_candidates` one query with the reference's return.  The loop around them
-(shortage per sub-network, claimed candidates added to the hash, the sub-network solved again) is
-not here.  There is no CPU fallback.
+(shortage per sub-network, merging, the sub-network solved with the claimed candidates) is
+``find_link.find_link``.  There is no CPU fallback.
 """
 import numpy as np
 

@@ -463,7 +463,7 @@ int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream);
 /* Relocation candidates of lost features on the device: the rule of the reference's
  * FindLinker.get_relocate_candidates (find_link.py:811-867), the look-again step that
  * makes find_link more than locate followed by link.  The loop around it (shortage per sub-network,
- * claimed candidates added to the hash, the sub-network solved again) is the caller's.
+ * merging, the sub-network solved with the claimed candidates) is ctr_find_link_device, below.
  * Derived once per call, as FindLinker.__init__ derives them: box = int(2 separation / sqrt(ndim))
  * per axis (0 filters like 1), slice_radius = int(search_range + radius + 1),
  * bg_radius = slice_radius + radius + 1, max_dist = max(bg_radius / search_range).
@@ -555,6 +555,91 @@ typedef struct ctr_relocate {
 } ctr_relocate;
 int ctr_relocate_device(ctr_handle* h, const ctr_relocate* r, void* hip_stream);
 int ctr_relocate_plan(const ctr_relocate* r, int64_t* tile_pixels, int64_t* lds_bytes);
+
+/* Find and link with relocation on the device: the loop of the reference's find_link
+ * (FindLinker.assign_links, find_link.py:869-911, with Subnets.merge_lost_subnets, :329-370;
+ * DESIGN.md 7b) around ctr_link_device's rule and ctr_relocate_device's.  The caller has located
+ * the features of every frame (ctr_locate_maxima_device, ctr_characterize_device, mass >= minmass):
+ * rows [frame_offset[t], frame_offset[t+1]) of pos / mass / signal / size are the located rows of
+ * frame t.  `frames` is what the relocation looks at (the preprocessed frames where there are any),
+ * threshold[t] what ctr_locate wrote for them.
+ * Level 0: the located rows of frame 0 start tracks in row order.
+ * Level t >= 1: destinations = the located rows of frame t; sources = all rows of level t - 1, the
+ * relocated ones included, and the rows remembered by ctr_link_device's memory rule.
+ *   1. candidates and sub-networks as ctr_link_device forms them; a source without candidate is a
+ *      sub-network of its own, without destination;
+ *   2. merging: shortage = sources - destinations per sub-network, before any merging; for every
+ *      source of a sub-network with a positive one its up to 10 nearest sources (itself and the
+ *      remembered ones included) at scaled distance <= 2 + 1e-7; the sub-networks of those sources
+ *      unite (a union: the order decides nothing);
+ *   3. relocation: every sub-network whose shortage after merging is positive issues one query by the
+ *      rule of ctr_relocate_device: its sources, the located rows of frame t as known features,
+ *      threshold[t].  Its first min(shortage, n_found) candidates by mass join the destinations, each
+ *      a link candidate of every source of the sub-network at scaled distance <= 1 + 1e-7
+ *      (sum((c / search_range - s / search_range)^2), axis order);
+ *   4. solve: inside a sub-network the links that maximise sum(2 - d^2), from the exact solver of
+ *      ctr_link_device (the reference's FindLinker sorts its candidates before the recursion, so its
+ *      recursion is exact too: the two differ at ties only).  A claimed candidate becomes a row of
+ *      level t with relocated = 1 and the mass, signal and size ctr_relocate_device gave it; an
+ *      unclaimed one is dropped; an unlinked located destination starts a track;
+ *   5. ids, births and memory as ctr_link_device; a relocated row is never a birth.
+ * The short sub-networks of a level do not see each other's claimed candidates (the reference adds
+ * them to the background of the queries it issues later, in dict order): coupled[t] = 1 where a
+ * claimed candidate lies at scaled distance <= max_dist (ctr_relocate_device) of a source of another
+ * query of the level -- only there could the reference's result differ.
+ * Output: the rows of all levels packed in level order, the located rows of a level in their order,
+ * then its relocated rows in C order of position; frame_offset_out[T] is their number (at most
+ * n_located + (n_frames - 1) * max_relocated, the rows the output arrays must hold).
+ * status[0] = CTR_FIND_LINK_*, for a non-zero one status[1] = the level and status[2] = a size:
+ * OVERSIZE more than CTR_LINK_MAX_SOURCES sources in a sub-network after merging; CAPACITY more than
+ * CTR_LINK_MAX_DESTINATIONS destinations, relocated included; RELOCATE a query ended with a
+ * non-zero status (status[2]); QUERIES more than max_queries short sub-networks in the level; ROWS
+ * more than max_relocated claimed candidates.  The first level that fails is reported; no kernel
+ * stops, and with a non-zero status no output is a result.  The call zeroes status and coupled.
+ * Levels are queued one after the other on the stream (candidates, merge, relocation with
+ * max_queries workgroups -- one without sources ends at once --, solve); nothing crosses to the host
+ * in between.  Scratch belongs to the handle (the block of ctr_link_device); no floating-point
+ * atomics: the same bytes on any stream.
+ * The descriptor is checked before the handle, as for ctr_characterize_device.
+ * Device pointers; asynchronous on `hip_stream` (NULL = the handle's stream): read status after
+ * synchronising. */
+enum { CTR_FIND_LINK_OK = 0, CTR_FIND_LINK_OVERSIZE = 1, CTR_FIND_LINK_CAPACITY = 2, CTR_FIND_LINK_RELOCATE = 3,
+       CTR_FIND_LINK_QUERIES = 4, CTR_FIND_LINK_ROWS = 5 };
+typedef struct ctr_find_link {
+  int32_t ndim;                /* 2 or 3 */
+  int32_t frame_dtype;         /* CTR_DTYPE_* */
+  int64_t n_frames;            /* T */
+  int64_t shape[CTR_MAX_NDIM]; /* (z,) y, x */
+  int64_t radius[CTR_MAX_NDIM];        /* per axis, >= 0: diameter // 2 */
+  double separation[CTR_MAX_NDIM];     /* per axis, > 0 */
+  double search_range[CTR_MAX_NDIM];   /* per axis, > 0 */
+  int32_t isotropic;           /* != 0: one size per row */
+  int32_t memory;              /* >= 0 */
+  int32_t max_queries;         /* 1 .. 1024: relocation queries per level */
+  int32_t max_relocated;       /* 1 .. 1024: relocated rows per level */
+  double minmass;              /* of a relocation candidate */
+  double scale_factor;         /* of a relocation candidate's mass and signal; not 0 */
+  const void* frames;          /* [T, *shape] */
+  const double* threshold;     /* [T] */
+  int64_t n_located;           /* M */
+  const double* pos;           /* [M, ndim] located rows, sorted by frame */
+  const int64_t* frame_offset; /* [T + 1] */
+  const double* mass;          /* [M] */
+  const double* signal;        /* [M] */
+  const double* size;          /* [M] (isotropic) or [M, ndim] */
+  int64_t capacity;            /* rows of the outputs: >= M + (T - 1) * max_relocated */
+  double* pos_out;             /* [capacity, ndim] out */
+  int64_t* frame_offset_out;   /* [T + 1] out */
+  int64_t* particle;           /* [capacity] out */
+  double* mass_out;            /* [capacity] out */
+  double* signal_out;          /* [capacity] out */
+  double* size_out;            /* [capacity] or [capacity, ndim] out */
+  uint8_t* relocated;          /* [capacity] out */
+  int64_t* n_tracks;           /* [1] out */
+  int32_t* coupled;            /* [T] out */
+  int32_t* status;             /* [4] out */
+} ctr_find_link;
+int ctr_find_link_device(ctr_handle* h, const ctr_find_link* f, void* hip_stream);
 
 /* Orientation of tracked clusters on the device: the rule of the reference's motion.orientation_df
  * (motion.py:40-162), the step behind ctr_link_device.  `pos` holds, per track and
