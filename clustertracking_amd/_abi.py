@@ -204,6 +204,17 @@ class FindLink(C.Structure):
     ]
 
 
+class RefineCom(C.Structure):
+    """``ctr_refine_com`` (include/ctrefine.h): centre-of-mass refinement of features."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('frame_dtype', C.c_int32), ('n_frames', C.c_int64),
+        ('shape', C.c_int64 * MAX_NDIM), ('radius', C.c_int64 * MAX_NDIM),
+        ('max_iterations', C.c_int32), ('reserved0', C.c_int32), ('shift_thresh', C.c_double),
+        ('frames', C.c_void_p), ('n_features', C.c_int64), ('frame_offset', C.c_void_p),
+        ('pos', C.c_void_p), ('pos_out', C.c_void_p), ('mass', C.c_void_p), ('n_iter', C.c_void_p),
+    ]
+
+
 class Orientation(C.Structure):
     """``ctr_orientation`` (include/ctrefine.h): orientation of tracked clusters on the device."""
     _fields_ = [

@@ -50,6 +50,8 @@ SIGNATURES = {
     'ctr_relocate_device': _stage(_abi.Relocate),
     'ctr_relocate_plan': (C.c_int, [_P(_abi.Relocate), _P(C.c_int64), _P(C.c_int64)]),
     'ctr_find_link_device': _stage(_abi.FindLink),
+    'ctr_refine_com_device': _stage(_abi.RefineCom),
+    'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
     'ctr_diffusion_ci_device': _stage(_abi.DiffusionCI),
     'ctr_diffusion_ci_plan': (C.c_int, [_P(_abi.DiffusionCI), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                         _P(C.c_int64)]),
@@ -309,6 +311,12 @@ class Engine(object):
             call(*args, 0)
             self.stream_wait_engine(0)
 
+    def find_link_refine_device(self, desc, com, stream=None):
+        """``ctr_find_link_refine_device``: ``desc`` an ``_abi.FindLink``, ``com`` an ``_abi.RefineCom``
+        (raw frames, ``max_iterations``, ``shift_thresh``), device pointers."""
+        self._check(self._lib.ctr_find_link_refine_device(self._h, C.byref(desc), C.byref(com),
+                                                          C.c_void_p(stream or 0)), 'ctr_find_link_refine_device')
+
     def last_kernel_ms(self):
         a, b = C.c_double(), C.c_double()
         self._check(self._lib.ctr_last_kernel_ms(self._h, C.byref(a), C.byref(b)),
@@ -334,7 +342,8 @@ for _name, _symbol, _too_large in (
         ('diffusion_device', 'ctr_diffusion_device', False),
         ('diffusion_ci_device', 'ctr_diffusion_ci_device', False),
         ('relocate_device', 'ctr_relocate_device', False),
-        ('find_link_device', 'ctr_find_link_device', False)):
+        ('find_link_device', 'ctr_find_link_device', False),
+        ('refine_com_device', 'ctr_refine_com_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 
 

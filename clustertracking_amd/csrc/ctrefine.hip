@@ -114,7 +114,7 @@ struct ctr_handle {
   hipStream_t side[NSIDE] = {};
   hipEvent_t ev_fork = nullptr, ev_gate = nullptr, ev_order = nullptr, ev_join[NSIDE] = {};
   int* d_counter = nullptr;       // work counters of the small-kernel launches
-  // ctr_link_device and ctr_find_link_device; ctr_diffusion_device and ctr_diffusion_ci_device (partial sums, rows, statistics)
+  // ctr_link_device, ctr_find_link_device and ctr_find_link_refine_device; ctr_diffusion_device and ctr_diffusion_ci_device (partial sums, rows, statistics)
   Scratch link, motion;
 };
 
@@ -1059,6 +1059,15 @@ int ctr_relocate_device(ctr_handle* h, const ctr_relocate* r, void* hip_stream) 
 
 int ctr_find_link_device(ctr_handle* h, const ctr_find_link* f, void* hip_stream) {
   return run_stage("ctr_find_link_device", h, &ctr_handle::link, f, hip_stream, ctr_find_link_launch);
+}
+
+int ctr_refine_com_device(ctr_handle* h, const ctr_refine_com* c, void* hip_stream) {
+  return run_stage("ctr_refine_com_device", h, nullptr, c, hip_stream, ctr_refine_com_launch);
+}
+
+int ctr_find_link_refine_device(ctr_handle* h, const ctr_find_link* f, const ctr_refine_com* com, void* hip_stream) {
+  const FindLinkRefine d = {f, com};
+  return run_stage("ctr_find_link_refine_device", h, &ctr_handle::link, &d, hip_stream, ctr_find_link_refine_launch);
 }
 
 int ctr_relocate_plan(const ctr_relocate* r, int64_t* tile_pixels, int64_t* lds_bytes) {

@@ -121,7 +121,8 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // feature location (tu_locate.hip, locate_kernels.h): checks the descriptor and queues the whole
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
-// The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink)
+// The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
+// tu_refine_com)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -157,5 +158,26 @@ int ctr_relocate_launch(const ctr_relocate* r, StageRun* stage, const char** msg
                         long long* lds_bytes);
 // find and link with relocation (findlink_kernels.h; scratch): queues ctr_relocate_launch per level
 int ctr_find_link_launch(const ctr_find_link* f, StageRun* stage, const char** msg);
+// centre-of-mass refinement (refine_com_kernels.h).  level (may be null): instead of the
+// descriptor's table, the rows [*start, *start + *cnt) of a level of ctr_find_link_launch's table,
+// counted on the device (at most max_rows), all of frame `frame`, refined in place: pos and mass,
+// and spos = pos / sr
+struct RefineComLevel {
+  const long long* start;
+  const int* cnt;
+  long long max_rows;
+  int frame;
+  double* pos;
+  double* mass;
+  double* spos;
+  double sr[3];
+};
+int ctr_refine_com_launch(const ctr_refine_com* c, StageRun* stage, const char** msg, const RefineComLevel* level);
+// ctr_find_link_refine_device: ctr_find_link_launch's loop with ctr_refine_com_launch per level
+struct FindLinkRefine {
+  const ctr_find_link* f;
+  const ctr_refine_com* com;
+};
+int ctr_find_link_refine_launch(const FindLinkRefine* d, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

@@ -1,4 +1,5 @@
-// tu_findlink.hip -- find and link with relocation (ctr_find_link_device; findlink_kernels.h,
+// tu_findlink.hip -- find and link with relocation (ctr_find_link_device and, with the
+// centre-of-mass refinement of every level, ctr_find_link_refine_device; findlink_kernels.h,
 // DESIGN.md 7b).  Distances are compared with the host linker's and the relocation's: no
 // floating-point contraction in this unit.
 #pragma clang fp contract(off)
@@ -45,20 +46,31 @@ size_t layout(FlArgs& a, char* base, int ndim, long long n_levels) {
   return base ? zeroed : at;
 }
 
+// com (may be null): the rows of level t are refined in place in the table (ctr_refine_com_launch)
+int refine_level(const FlArgs& a, const ctr_refine_com* com, int t, StageRun* sub, const char** msg) {
+  if (!com) return CTR_OK;
+  RefineComLevel level = {a.start + t, a.cnt + t, a.ncap, t, a.ppos, a.pmass, a.l.spos, {a.l.sr[0], a.l.sr[1], a.l.sr[2]}};
+  return ctr_refine_com_launch(com, sub, msg, &level);
+}
+
 template <int ND>
-int run(const FlArgs& a, const ctr_relocate& rel, hipStream_t s, const char** msg) {
+int run(const FlArgs& a, const ctr_relocate& rel, const ctr_refine_com* com, hipStream_t s, const char** msg) {
   const unsigned rows = (unsigned)((a.ncap + LNK_THREADS - 1) / LNK_THREADS);
   hipLaunchKernelGGL(fl_start_kernel, dim3(1), dim3(LNK_THREADS), 0, s, a);
   hipLaunchKernelGGL(fl_fill_kernel<ND>, dim3(rows), dim3(LNK_THREADS), 0, s, a);
   // the host does not read the levels' sizes: a fixed grid strides over a level's rows
   const unsigned per_level = rows < 16u ? rows : 16u;
   StageRun sub = {STAGE_LAUNCH, s, nullptr, 0};
+  int rc = refine_level(a, com, 0, &sub, msg);
+  if (rc != CTR_OK) return rc;
   for (int t = 1; t < a.n_levels; ++t) {
     hipLaunchKernelGGL(link_cand_kernel<ND>, dim3(per_level), dim3(LNK_THREADS), 0, s, a.l, t, t + 1);
     hipLaunchKernelGGL(fl_merge_kernel<ND>, dim3(1), dim3(LNK_THREADS), 0, s, a, t);
-    const int rc = ctr_relocate_launch(&rel, &sub, msg, nullptr, nullptr);
+    rc = ctr_relocate_launch(&rel, &sub, msg, nullptr, nullptr);
     if (rc != CTR_OK) return rc;
     hipLaunchKernelGGL(fl_solve_kernel<ND>, dim3(1), dim3(LNK_THREADS), 0, s, a, t);
+    rc = refine_level(a, com, t, &sub, msg);
+    if (rc != CTR_OK) return rc;
   }
   hipLaunchKernelGGL(link_rank_kernel<ND>, dim3(rows), dim3(LNK_THREADS), 0, s, a.l);
   hipLaunchKernelGGL(link_scan_kernel, dim3(1), dim3(LNK_THREADS), 0, s, a.l);
@@ -70,9 +82,8 @@ int run(const FlArgs& a, const ctr_relocate& rel, hipStream_t s, const char** ms
   return CTR_OK;
 }
 
-}  // namespace
-
-int ctr_find_link_launch(const ctr_find_link* f, StageRun* stage, const char** msg) {
+// what both entry points run.  com (may be null): the refinement of every level
+int find_link(const ctr_find_link* f, const ctr_refine_com* com, StageRun* stage, const char** msg) {
   *msg = "";
   if (!f) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
   if (f->ndim != 2 && f->ndim != 3) { *msg = "ndim must be 2 or 3"; return CTR_ERR_INVALID; }
@@ -106,6 +117,18 @@ int ctr_find_link_launch(const ctr_find_link* f, StageRun* stage, const char** m
   for (int d = 0; d < f->ndim; ++d) {   // FindLinker.__init__ (find_link.py:766-781), as tu_relocate.hip
     const long long slr = (long long)(f->search_range[d] + (double)f->radius[d] + 1.);
     max_dist = std::max(max_dist, (double)(slr + f->radius[d] + 1) / f->search_range[d]);
+  }
+  if (com) {   // its own checks of max_iterations, shift_thresh and the window; then the shared fields
+    StageRun com_scalars = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+    const int rcc = ctr_refine_com_launch(com, &com_scalars, msg, nullptr);
+    if (rcc != CTR_OK) return rcc;
+    if (com->ndim != f->ndim) { *msg = "the refinement's ndim differs from the find-link descriptor's"; return CTR_ERR_INVALID; }
+    if (com->n_frames != f->n_frames) { *msg = "the refinement's n_frames differs from the find-link descriptor's"; return CTR_ERR_INVALID; }
+    for (int d = 0; d < f->ndim; ++d) {
+      if (com->shape[d] != f->shape[d]) { *msg = "the refinement's shape differs from the find-link descriptor's"; return CTR_ERR_INVALID; }
+      if (com->radius[d] != f->radius[d]) { *msg = "the refinement's radius differs from the find-link descriptor's"; return CTR_ERR_INVALID; }
+    }
+    if (f->n_frames > 0 && !com->frames) { *msg = "null frames of the refinement"; return CTR_ERR_INVALID; }
   }
   if (f->n_frames > 0 && !f->frame_offset) { *msg = "null frame_offset"; return CTR_ERR_INVALID; }
   if (f->n_located > 0 && (!f->pos || !f->mass || !f->signal || !f->size)) { *msg = "null table of located rows"; return CTR_ERR_INVALID; }
@@ -170,9 +193,22 @@ int ctr_find_link_launch(const ctr_find_link* f, StageRun* stage, const char** m
   rel.signal = a.r_signal;
   rel.size = a.r_size;
   rel.status = a.r_status;
-  const int rr = f->ndim == 2 ? run<2>(a, rel, s, msg) : run<3>(a, rel, s, msg);
+  const int rr = f->ndim == 2 ? run<2>(a, rel, com, s, msg) : run<3>(a, rel, com, s, msg);
   if (rr != CTR_OK) return rr;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { *msg = hipGetErrorString(e); return CTR_ERR_DEVICE; }
   return CTR_OK;
+}
+
+}  // namespace
+
+int ctr_find_link_launch(const ctr_find_link* f, StageRun* stage, const char** msg) {
+  return find_link(f, nullptr, stage, msg);
+}
+
+int ctr_find_link_refine_launch(const FindLinkRefine* d, StageRun* stage, const char** msg) {
+  *msg = "";
+  if (!d || !d->f) { *msg = "null descriptor"; return CTR_ERR_INVALID; }
+  if (!d->com) { *msg = "null refinement descriptor"; return CTR_ERR_INVALID; }
+  return find_link(d->f, d->com, stage, msg);
 }

@@ -12,7 +12,16 @@ There is no CPU fallback.
 Not the reference's on every input: the short sub-networks of a level do not see each other's
 claimed candidates (the reference adds them to the background of the queries it issues later), so
 on a *coupled* level -- reported per level, see :func:`find_link_arrays` -- parity with the reference
-is not pinned.  ``before_link``, ``after_link`` and ``refine`` are not taken.
+is not pinned.
+
+``refine=True`` is the reference's convenience parameter (find_link.py:436-465): after every level
+its features, the relocated ones included, are moved to their centre of mass in the RAW frame
+(``ctr_find_link_refine_device``; the rule of ``refine_com.refine_com_arrays``), and the linker
+measures the next level from the refined positions, so a track is kept or lost differently than
+with whole-pixel sources.  The rule is trackpy's ``refine_com`` restated, with a clip at the edge of
+the frame that trackpy lacks: parity with trackpy itself is not pinned, the loop around it is the
+reference's.  ``before_link`` and ``after_link`` (Python per frame) and a callable ``refine`` are
+not taken.
 """
 import collections
 
@@ -23,6 +32,7 @@ from . import _abi, _lib
 from ._lib import EngineError
 from .find import _characterize_device, _device_frames, _size_columns, locate_arrays
 from .link import SubnetOversizeException
+from .refine_com import MAX_ITERATIONS, SHIFT_THRESH, descriptor as _refine_descriptor
 from .utils import validate_tuple
 
 MAX_QUERIES = 64        # relocation queries per level (short sub-networks after merging)
@@ -32,11 +42,14 @@ FindLinkResult = collections.namedtuple(
     'FindLinkResult', 'pos frame_offset particle mass signal size relocated n_tracks coupled status')
 
 
-def _refuse_callbacks(kwargs):
-    for name in ('before_link', 'after_link', 'refine'):
+def _refuse_callbacks(kwargs, refine=False):
+    if refine and refine is not True:
+        raise NotImplementedError("find_link: a callback is not taken: refine takes True (centre-of-mass "
+                                  "refinement after every level) or False")
+    for name in ('before_link', 'after_link'):
         if kwargs.pop(name, None):
-            raise NotImplementedError("find_link: %s is not taken (a callback per frame; refine needs trackpy): "
-                                      "refine the result with refine_leastsq" % name)
+            raise NotImplementedError("find_link: %s is not taken (a callback per frame): refine=True refines "
+                                      "every level by centre of mass, refine_leastsq the result" % name)
     if kwargs:
         raise TypeError("find_link: unexpected arguments %s" % sorted(kwargs))
 
@@ -44,7 +57,7 @@ def _refuse_callbacks(kwargs):
 def find_link_arrays(frames, search_range, separation, diameter=None, memory=0, minmass=0, noise_size=None,
                      smoothing_size=None, threshold=None, percentile=64, device=0, dtype=None,
                      max_queries=MAX_QUERIES, max_relocated=MAX_RELOCATED, scale_factor=1., _on_device=False,
-                     **kwargs):
+                     refine=False, max_iterations=MAX_ITERATIONS, shift_thresh=SHIFT_THRESH, **kwargs):
     """The arrays behind :func:`find_link`: a ``FindLinkResult`` of NumPy arrays (``_on_device``,
     internal: of torch tensors on the device) --
 
@@ -61,11 +74,16 @@ def find_link_arrays(frames, search_range, separation, diameter=None, memory=0, 
     the reference reads from the frames' metadata; it divides mass and signal of the relocated rows
     and, without preprocessing (the frames the location looks at are the ones that carry it), of
     the located rows before ``minmass``.
+    ``refine=True`` (with ``max_iterations``, ``shift_thresh``: ``refine_com.refine_com_arrays``):
+    ``pos`` is sub-pixel, the centre of mass in the raw frame, and ``mass`` the refinement's (the sum
+    of the masked raw pixels, no scale factor) for located and relocated rows alike; ``signal`` and
+    ``size`` stay from the unrefined position; the relocated rows of a frame follow in C order of
+    their refined position.
     Raises ``SubnetOversizeException`` for a sub-network of more than 30 sources after merging and
     ``EngineError`` naming the level for one of more than 64 destinations (relocated included), a
     relocation query beyond ``ctr_relocate_device``'s limits, or a level beyond ``max_queries`` /
     ``max_relocated``; also without a library or a GPU."""
-    _refuse_callbacks(kwargs)
+    _refuse_callbacks(kwargs, refine)
     if not hasattr(frames, 'shape'):
         frames = np.asarray(frames)
     shape = tuple(frames.shape)
@@ -146,7 +164,12 @@ def find_link_arrays(frames, search_range, separation, diameter=None, memory=0, 
         d.pos_out, d.frame_offset_out, d.particle = out_pos.data_ptr(), out_off.data_ptr(), particle.data_ptr()
         d.mass_out, d.signal_out, d.size_out = out_mass.data_ptr(), out_signal.data_ptr(), out_size.data_ptr()
         d.relocated, d.n_tracks, d.coupled, d.status = (x.data_ptr() for x in (relocated, n_tracks, coupled, status))
-        eng.on_current_stream(eng.find_link_device, d, dev=dev)
+        if refine:      # find_link.py:462: the refinement reads the raw image
+            com = _refine_descriptor(shape[1:], raw_pix, n_frames, radius, max_iterations, shift_thresh)
+            com.frames = raw_t.data_ptr()
+            eng.on_current_stream(eng.find_link_refine_device, d, com, dev=dev)
+        else:
+            eng.on_current_stream(eng.find_link_device, d, dev=dev)
         # the one synchronisation of the loop: the status words and the number of rows
         tail = torch.cat([status.to(torch.int64), out_off[-1:]]).cpu()
     code, level, size_seen, _, n = (int(v) for v in tail)
@@ -171,7 +194,8 @@ def find_link_arrays(frames, search_range, separation, diameter=None, memory=0, 
 
 
 def find_link(frames, search_range, separation, diameter=None, memory=0, minmass=0, noise_size=None,
-              smoothing_size=None, threshold=None, percentile=64, device=0, dtype=None, **kwargs):
+              smoothing_size=None, threshold=None, percentile=64, device=0, dtype=None, refine=False,
+              max_iterations=MAX_ITERATIONS, shift_thresh=SHIFT_THRESH, **kwargs):
     """Reference ``find_link`` on the MI355X: the features of every frame of ``frames``
     ([T, (z,) y, x], ndarray or tensor on cuda:``device``, as for ``locate``) located, characterised
     and linked, with relocation of the features the location lost.
@@ -185,10 +209,14 @@ def find_link(frames, search_range, separation, diameter=None, memory=0, minmass
     ``noise_size=None`` (the default here; the reference's is 1) skips the preprocessing.  With it,
     maxima and relocation use the preprocessed frames, which stay on the device; mass, signal and
     size of located rows come from the raw frames, those of relocated rows from the masked
-    preprocessed frame (find_link.py:860).  ``before_link``, ``after_link`` and ``refine`` raise
+    preprocessed frame (find_link.py:860).  ``refine=True``: the features of every level are moved
+    to their centre of mass in the raw frame before the next level is linked (``max_iterations``,
+    ``shift_thresh``; :func:`find_link_arrays`); the positions are then sub-pixel and ``mass`` is
+    the refinement's.  ``before_link``, ``after_link`` and a callable ``refine`` raise
     ``NotImplementedError``.  Further keywords and the errors: :func:`find_link_arrays`."""
     r = find_link_arrays(frames, search_range, separation, diameter, memory, minmass, noise_size, smoothing_size,
-                         threshold, percentile, device, dtype, **kwargs)
+                         threshold, percentile, device, dtype, refine=refine, max_iterations=max_iterations,
+                         shift_thresh=shift_thresh, **kwargs)
     ndim = r.pos.shape[1]
     result = pd.DataFrame(r.pos, columns=['z', 'y', 'x'][3 - ndim:])
     result['frame'] = np.repeat(np.arange(len(r.frame_offset) - 1, dtype=np.int64), np.diff(r.frame_offset))

@@ -641,6 +641,73 @@ typedef struct ctr_find_link {
 } ctr_find_link;
 int ctr_find_link_device(ctr_handle* h, const ctr_find_link* f, void* hip_stream);
 
+/* Centre-of-mass refinement of features on the device: what the reference's find_link(refine=True)
+ * asks of trackpy.refine(image, image, radius, coords, separation=0, characterize=False)
+ * (find_link.py:436-465).  trackpy is not part of the reference's tree: the rule
+ * below is its refine_com loop RESTATED from the published source and made total (step 1); parity
+ * with trackpy itself is not pinned.
+ * Inputs of one feature: a frame of `shape`; a start c, each axis rounded half to even to an
+ * integer; an integer radius r, at least 1 per axis, with 2 r[a] + 1 <= shape[a]; max_iterations
+ * (1 .. 100; trackpy's default 10); shift_thresh (> 0; trackpy's default 0.6).
+ * Mask: the window offsets k with -r[a] <= k[a] <= r[a] and sum((k[a] / r[a])^2) <= 1, the support
+ * of ctr_characterize_device's weights.
+ *   1. clip c to [r, shape - 1 - r] per axis (trackpy does not, and would slice out of the frame: a
+ *      relocated row can lie closer to the edge than r);
+ *   2. evaluate the window at c: m = the sum of the masked pixels, cm[a] = the sum of the masked
+ *      pixels times j[a], divided by m, with j = k + r (the window index from 0);
+ *      off[a] = cm[a] - r[a]; if any cm[a] is NaN (m == 0; trackpy's _safe_center_of_mass): off = 0.
+ *      Integer frames: both sums are exact in int64 and each is converted to float64 once.  Float
+ *      frames: float64 sums (pixels outside the mask are multiplied by 0, as NumPy's mask * image);
+ *   3. if abs(off[a]) < shift_thresh on every axis: stop;
+ *   4. otherwise c[a] += 1 where off[a] > shift_thresh, c[a] -= 1 where off[a] < -shift_thresh, clip as
+ *      in step 1 and, if fewer than max_iterations windows have been evaluated, go to step 2.
+ * Result, all of it from the last evaluated window and the c it was evaluated at, not from a move
+ * made after it: pos[a] = (cm[a] - r[a]) + c[a] in that order (float64, no contraction); mass = m
+ * as float64, not divided by any scale factor; n_iter = the number of windows evaluated.  An off
+ * exactly equal to the threshold neither stops nor moves: the same window is evaluated until
+ * max_iterations.
+ * Rows [frame_offset[t], frame_offset[t+1]) of pos are the features of frame t (what ctr_locate and
+ * ctr_find_link write).  pos_out may be pos.  A NaN start has no defined result (the Python layer
+ * refuses it).  No scratch, no atomics: the same bytes in any launch.
+ * The descriptor is checked before the handle, as for ctr_characterize_device.
+ * Device pointers; asynchronous on `hip_stream` (NULL = the handle's stream). */
+typedef struct ctr_refine_com {
+  int32_t ndim;                /* 2 or 3 */
+  int32_t frame_dtype;         /* CTR_DTYPE_* */
+  int64_t n_frames;
+  int64_t shape[CTR_MAX_NDIM]; /* (z,) y, x */
+  int64_t radius[CTR_MAX_NDIM];    /* per axis, >= 1, 2 radius + 1 <= shape */
+  int32_t max_iterations;      /* 1 .. 100 */
+  int32_t reserved0;
+  double shift_thresh;         /* > 0 */
+  const void* frames;          /* [n_frames, *shape] */
+  int64_t n_features;          /* N */
+  const int64_t* frame_offset; /* [n_frames + 1] */
+  const double* pos;           /* [N, ndim] starts (z,) y, x */
+  double* pos_out;             /* [N, ndim] out */
+  double* mass;                /* [N] out */
+  int32_t* n_iter;             /* [N] out */
+} ctr_refine_com;
+int ctr_refine_com_device(ctr_handle* h, const ctr_refine_com* c, void* hip_stream);
+
+/* ctr_find_link_device with the refinement above after every level: the reference's
+ * find_link(refine=True), whose after_link callback refines the features of a level and whose
+ * linker.set_dataframe writes the positions back into the points (find_link.py:651-654, 1001-1007).
+ * `com` supplies the raw frames ([T, *shape]), their dtype, max_iterations and shift_thresh; its
+ * ndim, n_frames, shape and radius must equal f's (else CTR_ERR_INVALID naming the field); its
+ * table pointers (n_features, frame_offset, pos, pos_out, mass, n_iter) are ignored.
+ * The rows of level 0 are refined before the first level is linked; the rows of level t >= 1, its
+ * claimed relocated rows included, after step 4 of that level.  The refinement is in place in the
+ * linker's table: position and mass of the row become pos and mass of ctr_refine_com.  So the
+ * sources of level t + 1 (the remembered ones keep what they had), the sources of the relocation
+ * queries, the coupled test (whose claimed candidates are still whole pixels when it runs) and the
+ * emitted table see refined values; the destinations of a level are linked from where they were
+ * located; the known features that the relocation masks with stay the located ones
+ * (find_link.py:827); signal and size stay from the unrefined position.  The relocated rows of a
+ * level are emitted in C order of their refined position.
+ * Everything else, the status words included, as ctr_find_link_device. */
+int ctr_find_link_refine_device(ctr_handle* h, const ctr_find_link* f, const ctr_refine_com* com, void* hip_stream);
+
 /* Orientation of tracked clusters on the device: the rule of the reference's motion.orientation_df
  * (motion.py:40-162), the step behind ctr_link_device.  `pos` holds, per track and
  * frame, the features of the cluster in the order of their `particle`; a frame in which the cluster
