@@ -13,6 +13,7 @@ from .preprocessing import lowpass, bandpass, preprocess
 from .relocate import relocate_arrays, relocate_candidates
 from .find_link import find_link, find_link_arrays
 from .refine_com import refine_com, refine_com_arrays
+from .train import train_leastsq, train_arrays
 from .fitfunc import FitFunctions
 from .utils import ArrayReader, RefineException
 from . import constraints, artificial, link, motion, motion_ci, preprocessing
@@ -21,7 +22,7 @@ from .motion_ci import diffusion_tensor_ci, bootstrap_indices
 link_df = link.link
 link_arrays = link.link_arrays
 
-__all__ = ['refine_leastsq', 'find_clusters', 'grey_dilation', 'locate_maxima',
+__all__ = ['refine_leastsq', 'train_leastsq', 'train_arrays', 'find_clusters', 'grey_dilation', 'locate_maxima',
            'characterize', 'characterize_arrays', 'locate', 'relocate_arrays', 'relocate_candidates', 'find_link', 'find_link_arrays', 'refine_com', 'refine_com_arrays', 'lowpass', 'bandpass', 'preprocess', 'preprocessing',
            'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'link_arrays', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',

@@ -215,6 +215,27 @@ class RefineCom(C.Structure):
     ]
 
 
+TRAIN_MAX_GLOBALS, TRAIN_MAX_FEATURES = 8, 64
+
+
+class Train(C.Structure):
+    """``ctr_train`` (include/ctrefine.h): training of shared fit parameters on the device."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('isotropic', C.c_int32), ('fit_function', C.c_int32),
+        ('n_params', C.c_int32), ('modes', C.c_int32 * MAX_PARAMS), ('radius', C.c_int32 * MAX_NDIM),
+        ('frame_dtype', C.c_int32), ('solver_maxiter', C.c_int32), ('max_features', C.c_int32),
+        ('check_every', C.c_int32),
+        ('n_frames', C.c_int64), ('shape', C.c_int64 * MAX_NDIM),
+        ('n_problems', C.c_int64), ('n_clusters', C.c_int64), ('n_features', C.c_int64),
+        ('residual_factor', C.c_double), ('max_rms_dev', C.c_double),
+        ('xtol', C.c_double), ('ftol', C.c_double),
+        ('frames', C.c_void_p), ('params', C.c_void_p), ('feat_offset', C.c_void_p),
+        ('frame_index', C.c_void_p), ('problem_offset', C.c_void_p),
+        ('start', C.c_void_p), ('low', C.c_void_p), ('high', C.c_void_p),
+        ('globals', C.c_void_p), ('cost', C.c_void_p), ('status', C.c_void_p), ('n_iter', C.c_void_p),
+    ]
+
+
 class Orientation(C.Structure):
     """``ctr_orientation`` (include/ctrefine.h): orientation of tracked clusters on the device."""
     _fields_ = [

@@ -51,6 +51,7 @@ SIGNATURES = {
     'ctr_relocate_plan': (C.c_int, [_P(_abi.Relocate), _P(C.c_int64), _P(C.c_int64)]),
     'ctr_find_link_device': _stage(_abi.FindLink),
     'ctr_refine_com_device': _stage(_abi.RefineCom),
+    'ctr_train_device': _stage(_abi.Train),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
     'ctr_diffusion_ci_device': _stage(_abi.DiffusionCI),
     'ctr_diffusion_ci_plan': (C.c_int, [_P(_abi.DiffusionCI), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
@@ -343,7 +344,8 @@ for _name, _symbol, _too_large in (
         ('diffusion_ci_device', 'ctr_diffusion_ci_device', False),
         ('relocate_device', 'ctr_relocate_device', False),
         ('find_link_device', 'ctr_find_link_device', False),
-        ('refine_com_device', 'ctr_refine_com_device', False)):
+        ('refine_com_device', 'ctr_refine_com_device', False),
+        ('train_device', 'ctr_train_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 
 

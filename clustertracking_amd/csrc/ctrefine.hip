@@ -116,6 +116,7 @@ struct ctr_handle {
   int* d_counter = nullptr;       // work counters of the small-kernel launches
   // ctr_link_device, ctr_find_link_device and ctr_find_link_refine_device; ctr_diffusion_device and ctr_diffusion_ci_device (partial sums, rows, statistics)
   Scratch link, motion;
+  Scratch train;   // ctr_train_device: frame maxima, partial sums, solver state
 };
 
 namespace {
@@ -212,16 +213,6 @@ int n_vars(const ctr_problem* p, int n) {
   return nv;
 }
 
-size_t host_dtype_size(int dtype) {
-  switch (dtype) {
-    case CTR_DTYPE_U8: return 1;
-    case CTR_DTYPE_U16: case CTR_DTYPE_I16: return 2;
-    case CTR_DTYPE_I32: case CTR_DTYPE_F32: return 4;
-    case CTR_DTYPE_F64: return 8;
-    default: return 0;
-  }
-}
-
 // at least `need` bytes in sc.  A block that grows is replaced once the device is idle: a kernel
 // of an earlier call, on whichever stream, may still use the old one.
 int reserve(ctr_handle* h, Scratch& sc, size_t need, const char* or_else) {
@@ -277,16 +268,10 @@ int launch_frame_max(ctr_handle* h, const void* frames, int dtype, int64_t n_fra
   if (n_frames <= 0) return CTR_OK;
   int rc = ensure_fmax(h, n_frames);
   if (rc) return rc;
-  const size_t chunk_elems = FM_CHUNK_BYTES / isz;
-  const int chunks = (int)(((size_t)frame_elems + chunk_elems - 1) / chunk_elems);
-  HIP_TRY(h, hipMemsetAsync(h->enc.ptr, 0, sizeof(unsigned long long) * (size_t)n_frames, s));
-  const long long grid = (long long)n_frames * chunks;
-  if (grid > 0x7fffffffLL) return fail(h, CTR_ERR_INVALID, "frame block too large for one launch");
-  hipLaunchKernelGGL(frame_max_kernel, dim3((unsigned)grid), dim3(FM_THREADS), 0, s, frames, dtype,
-                     (size_t)frame_elems, chunks, chunk_elems, (unsigned long long*)h->enc.ptr);
-  hipLaunchKernelGGL(frame_max_decode_kernel, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, s,
-                     (const unsigned long long*)h->enc.ptr, out, n_frames);
-  HIP_TRY(h, hipGetLastError());
+  bool too_large = false;
+  const hipError_t e = queue_frame_max(frames, dtype, n_frames, frame_elems, (unsigned long long*)h->enc.ptr, out, s, &too_large);
+  if (too_large) return fail(h, CTR_ERR_INVALID, "frame block too large for one launch");
+  HIP_TRY(h, e);
   return CTR_OK;
 }
 
@@ -490,7 +475,7 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1063,6 +1048,10 @@ int ctr_find_link_device(ctr_handle* h, const ctr_find_link* f, void* hip_stream
 
 int ctr_refine_com_device(ctr_handle* h, const ctr_refine_com* c, void* hip_stream) {
   return run_stage("ctr_refine_com_device", h, nullptr, c, hip_stream, ctr_refine_com_launch);
+}
+
+int ctr_train_device(ctr_handle* h, const ctr_train* t, void* hip_stream) {
+  return run_stage("ctr_train_device", h, &ctr_handle::train, t, hip_stream, ctr_train_launch);
 }
 
 int ctr_find_link_refine_device(ctr_handle* h, const ctr_find_link* f, const ctr_refine_com* com, void* hip_stream) {

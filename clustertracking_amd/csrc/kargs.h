@@ -122,7 +122,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
-// tu_refine_com)
+// tu_refine_com, tu_train)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -179,5 +179,7 @@ struct FindLinkRefine {
   const ctr_refine_com* com;
 };
 int ctr_find_link_refine_launch(const FindLinkRefine* d, StageRun* stage, const char** msg);
+// training of shared fit parameters (train_kernels.h; scratch: frame maxima, partials, solver state)
+int ctr_train_launch(const ctr_train* t, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

@@ -88,7 +88,7 @@ def prepare_batch(f, reader, diameter, separation=None, fit_function='gauss',
         raise NotImplementedError(
             "param_mode 'global' couples all features into one problem "
             "(reference refine.py:319-332) and is not supported by the MI355X "
-            "engine")
+            "engine; train_leastsq fits shared parameters with everything else constant")
     if not np.all(modes <= 3):
         raise NotImplementedError("param modes 'particle'/'frame' are not "
                                   "implemented (reference refine.py:339-340)")

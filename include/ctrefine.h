@@ -851,6 +851,105 @@ int ctr_diffusion_ci_device(ctr_handle* h, const ctr_diffusion_ci* d, void* hip_
 int ctr_diffusion_ci_plan(const ctr_diffusion_ci* d, int32_t* rows_in_lds, int64_t* lds_bytes, int64_t* scratch_bytes,
                           int64_t* pairs_per_chunk);
 
+/* Training of shared fit parameters on the device: what the reference's train_leastsq
+ * (refine.py:455-515) asks of refine_leastsq -- positions, signal and background constant, the
+ * size column(s) and the profile's own parameters fitted as ONE value shared by all features
+ * (param_mode 'global').  With every other parameter constant the unknowns of a
+ * problem are its G shared values alone (1 to 8), the windows never move, and the objective is a
+ * sum over clusters.  General global mode (per-feature variables beside shared ones: an arrowhead
+ * system over all clusters) stays refused by ctr_validate_problem.
+ * A call holds P independent problems; problem p owns the clusters [problem_offset[p],
+ * problem_offset[p + 1]), cluster c the features [feat_offset[c], feat_offset[c + 1]) of `params`
+ * and the frame frame_index[c].  For one problem:
+ *   objective: F(g) = (1 / norm) sum_c (1 / P_c) sum_{pixels of c} (I - bg_c - sum_{i in c, pixel in
+ *     mask_i} s_i f(r2_i(g), g))^2 (fitfunc.py:436-450): bg_c the background of the cluster's first
+ *     feature; a pixel whose residual is NaN (a NaN pixel; ring and disc within one pixel of a
+ *     centre, fitfunc.py:20-26) is left out of the sum and still counts in P_c (np.nansum);
+ *   windows and masks: those of ctr_refine_batch to the letter -- the union window of the cluster
+ *     from the centres rounded half to even, the centres beyond the frame by more than the radius
+ *     left out, clipped to the frame (masks.py:42-68); a feature counts only inside its own mask
+ *     sum(((idx - (c - origin)) / radius)^2) <= 1 on the unrounded centre, evaluated without
+ *     contraction at the boundary; P_c = the pixels of the window inside any mask;
+ *   norm = (max over the frames of the problem's clusters of frame.max())^2 / residual_factor
+ *     (refine.py:325-331): ONE maximum for the problem, not one per frame; a NaN maximum is passed
+ *     over, as Python's max(norm, nan) does;
+ *   variables, in the order of the columns: every column with mode CTR_MODE_GLOBAL.  Only the size
+ *     column(s) and the profile's columns may be global, every other mode must be CTR_MODE_CONST
+ *     (else CTR_ERR_UNSUPPORTED), and at least one column is global;
+ *   start, low, high [P, G] are the caller's: the mean of the column over the problem's features
+ *     (refine.py:361), the minimum of the per-feature lower and the maximum of the per-feature upper
+ *     bounds of fitfunc.py:535-558; the start is clipped into the box; low > high fails the problem;
+ *   one window round: the positions are constant (refine.py:384 breaks at once);
+ *   minimiser: the engine's bounded Levenberg-Marquardt on the G variables with the
+ *     Gauss-Newton matrix: active set on the box, (J^T J + mu diag(J^T J)) d = -g on the free
+ *     variables, projection, predicted decrease, trial evaluation, Nielsen's update; mu0 = 1 (a size
+ *     is always among the variables); converged at a relative step <= xtol after an accepted step or
+ *     |predicted decrease| <= ftol F / 2; at most solver_maxiter iterations, where a last accepted
+ *     step that lowered F by less than 1e-9 (relative) still counts as converged; an evaluation
+ *     with a size of 0 is not valid and is rejected; a trial whose F equals the accepted point's to
+ *     within 16 units in the last place is accepted where its projected gradient is the smaller
+ *     (the decrease of F drops below the rounding of its sum before the gradient does);
+ *   result: globals[p, :] the G values, cost[p] = sqrt(F / residual_factor), n_iter[p] the
+ *     iterations, status[p] a CTR_STATUS_*: NONFINITE a non-finite entry in the parameters of the
+ *     problem's features, OUT_OF_BOUNDS a cluster without a pixel (no centre near the frame; also a
+ *     problem without clusters and a frame_index beyond the frames), NO_CONVERGENCE, RMS_DEV
+ *     cost > max_rms_dev, TOO_LARGE a cluster of more than 64 features.  A failed problem has NaN
+ *     globals and cost; it never stops a kernel and leaves the other problems' bytes as they are.
+ * Per iteration two kernels run on the stream: one workgroup per cluster sums the weighted J^T J,
+ * J^T r and r^2 of its pixels at the trial point in float64 and reduces them, lanes then wavefronts in
+ * a fixed order, into its row of a table; one workgroup per problem adds the rows of its clusters
+ * in a fixed order and does the bookkeeping of the iteration.  No floating-point atomics, no
+ * workgroup waits for another: the same bytes on any stream, alone and in any batch.  The
+ * workgroups of a finished problem return at once.
+ * check_every = 0: solver_maxiter + 1 iterations are queued blind and the call is asynchronous.
+ * check_every = K > 0: the host reads one word every K iterations and stops queueing when every
+ * problem has finished; the call then returns with the stream synchronised.  Same results.
+ * problem_offset must rise from 0 to C (problem_offset[p] <= problem_offset[p + 1]): the device checks
+ * each problem's own range, not that the ranges of different problems are disjoint; overlapping
+ * ranges give undefined globals with a status of OK.
+ * max_features is the caller's statement of the largest cluster (the host cannot read
+ * feat_offset): more than 64 is CTR_ERR_UNSUPPORTED; the device checks every cluster again.
+ * Scratch (the table, the solver state, the frame maxima) belongs to the handle: calls of one
+ * handle are ordered on the device whatever streams they are given.
+ * The descriptor is checked before the handle, as for ctr_characterize_device.
+ * Device pointers; asynchronous on `hip_stream` (NULL = the handle's stream) unless check_every. */
+#define CTR_TRAIN_MAX_GLOBALS 8
+#define CTR_TRAIN_MAX_FEATURES 64
+typedef struct ctr_train {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t isotropic;               /* 1: one 'size' column; 0: one per axis */
+  int32_t fit_function;            /* CTR_FIT_* */
+  int32_t n_params;                /* as ctr_problem.n_params */
+  int32_t modes[CTR_MAX_PARAMS];   /* CTR_MODE_CONST or CTR_MODE_GLOBAL per column */
+  int32_t radius[CTR_MAX_NDIM];    /* mask radius per axis, >= 1 */
+  int32_t frame_dtype;             /* CTR_DTYPE_* */
+  int32_t solver_maxiter;          /* 1 .. 10000 (refine.py:243; default 100) */
+  int32_t max_features;            /* features of the largest cluster, <= CTR_TRAIN_MAX_FEATURES */
+  int32_t check_every;             /* 0, or iterations between two looks at the finished count */
+  int64_t n_frames;
+  int64_t shape[CTR_MAX_NDIM];     /* (z,) y, x */
+  int64_t n_problems;              /* P */
+  int64_t n_clusters;              /* C */
+  int64_t n_features;              /* N */
+  double residual_factor;          /* > 0 (default 1e5) */
+  double max_rms_dev;              /* refine.py:391 (default 1) */
+  double xtol;                     /* <= 0 -> 1e-9 */
+  double ftol;                     /* <= 0 -> 1e-14 */
+  const void* frames;              /* [n_frames, *shape] */
+  const double* params;            /* [N, n_params] */
+  const int32_t* feat_offset;      /* [C + 1] */
+  const int32_t* frame_index;      /* [C] */
+  const int32_t* problem_offset;   /* [P + 1] offsets into the clusters */
+  const double* start;             /* [P, G] */
+  const double* low;               /* [P, G], -inf = none */
+  const double* high;              /* [P, G], +inf = none */
+  double* globals;                 /* [P, G] out */
+  double* cost;                    /* [P] out */
+  int32_t* status;                 /* [P] out */
+  int32_t* n_iter;                 /* [P] out */
+} ctr_train;
+int ctr_train_device(ctr_handle* h, const ctr_train* t, void* hip_stream);
+
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
  * several batches in flight hand finished batches on (e.g. to the result gather) from the host
