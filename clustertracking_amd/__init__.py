@@ -18,6 +18,7 @@ from .fitfunc import FitFunctions
 from .utils import ArrayReader, RefineException
 from . import constraints, artificial, link, motion, motion_ci, preprocessing
 from .motion_ci import diffusion_tensor_ci, bootstrap_indices
+from .cluster_tracks import cluster_tracks, cluster_tracks_arrays, track_positions, track_positions_arrays
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -26,7 +27,8 @@ __all__ = ['refine_leastsq', 'train_leastsq', 'train_arrays', 'find_clusters', '
            'characterize', 'characterize_arrays', 'locate', 'relocate_arrays', 'relocate_candidates', 'find_link', 'find_link_arrays', 'refine_com', 'refine_com_arrays', 'lowpass', 'bandpass', 'preprocess', 'preprocessing',
            'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'link_arrays', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',
-           'write_back', 'motion', 'motion_ci', 'diffusion_tensor_ci', 'bootstrap_indices']
+           'write_back', 'motion', 'motion_ci', 'diffusion_tensor_ci', 'bootstrap_indices',
+           'cluster_tracks', 'cluster_tracks_arrays', 'track_positions', 'track_positions_arrays']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

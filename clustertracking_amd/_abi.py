@@ -236,6 +236,32 @@ class Train(C.Structure):
     ]
 
 
+TRACKS_PAIRS, TRACKS_COMPONENTS = 0, 1                        # ctr_cluster_tracks.phase
+TRACKS_OK, TRACKS_BAD_TABLE, TRACKS_ROUNDS = 0, 1, 2           # status[0] of both calls
+TRACKS_NO_KEY = 0x7fffffffffffffff
+
+
+class ClusterTracks(C.Structure):
+    """``ctr_cluster_tracks`` (include/ctrefine.h): which particles form one cluster over time."""
+    _fields_ = [
+        ('phase', C.c_int32), ('cluster_size', C.c_int32), ('check_every', C.c_int32), ('reserved0', C.c_int32),
+        ('min_frames', C.c_int64), ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64),
+        ('frame_offset', C.c_void_p), ('particle', C.c_void_p), ('cluster', C.c_void_p), ('keys', C.c_void_p),
+        ('track_of_particle', C.c_void_p), ('n_tracks', C.c_void_p), ('n_members', C.c_void_p),
+        ('status', C.c_void_p), ('n_rounds', C.c_void_p),
+    ]
+
+
+class TrackPositions(C.Structure):
+    """``ctr_track_positions`` (include/ctrefine.h): the dense block of tracked clusters."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('cluster_size', C.c_int32), ('n_frames', C.c_int64), ('n_features', C.c_int64),
+        ('n_particles', C.c_int64), ('n_tracks', C.c_int64),
+        ('frame_offset', C.c_void_p), ('particle', C.c_void_p), ('track_of_particle', C.c_void_p),
+        ('pos', C.c_void_p), ('present', C.c_void_p), ('pos_out', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
 class Orientation(C.Structure):
     """``ctr_orientation`` (include/ctrefine.h): orientation of tracked clusters on the device."""
     _fields_ = [

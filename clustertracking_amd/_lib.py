@@ -52,6 +52,9 @@ SIGNATURES = {
     'ctr_find_link_device': _stage(_abi.FindLink),
     'ctr_refine_com_device': _stage(_abi.RefineCom),
     'ctr_train_device': _stage(_abi.Train),
+    'ctr_cluster_tracks_device': _stage(_abi.ClusterTracks),
+    'ctr_cluster_tracks_plan': (C.c_int, [_P(_abi.ClusterTracks), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
+    'ctr_track_positions_device': _stage(_abi.TrackPositions),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
     'ctr_diffusion_ci_device': _stage(_abi.DiffusionCI),
     'ctr_diffusion_ci_plan': (C.c_int, [_P(_abi.DiffusionCI), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
@@ -157,6 +160,18 @@ def diffusion_ci_plan(desc):
         msg = (lib.ctr_last_error(None) or b'').decode()
         raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
     return bool(in_lds.value), lds.value, scratch.value, chunk.value
+
+
+def cluster_tracks_plan(desc):
+    """``(scratch_bytes, max_rounds, jumps_per_round)`` of a ``ctr_cluster_tracks_device`` call
+    (``ctr_cluster_tracks_plan``, no device needed); ``ValueError`` / ``NotImplementedError`` as the call itself."""
+    lib = load()
+    scratch, rounds, jumps = C.c_int64(), C.c_int32(), C.c_int32()
+    rc = lib.ctr_cluster_tracks_plan(C.byref(desc), C.byref(scratch), C.byref(rounds), C.byref(jumps))
+    if rc != _abi.OK:
+        msg = (lib.ctr_last_error(None) or b'').decode()
+        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
+    return scratch.value, rounds.value, jumps.value
 
 
 class Engine(object):
@@ -345,7 +360,9 @@ for _name, _symbol, _too_large in (
         ('relocate_device', 'ctr_relocate_device', False),
         ('find_link_device', 'ctr_find_link_device', False),
         ('refine_com_device', 'ctr_refine_com_device', False),
-        ('train_device', 'ctr_train_device', False)):
+        ('train_device', 'ctr_train_device', False),
+        ('cluster_tracks_device', 'ctr_cluster_tracks_device', False),
+        ('track_positions_device', 'ctr_track_positions_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 
 

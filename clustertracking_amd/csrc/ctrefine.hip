@@ -117,6 +117,7 @@ struct ctr_handle {
   // ctr_link_device, ctr_find_link_device and ctr_find_link_refine_device; ctr_diffusion_device and ctr_diffusion_ci_device (partial sums, rows, statistics)
   Scratch link, motion;
   Scratch train;   // ctr_train_device: frame maxima, partial sums, solver state
+  Scratch tracks;  // ctr_cluster_tracks_device: labels, member counts, the words of the rounds
 };
 
 namespace {
@@ -475,7 +476,7 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1052,6 +1053,27 @@ int ctr_refine_com_device(ctr_handle* h, const ctr_refine_com* c, void* hip_stre
 
 int ctr_train_device(ctr_handle* h, const ctr_train* t, void* hip_stream) {
   return run_stage("ctr_train_device", h, &ctr_handle::train, t, hip_stream, ctr_train_launch);
+}
+
+int ctr_cluster_tracks_device(ctr_handle* h, const ctr_cluster_tracks* c, void* hip_stream) {
+  return run_stage("ctr_cluster_tracks_device", h, &ctr_handle::tracks, c, hip_stream, ctr_cluster_tracks_launch);
+}
+
+int ctr_cluster_tracks_plan(const ctr_cluster_tracks* c, int64_t* scratch_bytes, int32_t* max_rounds,
+                            int32_t* jumps_per_round) {
+  const char* msg = "";
+  ctr_tracks_plan plan = {};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  const int rc = ctr_cluster_tracks_launch(c, &run, &msg, &plan);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_cluster_tracks_plan: ") + msg);
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  if (max_rounds) *max_rounds = plan.max_rounds;
+  if (jumps_per_round) *jumps_per_round = plan.jumps_per_round;
+  return CTR_OK;
+}
+
+int ctr_track_positions_device(ctr_handle* h, const ctr_track_positions* p, void* hip_stream) {
+  return run_stage("ctr_track_positions_device", h, nullptr, p, hip_stream, ctr_track_positions_launch);
 }
 
 int ctr_find_link_refine_device(ctr_handle* h, const ctr_find_link* f, const ctr_refine_com* com, void* hip_stream) {

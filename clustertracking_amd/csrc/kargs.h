@@ -122,7 +122,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
-// tu_refine_com, tu_train)
+// tu_refine_com, tu_train, tu_cluster_tracks)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -181,5 +181,13 @@ struct FindLinkRefine {
 int ctr_find_link_refine_launch(const FindLinkRefine* d, StageRun* stage, const char** msg);
 // training of shared fit parameters (train_kernels.h; scratch: frame maxima, partials, solver state)
 int ctr_train_launch(const ctr_train* t, StageRun* stage, const char** msg);
+// cluster tracks (cluster_track_kernels.h; scratch: labels, member counts, the words of the rounds):
+// the round bound goes to *plan (may be null)
+struct ctr_tracks_plan {
+  long long scratch_bytes;
+  int max_rounds, jumps_per_round;
+};
+int ctr_cluster_tracks_launch(const ctr_cluster_tracks* c, StageRun* stage, const char** msg, ctr_tracks_plan* plan);
+int ctr_track_positions_launch(const ctr_track_positions* p, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

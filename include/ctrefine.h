@@ -950,6 +950,114 @@ typedef struct ctr_train {
 } ctr_train;
 int ctr_train_device(ctr_handle* h, const ctr_train* t, void* hip_stream);
 
+/* ---- cluster tracks: which particles form one cluster over time (ABI 8, additions) ----
+ * The step between the linker and the motion stage: ctr_link_device / ctr_find_link_device give every
+ * feature a `particle`, ctr_find_clusters labels the clusters of each frame, ctr_orientation_device
+ * takes a dense block of tracked clusters.  The rule is this project's own (the reference's
+ * orientation_df assumes one cluster per table, motion.py:146-162); tests/_cluster_tracks.py restates
+ * it in NumPy / SciPy.
+ * Input: N rows sorted by frame; frame_offset [T + 1] (0 <= off[t] <= off[t + 1] <= N, rows [off[t],
+ * off[t + 1]) are frame t; a row in no frame is passed over); particle [N], dense ids 0 .. P - 1, a
+ * negative id is an unlinked row; cluster [N], any integers: equal within a frame means the same
+ * cluster, the values need not be unique across frames; pos [N, ndim]; cluster_size in {2, 3, 4};
+ * min_frames >= 1.
+ *   1. complete group: the rows of one frame with the same `cluster` value form a complete group when
+ *      there are exactly cluster_size of them, all with particle >= 0 and pairwise different
+ *      particles.  A group of any other size is no evidence (two dimers that touch in a frame form a
+ *      group of four and bond nothing).
+ *   2. bond: b(p, q) = the number of frames in which p and q share a complete group; p and q are
+ *      bonded iff b(p, q) >= min_frames.
+ *   3. track: the connected components of the bond graph with at least two particles, numbered
+ *      0 .. n_tracks - 1 by ascending smallest particle id.  track_of_particle [P] is that number, -1
+ *      for every other particle; n_members [n_tracks] the size of the component (it can exceed
+ *      cluster_size where the linker lost a feature and gave it a new id: A-B, later A-B', is one
+ *      track of three members).
+ *   4. positions: for track k and frame t take the rows of frame t whose particle is a member of k,
+ *      whatever their `cluster` value.  present [n_tracks, T] is their count.  Where it equals
+ *      cluster_size, pos_out[k, t, j, :] is the position of the j-th of them in ascending order of
+ *      (particle, row); anywhere else all of pos_out[k, t] is NaN.  present < cluster_size is an
+ *      incomplete frame, present > cluster_size a conflict; nothing is chosen at random.
+ * Integers and copies of doubles: the same bytes on every run and stream.
+ *
+ * ctr_cluster_tracks_device has two phases with the caller's sort between them:
+ *   CTR_TRACKS_PAIRS: a kernel checks the tables (frame_offset as above, particle < P) before any
+ *     other follows an index; a failed check gives status[0] = CTR_TRACKS_BAD_TABLE and no key.  One
+ *     workgroup per frame: every row finds its group's size, whether it is complete and its rank by
+ *     particle, and writes into keys[row (cluster_size - 1) ...] one key (lo << 32 | hi), lo < hi, per
+ *     member of higher rank -- cluster_size (cluster_size - 1) / 2 per complete group -- and
+ *     CTR_TRACKS_NO_KEY into every other slot.
+ *   The caller sorts keys [N (cluster_size - 1)] ascending (any device sort; equal keys must be
+ *     adjacent, nothing more is used).
+ *   CTR_TRACKS_COMPONENTS: slot e is an edge where it starts a run of equal keys (keys[e - 1] differs),
+ *     keys[e + min_frames - 1] == keys[e] and both ids are below P.  Components by hooking to the smaller label and pointer jumping: a round is one hook
+ *     kernel (every edge between two trees hangs the root with the larger id under the smaller, by
+ *     atomicMin, reading the labels of the round's start) and up to J = ceil(log2 P) + 1 jump kernels
+ *     (label = label of label) that flatten every tree to a star.  A tree with an edge to another
+ *     tree is merged with one within two rounds, so R = 2 ceil(log2 P) + 2 rounds suffice
+ *     (ctr_cluster_tracks_plan gives R and J).  Kernel boundaries are the only synchronisation
+ *     between workgroups; a kernel that has nothing left to do returns at its first load.
+ *     check_every = 0: the R rounds are queued blind and the call is asynchronous; K > 0: the host
+ *     reads one word every K rounds and stops queueing after a round that hooked nothing; the call
+ *     then returns with the stream synchronised.  Same bytes.  A last kernel verifies that a further
+ *     round would change nothing; if it would, status[0] = CTR_TRACKS_ROUNDS and no track is given.
+ *     Then the roots with at least two members are numbered in ascending order (block counts, their
+ *     scan, ranks) and track_of_particle, n_tracks, n_members and n_rounds (the rounds that hooked
+ *     anything; may be null) are written.  status[0] is the PAIRS phase's and is not reset: a refused
+ *     table gives n_tracks = 0 and -1 everywhere.
+ * ctr_track_positions_device: a kernel checks the tables again (and track_of_particle < n_tracks);
+ * status[0] = CTR_TRACKS_BAD_TABLE leaves present 0 and pos_out NaN.  present by one integer
+ * atomicAdd per member row; pos_out by a NaN fill and a scatter by rank, one workgroup per frame.
+ * n_tracks is the only number the host needs between the two calls.
+ * Scratch of ctr_cluster_tracks_device belongs to the handle: calls of one handle are ordered on
+ * the device whatever streams they are given.  Descriptors are checked before the handle, as for
+ * ctr_characterize_device.  Device pointers; asynchronous on `hip_stream` unless check_every. */
+#define CTR_TRACKS_PAIRS 0
+#define CTR_TRACKS_COMPONENTS 1
+#define CTR_TRACKS_OK 0
+#define CTR_TRACKS_BAD_TABLE 1
+#define CTR_TRACKS_ROUNDS 2
+#define CTR_TRACKS_NO_KEY 0x7fffffffffffffffLL
+typedef struct ctr_cluster_tracks {
+  int32_t phase;                   /* CTR_TRACKS_PAIRS or CTR_TRACKS_COMPONENTS */
+  int32_t cluster_size;            /* 2, 3 or 4 */
+  int32_t check_every;             /* COMPONENTS: 0, or rounds between two looks at the hook word */
+  int32_t reserved0;
+  int64_t min_frames;              /* >= 1 */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P <= 2^31 - 2 */
+  const int64_t* frame_offset;     /* [T + 1]  (PAIRS) */
+  const int64_t* particle;         /* [N]      (PAIRS) */
+  const int64_t* cluster;          /* [N]      (PAIRS) */
+  int64_t* keys;                   /* [N (cluster_size - 1)]: PAIRS out; COMPONENTS in, sorted */
+  int32_t* track_of_particle;      /* [P] out          (COMPONENTS) */
+  int32_t* n_tracks;               /* [1] out          (COMPONENTS) */
+  int32_t* n_members;              /* [P / 2] out, the first n_tracks entries (COMPONENTS) */
+  int32_t* status;                 /* [1]: PAIRS out; COMPONENTS in and out */
+  int32_t* n_rounds;               /* [1] out or NULL  (COMPONENTS) */
+} ctr_cluster_tracks;
+int ctr_cluster_tracks_device(ctr_handle* h, const ctr_cluster_tracks* c, void* hip_stream);
+/* No device needed: the scratch of the call, its round bound R and the jump kernels per round J. */
+int ctr_cluster_tracks_plan(const ctr_cluster_tracks* c, int64_t* scratch_bytes, int32_t* max_rounds,
+                            int32_t* jumps_per_round);
+
+typedef struct ctr_track_positions {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t cluster_size;            /* 2, 3 or 4 */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P */
+  int64_t n_tracks;                /* n_tracks[0] of ctr_cluster_tracks_device */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const int64_t* particle;         /* [N] */
+  const int32_t* track_of_particle;/* [P] */
+  const double* pos;               /* [N, ndim] */
+  int32_t* present;                /* [n_tracks, T] out */
+  double* pos_out;                 /* [n_tracks, T, cluster_size, ndim] out */
+  int32_t* status;                 /* [1] out */
+} ctr_track_positions;
+int ctr_track_positions_device(ctr_handle* h, const ctr_track_positions* p, void* hip_stream);
+
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
  * several batches in flight hand finished batches on (e.g. to the result gather) from the host
