@@ -6,7 +6,7 @@ for the part of it that this engine accelerates.
 """
 import logging
 
-from .refine import refine_leastsq, prepare_batch, write_back
+from .refine import refine_leastsq, refine_arrays, prepare_batch, write_back
 from .find import (find_clusters, grey_dilation, locate_maxima, percentile_threshold,
                    where_close, drop_close, characterize, characterize_arrays, locate)
 from .preprocessing import lowpass, bandpass, preprocess
@@ -23,7 +23,7 @@ from .cluster_tracks import cluster_tracks, cluster_tracks_arrays, track_positio
 link_df = link.link
 link_arrays = link.link_arrays
 
-__all__ = ['refine_leastsq', 'train_leastsq', 'train_arrays', 'find_clusters', 'grey_dilation', 'locate_maxima',
+__all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', 'find_clusters', 'grey_dilation', 'locate_maxima',
            'characterize', 'characterize_arrays', 'locate', 'relocate_arrays', 'relocate_candidates', 'find_link', 'find_link_arrays', 'refine_com', 'refine_com_arrays', 'lowpass', 'bandpass', 'preprocess', 'preprocessing',
            'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'link_arrays', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',

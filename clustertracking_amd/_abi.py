@@ -262,6 +262,29 @@ class TrackPositions(C.Structure):
     ]
 
 
+PREPARE_BATCH, PREPARE_SCATTER = 0, 1                          # ctr_refine_prepare.mode
+PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
+
+
+class RefinePrepare(C.Structure):
+    """``ctr_refine_prepare`` (include/ctrefine.h): a refine batch from device tables, and the
+    scatter of its results into input row order."""
+    _fields_ = [
+        ('mode', C.c_int32), ('ndim', C.c_int32), ('n_params', C.c_int32), ('reserved0', C.c_int32),
+        ('modes', C.c_int32 * MAX_PARAMS),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_clusters', C.c_int64),
+        ('separation', C.c_double * MAX_NDIM),
+        ('bound_abs', C.c_double * (2 * MAX_PARAMS)), ('bound_diff', C.c_double * (2 * MAX_PARAMS)),
+        ('bound_rel', C.c_double * (2 * MAX_PARAMS)),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('params0', C.c_void_p),
+        ('label', C.c_void_p), ('cluster_size', C.c_void_p), ('order', C.c_void_p),
+        ('feat_offset', C.c_void_p), ('frame_index', C.c_void_p), ('n_clusters_out', C.c_void_p),
+        ('params', C.c_void_p), ('low', C.c_void_p), ('high', C.c_void_p), ('status', C.c_void_p),
+        ('fit_params', C.c_void_p), ('fit_cost', C.c_void_p), ('fit_std', C.c_void_p),
+        ('params_out', C.c_void_p), ('cost_out', C.c_void_p), ('std_out', C.c_void_p),
+    ]
+
+
 class Orientation(C.Structure):
     """``ctr_orientation`` (include/ctrefine.h): orientation of tracked clusters on the device."""
     _fields_ = [

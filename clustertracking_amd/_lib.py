@@ -55,6 +55,8 @@ SIGNATURES = {
     'ctr_cluster_tracks_device': _stage(_abi.ClusterTracks),
     'ctr_cluster_tracks_plan': (C.c_int, [_P(_abi.ClusterTracks), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
     'ctr_track_positions_device': _stage(_abi.TrackPositions),
+    'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
+    'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
     'ctr_diffusion_ci_device': _stage(_abi.DiffusionCI),
     'ctr_diffusion_ci_plan': (C.c_int, [_P(_abi.DiffusionCI), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
@@ -172,6 +174,18 @@ def cluster_tracks_plan(desc):
         msg = (lib.ctr_last_error(None) or b'').decode()
         raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
     return scratch.value, rounds.value, jumps.value
+
+
+def refine_prepare_plan(desc):
+    """Scratch bytes of a ``ctr_refine_prepare_device`` call (``ctr_refine_prepare_plan``, no device
+    needed); ``ValueError`` / ``NotImplementedError`` as the call itself."""
+    lib = load()
+    scratch = C.c_int64()
+    rc = lib.ctr_refine_prepare_plan(C.byref(desc), C.byref(scratch))
+    if rc != _abi.OK:
+        msg = (lib.ctr_last_error(None) or b'').decode()
+        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
+    return scratch.value
 
 
 class Engine(object):
@@ -362,7 +376,8 @@ for _name, _symbol, _too_large in (
         ('refine_com_device', 'ctr_refine_com_device', False),
         ('train_device', 'ctr_train_device', False),
         ('cluster_tracks_device', 'ctr_cluster_tracks_device', False),
-        ('track_positions_device', 'ctr_track_positions_device', False)):
+        ('track_positions_device', 'ctr_track_positions_device', False),
+        ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 
 

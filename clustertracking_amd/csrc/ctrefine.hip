@@ -118,6 +118,7 @@ struct ctr_handle {
   Scratch link, motion;
   Scratch train;   // ctr_train_device: frame maxima, partial sums, solver state
   Scratch tracks;  // ctr_cluster_tracks_device: labels, member counts, the words of the rounds
+  Scratch prepare; // ctr_refine_prepare_device: scaled positions, member counts, ranks, clusters per frame
 };
 
 namespace {
@@ -476,7 +477,7 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1074,6 +1075,22 @@ int ctr_cluster_tracks_plan(const ctr_cluster_tracks* c, int64_t* scratch_bytes,
 
 int ctr_track_positions_device(ctr_handle* h, const ctr_track_positions* p, void* hip_stream) {
   return run_stage("ctr_track_positions_device", h, nullptr, p, hip_stream, ctr_track_positions_launch);
+}
+
+int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream) {
+  // the scatter has no scratch: it is not ordered with the handle's other calls
+  Scratch ctr_handle::*scratch = r && r->mode == CTR_PREPARE_SCATTER ? nullptr : &ctr_handle::prepare;
+  return run_stage("ctr_refine_prepare_device", h, scratch, r, hip_stream, ctr_refine_prepare_launch);
+}
+
+int ctr_refine_prepare_plan(const ctr_refine_prepare* r, int64_t* scratch_bytes) {
+  const char* msg = "";
+  long long bytes = 0;
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  const int rc = ctr_refine_prepare_launch(r, &run, &msg, &bytes);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_refine_prepare_plan: ") + msg);
+  if (scratch_bytes) *scratch_bytes = bytes;
+  return CTR_OK;
 }
 
 int ctr_find_link_refine_device(ctr_handle* h, const ctr_find_link* f, const ctr_refine_com* com, void* hip_stream) {

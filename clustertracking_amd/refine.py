@@ -7,6 +7,7 @@ parameter columns :299-305, bounds templates :315, and the DataFrame output
 objective, minimiser, re-window rounds, failure rules) is ONE batched call into
 the HIP engine through the C-ABI of ``include/ctrefine.h``.
 """
+import collections
 import logging
 
 import numpy as np
@@ -15,6 +16,7 @@ from . import _abi
 from .constraints import engine_constraint
 from .find import find_clusters
 from .fitfunc import FitFunctions
+from .motion import _is_tensor
 from .utils import (ArrayReader, guess_pos_columns, is_isotropic,
                     validate_tuple)
 
@@ -62,17 +64,9 @@ def _normalise_reader(f, reader, t_column):
     return {frame_no: reader}, ndim, False
 
 
-def prepare_batch(f, reader, diameter, separation=None, fit_function='gauss',
-                  param_mode=None, param_val=None, constraints=None, bounds=None,
-                  pos_columns=None, t_column='frame', max_iter=10, max_shift=1,
-                  max_rms_dev=1., residual_factor=100000., solver_maxiter=100,
-                  xtol=0., ftol=0., cluster_labels='reference', device=0,
-                  compute_error=False, noise_size=None, threshold=None):
-    """Host-side set-up of one refine call (reference refine.py:242-341)."""
-    if pos_columns is None:
-        pos_columns = guess_pos_columns(f)
-    frames_src, ndim, _ = _normalise_reader(f, reader, t_column)
-    assert ndim == len(pos_columns)
+def _check_options(ndim, diameter, separation, fit_function, param_mode, constraints, max_iter):
+    """What ``prepare_batch`` and ``refine_arrays`` refuse before any work, and the model they agree
+    on: ``(diameter, radius, isotropic, separation, ff, cons)``."""
     if int(max_iter) < 1:
         raise ValueError("max_iter must be at least 1")
 
@@ -93,6 +87,22 @@ def prepare_batch(f, reader, diameter, separation=None, fit_function='gauss',
         raise NotImplementedError("param modes 'particle'/'frame' are not "
                                   "implemented (reference refine.py:339-340)")
     cons = engine_constraint(constraints, ndim)
+    return diameter, radius, isotropic, separation, ff, cons
+
+
+def prepare_batch(f, reader, diameter, separation=None, fit_function='gauss',
+                  param_mode=None, param_val=None, constraints=None, bounds=None,
+                  pos_columns=None, t_column='frame', max_iter=10, max_shift=1,
+                  max_rms_dev=1., residual_factor=100000., solver_maxiter=100,
+                  xtol=0., ftol=0., cluster_labels='reference', device=0,
+                  compute_error=False, noise_size=None, threshold=None):
+    """Host-side set-up of one refine call (reference refine.py:242-341)."""
+    if pos_columns is None:
+        pos_columns = guess_pos_columns(f)
+    frames_src, ndim, _ = _normalise_reader(f, reader, t_column)
+    assert ndim == len(pos_columns)
+    diameter, radius, isotropic, separation, ff, cons = _check_options(
+        ndim, diameter, separation, fit_function, param_mode, constraints, max_iter)
     f = find_clusters(f, separation, pos_columns, t_column, labels=cluster_labels,
                       device=device)  # makes a copy
     if param_val is not None:
@@ -255,3 +265,260 @@ def refine_leastsq(f, reader, diameter, separation=None, fit_function='gauss',
     if prep.batch.n_clusters:
         _run_on_engine(prep.problem, prep.batch, device)
     return write_back(prep)
+
+
+RefineResult = collections.namedtuple(
+    'RefineResult', 'params columns cost cluster cluster_size params_std status n_rounds n_iter feat_offset')
+
+
+def _check_tables(frames, pos, frame_offset):
+    """The shapes ``refine_arrays`` refuses before any device work: ``(ndim, n_rows, n_frames)``.
+    The offsets of an ndarray are checked here, those of a tensor by the stage's first kernel."""
+    ndim = len(frames.shape) - 1
+    if ndim not in (2, 3):
+        raise ValueError("frames must be [T, (z,) y, x], not an array of %d dimensions" % len(frames.shape))
+    if len(pos.shape) != 2 or pos.shape[1] != ndim:
+        raise ValueError("pos must be [N, %d], not %s" % (ndim, tuple(pos.shape)))
+    n, n_frames = int(pos.shape[0]), int(frames.shape[0])
+    if n >= 2 ** 31 - 1:
+        raise ValueError("%d rows: one call takes fewer than 2**31 - 1" % n)
+    if len(frame_offset.shape) != 1 or frame_offset.shape[0] != n_frames + 1:
+        raise ValueError("frame_offset must have one entry per frame and one more (%d), not %s"
+                         % (n_frames + 1, tuple(frame_offset.shape)))
+    if not _is_tensor(frame_offset):
+        if frame_offset.dtype.kind not in 'iu':
+            raise ValueError("frame_offset must hold integers, not %s" % frame_offset.dtype)
+        if frame_offset[0] != 0 or frame_offset[-1] != n or np.any(np.diff(frame_offset.astype(np.int64)) < 0):
+            raise ValueError("frame_offset must not decrease, from 0 to the number of rows (%d)" % n)
+    return ndim, n, n_frames
+
+
+def _start_values(ff, pos_t, columns, n, dev):
+    """``params0`` [N, n_params] on the device from the start columns (scalars, ndarrays, tensors):
+    a handful of column copies."""
+    import torch
+    cols = []
+    for name in ff.params:
+        if name in ff.pos_columns:
+            cols.append(pos_t[:, ff.pos_columns.index(name)])
+            continue
+        v = columns[name]
+        if _is_tensor(v):
+            if v.device != dev:
+                raise ValueError("the %r tensor must be on %s" % (name, dev))
+            v = v.to(torch.float64)
+        else:
+            v = torch.from_numpy(np.array(v, dtype=np.float64)).to(dev)
+        if v.dim() == 0:
+            v = v.expand(n)
+        if v.dim() != 1 or v.shape[0] != n:
+            raise ValueError("%r must be a scalar or have one value per row (%d), not %s" % (name, n, tuple(v.shape)))
+        cols.append(v)
+    return torch.stack(cols, dim=1).contiguous()
+
+
+def _prepare_on_device(eng, dev, pos_t, off_t, params0, separation, ff, templates):
+    """Queue ``ctr_refine_prepare_device`` (CTR_PREPARE_BATCH) on torch's current stream; no
+    synchronisation.  Returns the descriptor and the tensors it names: ``head`` int32 ``[4 + N + 1]``
+    holds ``n_clusters``, ``status[2]``, a pad and ``feat_offset``, so that one copy brings all of
+    them to the host; then label, cluster_size, order, frame_index ``[N]`` and params, low, high."""
+    import torch
+    n, np_, ndim = int(pos_t.shape[0]), ff.n_params, int(pos_t.shape[1])
+    head = torch.empty(4 + n + 1, dtype=torch.int32, device=dev)
+    label, csize, order, frame_index = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+    params, low, high = (torch.empty((n, np_), dtype=torch.float64, device=dev) for _ in range(3))
+    d = _abi.RefinePrepare()
+    d.mode, d.ndim, d.n_params, d.n_frames, d.n_features = _abi.PREPARE_BATCH, ndim, np_, int(off_t.shape[0]) - 1, n
+    for k, m in enumerate(ff.modes):
+        d.modes[k] = int(m)
+    for a in range(ndim):
+        d.separation[a] = float(separation[a])
+    for field, tmpl in zip(('bound_abs', 'bound_diff', 'bound_rel'), templates):
+        arr = getattr(d, field)
+        for row in range(2):
+            for k in range(_abi.MAX_PARAMS):
+                arr[row * _abi.MAX_PARAMS + k] = float(tmpl[row][k]) if k < np_ else np.nan
+    d.pos, d.frame_offset, d.params0 = pos_t.data_ptr() or None, off_t.data_ptr(), params0.data_ptr() or None
+    d.label, d.cluster_size, d.order = label.data_ptr() or None, csize.data_ptr() or None, order.data_ptr() or None
+    d.frame_index = frame_index.data_ptr() or None
+    d.n_clusters_out, d.status, d.feat_offset = head.data_ptr(), head[1:].data_ptr(), head[4:].data_ptr()
+    d.params, d.low, d.high = params.data_ptr() or None, low.data_ptr() or None, high.data_ptr() or None
+    eng.on_current_stream(eng.refine_prepare_device, d, dev=dev)
+    return d, head, label, csize, order, frame_index, params, low, high
+
+
+PreparedArrays = collections.namedtuple(
+    'PreparedArrays', 'label cluster_size order feat_offset frame_index params low high n_clusters status')
+
+
+def prepare_arrays(pos, frame_offset, params0, separation, ff, bounds=None, radius=None, device=0):
+    """The prepare stage of :func:`refine_arrays` alone (``ctr_refine_prepare_device``): pos float64
+    ``[N, ndim]`` in frame order, frame_offset int64 ``[T + 1]``, params0 float64 ``[N, n_params]`` in
+    the column order of ``ff`` (a ``FitFunctions``), ndarrays or tensors on ``cuda:device``; bounds
+    and radius as ``FitFunctions.validate_bounds`` takes them.  Returns ``PreparedArrays`` of
+    tensors on the device -- label, cluster_size, order int32 ``[N]``, feat_offset int32 ``[C + 1]``,
+    frame_index int32 ``[C]``, params, low, high ``[N, n_params]`` in grouped
+    order -- and the ints ``n_clusters`` and ``status = (code, parameter)``: ``_abi.PREPARE_OK``,
+    ``PREPARE_BAD_TABLE`` (offsets that do not rise from 0 to N) or ``PREPARE_INFEASIBLE`` with the
+    index of the parameter.  One synchronisation, at the end."""
+    from . import _lib
+    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
+    import torch
+    dev = torch.device('cuda', device)
+    templates = ff.validate_bounds(bounds, radius=radius)
+    with torch.cuda.device(dev):
+        pos_t, off_t, par_t = (x if _is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=t)).to(dev)
+                               for x, t in ((pos, np.float64), (frame_offset, np.int64), (params0, np.float64)))
+        if pos_t.dim() != 2 or pos_t.shape[1] not in (2, 3) or tuple(par_t.shape) != (pos_t.shape[0], ff.n_params):
+            raise ValueError("pos must be [N, ndim] and params0 [N, %d]" % ff.n_params)
+        separation = validate_tuple(separation, int(pos_t.shape[1]))
+        _, head, label, csize, order, frame_index, params, low, high = _prepare_on_device(
+            eng, dev, pos_t.contiguous(), off_t.contiguous(), par_t.contiguous(), separation, ff, templates)
+        n_clusters, code, bad = (int(v) for v in head[:3].cpu())
+        return PreparedArrays(label, csize, order, head[4:4 + n_clusters + 1], frame_index[:n_clusters], params, low,
+                              high, n_clusters, (code, bad))
+
+
+def refine_arrays(frames, pos, frame_offset, diameter, separation=None, signal=None, size=None,
+                  background=0., fit_function='gauss', param_mode=None, param_val=None,
+                  constraints=None, bounds=None, noise_size=None, threshold=None, max_iter=10,
+                  max_shift=1, max_rms_dev=1., residual_factor=100000., compute_error=False,
+                  options=None, xtol=0., ftol=0., device=0):
+    """:func:`refine_leastsq` on arrays: tensors in, tensors on the device out; NumPy in, NumPy out.
+
+    frames ``[T, (z,) y, x]``; pos float64 ``[N, ndim]``, rows sorted by frame; frame_offset
+    ``[T + 1]`` integers, rows ``[off[t], off[t + 1])`` are frame t -- what ``locate_arrays`` and
+    ``find_link_arrays`` return; ndarrays, or tensors on ``cuda:device``.  signal: a scalar or
+    ``[N]``; size: a scalar, ``[N]`` or, for an anisotropic ``diameter``, ``[N, ndim]``; background as
+    signal; param_val: further columns of ``FitFunctions.params`` (scalars or ``[N]``), which also
+    override the three.  Everything else as :func:`refine_leastsq`, with ``cluster_labels='device'``:
+    the same kernels on the same batch, so the same bytes.
+
+    Returns ``RefineResult(params [N, n_params] and cost [N] in input row order, columns =
+    ff.params, cluster and cluster_size int64 [N] (the smallest row of the row's cluster, as
+    find_clusters(labels='device')), params_std ([N, n_params], NaN where a column is not fitted) or
+    None, status, n_rounds, n_iter int32 [C] per cluster in batch order, feat_offset int32 [C + 1])``.
+    A failed cluster keeps its parameters and has ``cost`` NaN and a non-zero ``status``
+    (``_abi.STATUS_TEXT``); no warning is logged.
+
+    The batch is grouped, bounded and laid out on the device (``ctr_refine_prepare_device``) on
+    torch's current stream.  There is ONE synchronisation with the host, after that stage: the words
+    ``n_clusters`` and ``status`` and the clusters' row ranges come over in one copy of 4 (N + 5)
+    bytes, of which the C + 1 offsets are used, because ``ctr_plan_create`` bins the clusters on the
+    host and sizes the grids from them.  Frames, positions and parameter tables given as tensors never
+    cross PCIe.  The plan (and the large clusters' workspace in it) lives for the call: the stream is
+    synchronised once more before it is destroyed, so the results are complete on return.
+
+    Raises, before any device work: ``NotImplementedError`` for ``param_mode`` 'global', dict fit
+    functions and more than one constraint; ``ValueError`` for ``max_iter < 1``, frames that are not
+    ``[T, (z,) y, x]``, a ``pos`` that is not ``[N, ndim]``, ``N >= 2**31 - 1`` and a ``frame_offset``
+    ndarray that decreases or does not run from 0 to N (a tensor's offsets are checked by the stage's
+    first kernel and refused at the synchronisation).  ``ValueError("SLSQP Error: ...")`` for a lower
+    bound above its upper bound, as ``prepare_batch``.  ``EngineError`` without a library or a GPU."""
+    as_tensor = _is_tensor(pos)
+    if not hasattr(frames, 'shape'):
+        frames = np.asarray(frames)
+    if not as_tensor:
+        pos = np.asarray(pos)
+    if not _is_tensor(frame_offset):
+        frame_offset = np.asarray(frame_offset)
+    ndim, n, n_frames = _check_tables(frames, pos, frame_offset)
+    diameter, radius, isotropic, separation, ff, cons = _check_options(
+        ndim, diameter, separation, fit_function, param_mode, constraints, max_iter)
+    separation = validate_tuple(separation, ndim)
+    if not all(float(s) > 0 and np.isfinite(float(s)) for s in separation):
+        raise ValueError("separation must be positive")
+    solver_maxiter = int(dict(options or {}).get('maxiter', 100))
+    problem = _abi.make_problem(ndim, isotropic, ff.modes, radius, cons, max_iter=max_iter, max_shift=max_shift,
+                                max_rms_dev=max_rms_dev, residual_factor=residual_factor,
+                                solver_maxiter=solver_maxiter, xtol=xtol, ftol=ftol,
+                                noise_size=None if noise_size is None else validate_tuple(noise_size, ndim),
+                                threshold=threshold, fit_function=ff.fit_function)
+    templates = ff.validate_bounds(bounds, radius=radius)
+    columns = dict(background=background)
+    if signal is not None:
+        columns['signal'] = signal
+    if size is not None:
+        if isotropic:
+            columns['size'] = size if len(getattr(size, 'shape', ())) < 2 else size[:, 0]
+        else:
+            for a, col in enumerate(ff.size_columns):
+                columns[col] = size if len(getattr(size, 'shape', ())) < 2 else size[:, a]
+    columns.update(param_val or {})
+    for col in ff.params:
+        if col in ff.default:
+            columns.setdefault(col, ff.default[col])
+    for col in ff.params:
+        if col not in columns and col not in ff.pos_columns:
+            raise ValueError("no start value for %r: give it as an argument or in param_val" % col)
+
+    from . import _lib
+    from .find import _device_frames
+    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
+    import torch
+    if not _is_tensor(frames) and frames.dtype not in _abi.DTYPE_CODES:
+        frames = frames.astype(np.float64)     # as HostBatch: refine.py:58
+    frames_t, pix = _device_frames(frames, device, None)
+    dev = frames_t.device
+    np_ = ff.n_params
+    with torch.cuda.device(dev):
+        if as_tensor:
+            if pos.device != dev or pos.dtype != torch.float64:
+                raise ValueError("a pos tensor is float64 on %s" % dev)
+            pos_t = pos.contiguous()
+        else:
+            pos_t = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.float64)).to(dev)
+        if _is_tensor(frame_offset):
+            if frame_offset.device != dev or frame_offset.dtype != torch.int64:
+                raise ValueError("a frame_offset tensor is int64 on %s" % dev)
+            off_t = frame_offset.contiguous()
+        else:
+            off_t = torch.from_numpy(np.ascontiguousarray(frame_offset, dtype=np.int64)).to(dev)
+        params0 = _start_values(ff, pos_t, columns, n, dev)
+
+        d, head, label, csize, order, frame_index, params, low, high = _prepare_on_device(
+            eng, dev, pos_t, off_t, params0, separation, ff, templates)
+        head_host = head.cpu().numpy()          # the one synchronisation
+        n_clusters, code, bad_param = (int(v) for v in head_host[:3])
+        if code == _abi.PREPARE_BAD_TABLE:
+            raise ValueError("frame_offset must not decrease, from 0 to the number of rows (%d)" % n)
+        if code == _abi.PREPARE_INFEASIBLE:
+            raise ValueError("SLSQP Error: the lower bound exceeds the "
+                             "upper bound (parameter %r)" % ff.params[bad_param])
+        feat_offset = head[4:4 + n_clusters + 1]
+
+        params_out = params0.clone()
+        cost = torch.full((n,), np.nan, dtype=torch.float64, device=dev)
+        std = torch.full((n, np_), np.nan, dtype=torch.float64, device=dev) if compute_error else None
+        cl_status, n_rounds, n_iter = (torch.zeros(n_clusters, dtype=torch.int32, device=dev) for _ in range(3))
+        if n_clusters:
+            plan = eng.plan(problem, head_host[4:4 + n_clusters + 1])
+            try:
+                fit = torch.empty((n, np_), dtype=torch.float64, device=dev)
+                fit_cost = torch.empty(n_clusters, dtype=torch.float64, device=dev)
+                fit_std = torch.empty((n, np_), dtype=torch.float64, device=dev) if compute_error else None
+                b = _abi.Batch()
+                b.frames, b.frame_dtype, b.n_frames = frames_t.data_ptr(), _abi.DTYPE_CODES[np.dtype(pix)], n_frames
+                for a in range(ndim):
+                    b.shape[a] = int(frames_t.shape[1 + a])
+                b.n_clusters, b.n_features = n_clusters, n
+                b.frame_index, b.feat_offset = frame_index.data_ptr(), feat_offset.data_ptr()
+                b.params, b.low, b.high = params.data_ptr(), low.data_ptr(), high.data_ptr()
+                b.params_out, b.cost, b.status = fit.data_ptr(), fit_cost.data_ptr(), cl_status.data_ptr()
+                b.n_rounds, b.n_iter = n_rounds.data_ptr(), n_iter.data_ptr()
+                b.params_std = fit_std.data_ptr() if compute_error else None
+                eng.on_current_stream(eng.refine_batch_device, plan, b, dev=dev)
+                d.mode, d.n_clusters = _abi.PREPARE_SCATTER, n_clusters
+                d.fit_params, d.fit_cost = fit.data_ptr(), fit_cost.data_ptr()
+                d.fit_std = fit_std.data_ptr() if compute_error else None
+                d.params_out, d.cost_out = params_out.data_ptr(), cost.data_ptr()
+                d.std_out = std.data_ptr() if compute_error else None
+                eng.on_current_stream(eng.refine_prepare_device, d, dev=dev)
+                torch.cuda.current_stream(dev).synchronize()     # the plan's tables are in use until here
+            finally:
+                plan.close()
+        res = RefineResult(params_out, list(ff.params), cost, label.to(torch.int64), csize.to(torch.int64), std,
+                           cl_status, n_rounds, n_iter, feat_offset.clone())
+        if as_tensor:
+            return res
+        return RefineResult(*(x.cpu().numpy() if _is_tensor(x) else x for x in res))

@@ -1058,6 +1058,89 @@ typedef struct ctr_track_positions {
 } ctr_track_positions;
 int ctr_track_positions_device(ctr_handle* h, const ctr_track_positions* p, void* hip_stream);
 
+/* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
+ * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
+ * (find_clusters, the stable sort by (frame, cluster), FitFunctions.feature_bounds, the feasibility
+ * check of the box), on tables that stay in HBM; tests/_refine_arrays.py restates it in NumPy.
+ * Input: pos [N, ndim], rows sorted by frame; frame_offset [T + 1], 0 = off[0] <= off[t] <=
+ * off[t + 1] <= off[T] = N; params0 [N, n_params], start values in the column order of ctr_problem;
+ * separation [ndim] > 0; the three bound templates of FitFunctions.validate_bounds, each
+ * [2][CTR_MAX_PARAMS] (row 0 lower, row 1 upper; the first n_params of a row are used), NaN = none;
+ * modes [n_params] as in ctr_problem.
+ * CTR_PREPARE_BATCH:
+ *   label [N]: the smallest row index of the row's cluster -- the rule of ctr_find_clusters: two rows
+ *     of a frame are joined when the sum over the axes of ((pos_i - pos_j) / separation)^2, with
+ *     pos / separation rounded first and every product rounded before it is added, is <= 1;
+ *     clusters are the connected components.  cluster_size [N]: the rows of the row's cluster.
+ *   order [N]: the input rows sorted by (frame, label), input order kept inside a cluster;
+ *     feat_offset [C + 1] and frame_index [C]: the clusters' row ranges in that order and their
+ *     frames (the caller gives room for N + 1 and N entries); n_clusters [1] = C.
+ *   params, low, high [N, n_params], in that order: params a copy of params0;
+ *     low  = fmax over the terms that are set of p - diff[0], p * (1 - rel[0]), abs[0],
+ *     high = fmin over the terms that are set of p + diff[1], p * (1 + rel[1]), abs[1],
+ *     every term one rounded operation on the row's own p (1 -+ rel rounded first), -inf / +inf
+ *     where no term is set or the result is NaN (a NaN p); with neither diff nor rel set the
+ *     absolute bound alone, whatever p.  No operation is contracted: the doubles are those of
+ *     FitFunctions.feature_bounds bit for bit (the sign of a zero apart).
+ *   status [2]: {CTR_PREPARE_OK, n_params}; {CTR_PREPARE_BAD_TABLE, n_params} when frame_offset is
+ *     not as above (checked by the first kernel before any offset is followed; C = 0, nothing else
+ *     is written); {CTR_PREPARE_INFEASIBLE, k} when a lower bound exceeds its upper bound, k the
+ *     smallest such parameter: per row for CTR_MODE_VAR, after the min of the lows and the max of
+ *     the highs over the cluster for the shared modes, never for CTR_MODE_CONST.
+ *   Launches: a setup kernel over the rows; one workgroup of 256 threads per frame that labels
+ *   (scaled positions in LDS tiles of 256 rows, so a frame of any row count; sweeps of
+ *   take-the-smallest-label-of-a-neighbour-and-of-that-label until one changes nothing, at most
+ *   rows + 1 of them), counts and ranks the rows; one workgroup that scans the clusters per frame;
+ *   one workgroup per frame that writes the tables; a kernel over the clusters for the feasibility.
+ *   Integer atomics only, no float sums.  Asynchronous; scratch (8 ndim + 12) N + 4 (T + 1) bytes of the handle
+ *   (ctr_refine_prepare_plan gives the number without a device).
+ * CTR_PREPARE_SCATTER: the fit's results back into input row order.  order, feat_offset as written
+ *   above, n_clusters = C as read by the host; fit_params [N, n_params], fit_cost [C] and fit_std
+ *   ([N, n_params] or NULL) are ctr_batch's params_out, cost and params_std; out params_out [N,
+ *   n_params], cost_out [N] (the cost of the row's cluster), std_out (or NULL).  No scratch.
+ * Descriptors are checked before the handle, as for ctr_characterize_device.  Device pointers. */
+#define CTR_PREPARE_BATCH 0
+#define CTR_PREPARE_SCATTER 1
+#define CTR_PREPARE_OK 0
+#define CTR_PREPARE_BAD_TABLE 1
+#define CTR_PREPARE_INFEASIBLE 2
+typedef struct ctr_refine_prepare {
+  int32_t mode;                    /* CTR_PREPARE_BATCH or CTR_PREPARE_SCATTER */
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t n_params;                /* 1 .. CTR_MAX_PARAMS */
+  int32_t reserved0;
+  int32_t modes[CTR_MAX_PARAMS];   /* CTR_MODE_* (BATCH) */
+  int64_t n_frames;                /* T (BATCH) */
+  int64_t n_features;              /* N < 2^31 - 1 */
+  int64_t n_clusters;              /* C (SCATTER) */
+  double separation[CTR_MAX_NDIM];
+  double bound_abs[2 * CTR_MAX_PARAMS];   /* [2][CTR_MAX_PARAMS] */
+  double bound_diff[2 * CTR_MAX_PARAMS];
+  double bound_rel[2 * CTR_MAX_PARAMS];
+  const double* pos;               /* [N, ndim]      (BATCH) */
+  const int64_t* frame_offset;     /* [T + 1]        (BATCH) */
+  const double* params0;           /* [N, n_params]  (BATCH) */
+  int32_t* label;                  /* [N] out        (BATCH) */
+  int32_t* cluster_size;           /* [N] out        (BATCH) */
+  int32_t* order;                  /* [N]: BATCH out, SCATTER in */
+  int32_t* feat_offset;            /* [N + 1], the first C + 1 used: BATCH out, SCATTER in */
+  int32_t* frame_index;            /* [N], the first C used: out (BATCH) */
+  int32_t* n_clusters_out;         /* [1] out        (BATCH) */
+  double* params;                  /* [N, n_params] out (BATCH) */
+  double* low;
+  double* high;
+  int32_t* status;                 /* [2] out        (BATCH) */
+  const double* fit_params;        /* [N, n_params]  (SCATTER) */
+  const double* fit_cost;          /* [C]            (SCATTER) */
+  const double* fit_std;           /* [N, n_params] or NULL (SCATTER) */
+  double* params_out;              /* [N, n_params] out (SCATTER) */
+  double* cost_out;                /* [N] out        (SCATTER) */
+  double* std_out;                 /* [N, n_params] out, with fit_std (SCATTER) */
+} ctr_refine_prepare;
+int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream);
+/* No device needed: the scratch of a call (0 for CTR_PREPARE_SCATTER). */
+int ctr_refine_prepare_plan(const ctr_refine_prepare* r, int64_t* scratch_bytes);
+
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
  * several batches in flight hand finished batches on (e.g. to the result gather) from the host
