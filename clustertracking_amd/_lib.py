@@ -139,53 +139,41 @@ def cluster_kernel(problem, n_features):
     return out
 
 
-def relocate_plan(desc):
-    """(pixels of the LDS tile, dynamic LDS bytes) of a ``ctr_relocate_device`` launch
-    (``ctr_relocate_plan``, no device needed); ``ValueError`` / ``NotImplementedError`` as the call itself."""
+def _plan(symbol, desc, *outs):
+    """Calls the plan entry ``symbol`` (no device needed) on ``desc``; returns the values of the
+    ctypes out-parameters ``outs``.  ``ValueError`` / ``NotImplementedError`` as the call itself."""
     lib = load()
-    tile, lds = C.c_int64(), C.c_int64()
-    rc = lib.ctr_relocate_plan(C.byref(desc), C.byref(tile), C.byref(lds))
+    rc = getattr(lib, symbol)(C.byref(desc), *[C.byref(o) for o in outs])
     if rc != _abi.OK:
         msg = (lib.ctr_last_error(None) or b'').decode()
         raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
-    return tile.value, lds.value
+    return tuple(o.value for o in outs)
+
+
+def relocate_plan(desc):
+    """(pixels of the LDS tile, dynamic LDS bytes) of a ``ctr_relocate_device`` launch
+    (``ctr_relocate_plan``, no device needed); ``ValueError`` / ``NotImplementedError`` as the call itself."""
+    return _plan('ctr_relocate_plan', desc, C.c_int64(), C.c_int64())
 
 
 def diffusion_ci_plan(desc):
     """The launch decision of ``ctr_diffusion_ci_device`` (``ctr_diffusion_ci_plan``, no device needed):
     ``(rows_in_lds, lds_bytes, scratch_bytes, pairs_per_chunk)``; ``ValueError`` /
     ``NotImplementedError`` as the call itself."""
-    lib = load()
-    in_lds, lds, scratch, chunk = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
-    rc = lib.ctr_diffusion_ci_plan(C.byref(desc), C.byref(in_lds), C.byref(lds), C.byref(scratch), C.byref(chunk))
-    if rc != _abi.OK:
-        msg = (lib.ctr_last_error(None) or b'').decode()
-        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
-    return bool(in_lds.value), lds.value, scratch.value, chunk.value
+    in_lds, lds, scratch, chunk = _plan('ctr_diffusion_ci_plan', desc, C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64())
+    return bool(in_lds), lds, scratch, chunk
 
 
 def cluster_tracks_plan(desc):
     """``(scratch_bytes, max_rounds, jumps_per_round)`` of a ``ctr_cluster_tracks_device`` call
     (``ctr_cluster_tracks_plan``, no device needed); ``ValueError`` / ``NotImplementedError`` as the call itself."""
-    lib = load()
-    scratch, rounds, jumps = C.c_int64(), C.c_int32(), C.c_int32()
-    rc = lib.ctr_cluster_tracks_plan(C.byref(desc), C.byref(scratch), C.byref(rounds), C.byref(jumps))
-    if rc != _abi.OK:
-        msg = (lib.ctr_last_error(None) or b'').decode()
-        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
-    return scratch.value, rounds.value, jumps.value
+    return _plan('ctr_cluster_tracks_plan', desc, C.c_int64(), C.c_int32(), C.c_int32())
 
 
 def refine_prepare_plan(desc):
     """Scratch bytes of a ``ctr_refine_prepare_device`` call (``ctr_refine_prepare_plan``, no device
     needed); ``ValueError`` / ``NotImplementedError`` as the call itself."""
-    lib = load()
-    scratch = C.c_int64()
-    rc = lib.ctr_refine_prepare_plan(C.byref(desc), C.byref(scratch))
-    if rc != _abi.OK:
-        msg = (lib.ctr_last_error(None) or b'').decode()
-        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
-    return scratch.value
+    return _plan('ctr_refine_prepare_plan', desc, C.c_int64())[0]
 
 
 class Engine(object):

@@ -110,8 +110,8 @@ __global__ void mark_kernel(const KArgs k, int code) {
 // Features of one frame closer than `separation` (per-axis scaled Euclidean distance <= 1,
 // the criterion of cKDTree(pos / separation).query_pairs(1)) share a cluster.  One workgroup
 // per frame; label propagation to the smallest row index of the cluster until nothing
-// changes (bounded by the number of features of the frame).  The label is canonical (the
-// reference's ids depend on Python set order); the PARTITION is the reference's.
+// changes (label_frame, stage_common.h).  The label is canonical (the reference's ids depend
+// on Python set order); the PARTITION is the reference's.
 constexpr int FC_THREADS = 256;
 
 // (scaled_dist2, the no-contraction distance of the pair test, lives in device_common.h: the
@@ -123,6 +123,7 @@ __global__ void __launch_bounds__(FC_THREADS) find_clusters_kernel(const double*
                                                                    double* __restrict__ spos, int32_t* label,
                                                                    int32_t* __restrict__ count,
                                                                    int32_t* __restrict__ size_out) {
+  __shared__ double s_pos[FC_THREADS * ND];
   const int f = blockIdx.x;
   const int r0 = frame_offset[f], r1 = frame_offset[f + 1];
   const double sep[3] = {s0, s1, s2};
@@ -132,32 +133,11 @@ __global__ void __launch_bounds__(FC_THREADS) find_clusters_kernel(const double*
     label[i] = i;
   }
   __syncthreads();
-  for (int sweep = 0; sweep <= r1 - r0; ++sweep) {
-    bool changed = false;
-    for (int i = r0 + threadIdx.x; i < r1; i += FC_THREADS) {
-      double p[ND];
-#pragma unroll
-      for (int a = 0; a < ND; ++a) p[a] = spos[(size_t)i * ND + a];
-      const int mine = __hip_atomic_load(&label[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      int m = mine;
-      for (int j = r0; j < r1; ++j) {
-        if (scaled_dist2<ND>(p, spos + (size_t)j * ND) <= 1.) {
-          const int lj = __hip_atomic_load(&label[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          m = lj < m ? lj : m;
-        }
-      }
-      if (m < mine) {
-        __hip_atomic_store(&label[i], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        changed = true;
-      }
-    }
-    if (!__syncthreads_or(changed ? 1 : 0)) break;
-  }
+  label_frame<ND, FC_THREADS>(spos, label, r0, r1, s_pos);
   // labels of this frame are final: root = smallest row index; count members, then sizes
   for (int i = r0 + threadIdx.x; i < r1; i += FC_THREADS) atomicAdd(&count[label[i]], 1);
   __syncthreads();
-  for (int i = r0 + threadIdx.x; i < r1; i += FC_THREADS)
-    size_out[i] = __hip_atomic_load(&count[label[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int i = r0 + threadIdx.x; i < r1; i += FC_THREADS) size_out[i] = ld_agent(&count[label[i]]);
 }
 
 #include "frame_max_kernels.h"

@@ -1,6 +1,6 @@
 // cluster_track_kernels.h -- cluster tracks: from linked features to the motion stage's input
 // (ctr_cluster_tracks_device, ctr_track_positions_device; include/ctrefine.h has the rule, DESIGN.md
-// 7b).  Included by tu_cluster_tracks.hip inside its anonymous namespace (device code only, gfx950).
+// 7b).  Included by tu_cluster_tracks.hip inside its anonymous namespace, after stage_common.h.
 // Integers and copies of doubles only.  The kernel boundary is the only synchronisation between
 // workgroups; every loop is bounded by the launch's arguments or, for the rows of a frame, by
 // offsets that ctk_setup_kernel has checked against them; integer atomicMin / atomicAdd only.
@@ -8,7 +8,6 @@
 #define CTREFINE_CLUSTER_TRACK_KERNELS_H
 
 constexpr int CTK_THREADS = 256;        // a workgroup of every kernel here: 4 wavefronts
-constexpr unsigned CTK_MAX_GRID = 1u << 16;   // grid-stride kernels
 
 struct CtkArgs {
   int cs, ndim;
@@ -40,13 +39,6 @@ struct CtkArgs {
   double* pos_out;
 };
 
-__device__ __forceinline__ int ctk_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void ctk_store(int* p, int v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // The caller's tables, before any kernel follows an index: offsets monotone and within N,
 // particle < P, track < n_tracks (positions only; track_in null otherwise).  fill_keys: every key
 // slot starts as CTR_TRACKS_NO_KEY.  status[0] was zeroed in front of this kernel.
@@ -57,16 +49,12 @@ __global__ void __launch_bounds__(CTK_THREADS) ctk_setup_kernel(const CtkArgs a,
   if (fill_keys && a.M > n) n = a.M;
   bool bad = false;
   for (long long i = (long long)blockIdx.x * CTK_THREADS + threadIdx.x; i < n; i += stride) {
-    if (i <= a.T) {
-      const long long o = a.frame_offset[i];
-      bad |= o < 0 || o > a.N;
-      if (i < a.T) bad |= a.frame_offset[i + 1] < o;
-    }
+    if (i <= a.T) bad |= offsets_bad(a.frame_offset, i, a.T, a.N);
     if (i < a.N) bad |= a.particle[i] >= a.P;
     if (a.track_in && i < a.P) bad |= (long long)a.track_in[i] >= a.n_trk;
     if (fill_keys && i < a.M) a.keys[i] = CTR_TRACKS_NO_KEY;
   }
-  if (bad) ctk_store(a.status, CTR_TRACKS_BAD_TABLE);
+  if (bad) st_agent(a.status, CTR_TRACKS_BAD_TABLE);
 }
 
 // One workgroup per frame.  Every row counts the rows of the frame with its `cluster` value (tiles
@@ -75,7 +63,7 @@ __global__ void __launch_bounds__(CTK_THREADS) ctk_setup_kernel(const CtkArgs a,
 // different in a complete group).
 __global__ void __launch_bounds__(CTK_THREADS) ctk_groups_kernel(const CtkArgs a) {
   __shared__ long long s_cl[CTK_THREADS], s_pt[CTK_THREADS];
-  if (ctk_load(a.status) != CTR_TRACKS_OK) return;
+  if (ld_agent(a.status) != CTR_TRACKS_OK) return;
   const int tid = threadIdx.x, cs = a.cs;
   for (long long f = blockIdx.x; f < a.T; f += gridDim.x) {
     const long long r0 = a.frame_offset[f], r1 = a.frame_offset[f + 1];
@@ -143,8 +131,8 @@ __device__ __forceinline__ bool ctk_edge(const CtkArgs& a, long long e, int& lo,
 // an edge between two trees hangs the root with the larger id under the smaller in B.  The roots
 // then form chains of descending ids, never a cycle.
 __global__ void __launch_bounds__(CTK_THREADS) ctk_hook_kernel(const CtkArgs a, int r) {
-  if (ctk_load(a.status) != CTR_TRACKS_OK) return;
-  if (r > 0 && ctk_load(a.flags + (size_t)(r - 1) * (a.J + 1)) == 0) return;   // the round before hooked nothing: done
+  if (ld_agent(a.status) != CTR_TRACKS_OK) return;
+  if (r > 0 && ld_agent(a.flags + (size_t)(r - 1) * (a.J + 1)) == 0) return;   // the round before hooked nothing: done
   const long long stride = (long long)gridDim.x * CTK_THREADS;
   bool changed = false;
   for (long long e = (long long)blockIdx.x * CTK_THREADS + threadIdx.x; e < a.M; e += stride) {
@@ -155,29 +143,29 @@ __global__ void __launch_bounds__(CTK_THREADS) ctk_hook_kernel(const CtkArgs a, 
     atomicMin(a.B + (ra > rb ? ra : rb), ra > rb ? rb : ra);
     changed = true;
   }
-  if (changed) ctk_store(a.flags + (size_t)r * (a.J + 1), 1);
+  if (changed) st_agent(a.flags + (size_t)r * (a.J + 1), 1);
 }
 
 // Round r, jump j: B[i] = B[B[i]], in place -- a label read here is the old one or one further up,
 // so the depth of every tree at least halves -- and A[i] = B[i].  Returns at once when the round's
 // hook, or the jump before, changed nothing: B is then flat and A == B.
 __global__ void __launch_bounds__(CTK_THREADS) ctk_jump_kernel(const CtkArgs a, int r, int j) {
-  if (ctk_load(a.status) != CTR_TRACKS_OK) return;
+  if (ld_agent(a.status) != CTR_TRACKS_OK) return;
   int* fl = a.flags + (size_t)r * (a.J + 1);
-  if (ctk_load(fl) == 0 || (j > 0 && ctk_load(fl + j) == 0)) return;
+  if (ld_agent(fl) == 0 || (j > 0 && ld_agent(fl + j) == 0)) return;
   const long long stride = (long long)gridDim.x * CTK_THREADS;
   bool changed = false;
   for (long long i = (long long)blockIdx.x * CTK_THREADS + threadIdx.x; i < a.P; i += stride) {
-    const int p = ctk_load(a.B + i), g = ctk_load(a.B + p);
-    if (g != p) { ctk_store(a.B + i, g); changed = true; }
+    const int p = ld_agent(a.B + i), g = ld_agent(a.B + p);
+    if (g != p) { st_agent(a.B + i, g); changed = true; }
     a.A[i] = g;
   }
-  if (changed) ctk_store(fl + 1 + j, 1);
+  if (changed) st_agent(fl + 1 + j, 1);
 }
 
 // Would a further round change anything?  Every edge inside one tree, every tree a star.
 __global__ void __launch_bounds__(CTK_THREADS) ctk_verify_kernel(const CtkArgs a) {
-  if (ctk_load(a.status) != CTR_TRACKS_OK) return;
+  if (ld_agent(a.status) != CTR_TRACKS_OK) return;
   const long long stride = (long long)gridDim.x * CTK_THREADS;
   const long long n = a.M > a.P ? a.M : a.P;
   bool open = false;
@@ -186,16 +174,16 @@ __global__ void __launch_bounds__(CTK_THREADS) ctk_verify_kernel(const CtkArgs a
     if (i < a.M && ctk_edge(a, i, u, v)) open |= a.A[u] != a.A[v];
     if (i < a.P) open |= a.A[a.A[i]] != a.A[i] || a.B[i] != a.A[i];
   }
-  if (open) ctk_store(a.status, CTR_TRACKS_ROUNDS);
+  if (open) st_agent(a.status, CTR_TRACKS_ROUNDS);
 }
 
 __global__ void __launch_bounds__(CTK_THREADS) ctk_count_kernel(const CtkArgs a) {
   if (blockIdx.x == 0 && threadIdx.x == 0 && a.n_rounds) {
     int used = 0;
-    for (int r = 0; r < a.R; ++r) used += ctk_load(a.flags + (size_t)r * (a.J + 1)) != 0;
+    for (int r = 0; r < a.R; ++r) used += ld_agent(a.flags + (size_t)r * (a.J + 1)) != 0;
     *a.n_rounds = used;
   }
-  if (ctk_load(a.status) != CTR_TRACKS_OK) return;
+  if (ld_agent(a.status) != CTR_TRACKS_OK) return;
   const long long stride = (long long)gridDim.x * CTK_THREADS;
   for (long long i = (long long)blockIdx.x * CTK_THREADS + threadIdx.x; i < a.P; i += stride) atomicAdd(a.size + a.A[i], 1);
 }
@@ -207,7 +195,7 @@ __device__ __forceinline__ bool ctk_track_root(const CtkArgs& a, long long i, bo
 
 // grid = blocks of CTK_THREADS particles
 __global__ void __launch_bounds__(CTK_THREADS) ctk_blocksum_kernel(const CtkArgs a) {
-  const bool ok = ctk_load(a.status) == CTR_TRACKS_OK;
+  const bool ok = ld_agent(a.status) == CTR_TRACKS_OK;
   const long long i = (long long)blockIdx.x * CTK_THREADS + threadIdx.x;
   const int n = __syncthreads_count(ctk_track_root(a, i, ok) ? 1 : 0);
   if (threadIdx.x == 0) a.blocksum[blockIdx.x] = n;
@@ -215,38 +203,15 @@ __global__ void __launch_bounds__(CTK_THREADS) ctk_blocksum_kernel(const CtkArgs
 
 // one workgroup: exclusive scan of the nb block counts in place, n_tracks = their sum
 __global__ void __launch_bounds__(CTK_THREADS) ctk_scan_kernel(const CtkArgs a, long long nb) {
-  __shared__ int s_wave[CTK_THREADS / 64], s_carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (long long c = 0; c < nb; c += CTK_THREADS) {
-    const int v = c + tid < nb ? a.blocksum[c + tid] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = s_carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < CTK_THREADS / 64; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    if (c + tid < nb) a.blocksum[c + tid] = before + incl - v;
-    __syncthreads();
-    if (tid == 0) s_carry += total;
-    __syncthreads();
-  }
-  if (tid == 0) *a.n_tracks = s_carry;
+  const int n = workgroup_scan_n<CTK_THREADS, int>(
+      nb, [&](long long i) { return a.blocksum[i]; }, [&](long long i, int before) { a.blocksum[i] = before; });
+  if (threadIdx.x == 0) *a.n_tracks = n;
 }
 
 // the roots in ascending order, compacted: number = roots of the blocks before + rank in the block
 __global__ void __launch_bounds__(CTK_THREADS) ctk_number_kernel(const CtkArgs a) {
   __shared__ int s_wave[CTK_THREADS / 64];
-  const bool ok = ctk_load(a.status) == CTR_TRACKS_OK;
+  const bool ok = ld_agent(a.status) == CTR_TRACKS_OK;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long i = (long long)blockIdx.x * CTK_THREADS + tid;
   const bool root = ctk_track_root(a, i, ok);
@@ -261,7 +226,7 @@ __global__ void __launch_bounds__(CTK_THREADS) ctk_number_kernel(const CtkArgs a
 }
 
 __global__ void __launch_bounds__(CTK_THREADS) ctk_assign_kernel(const CtkArgs a) {
-  const bool ok = ctk_load(a.status) == CTR_TRACKS_OK;
+  const bool ok = ld_agent(a.status) == CTR_TRACKS_OK;
   const long long stride = (long long)gridDim.x * CTK_THREADS;
   for (long long i = (long long)blockIdx.x * CTK_THREADS + threadIdx.x; i < a.P; i += stride) {
     int k = -1;
@@ -288,7 +253,7 @@ __device__ __forceinline__ int ctk_row_track(const CtkArgs& a, long long p) { re
 
 // one workgroup per frame; one integer add per member row
 __global__ void __launch_bounds__(CTK_THREADS) ctk_present_kernel(const CtkArgs a) {
-  if (ctk_load(a.status) != CTR_TRACKS_OK) return;
+  if (ld_agent(a.status) != CTR_TRACKS_OK) return;
   for (long long f = blockIdx.x; f < a.T; f += gridDim.x) {
     const long long r0 = a.frame_offset[f], r1 = a.frame_offset[f + 1];
     for (long long i = r0 + threadIdx.x; i < r1; i += CTK_THREADS) {
@@ -304,7 +269,7 @@ __global__ void __launch_bounds__(CTK_THREADS) ctk_present_kernel(const CtkArgs 
 __global__ void __launch_bounds__(CTK_THREADS) ctk_scatter_kernel(const CtkArgs a) {
   __shared__ long long s_pt[CTK_THREADS];
   __shared__ int s_tr[CTK_THREADS];
-  if (ctk_load(a.status) != CTR_TRACKS_OK) return;
+  if (ld_agent(a.status) != CTR_TRACKS_OK) return;
   const int tid = threadIdx.x;
   for (long long f = blockIdx.x; f < a.T; f += gridDim.x) {
     const long long r0 = a.frame_offset[f], r1 = a.frame_offset[f + 1];

@@ -32,6 +32,7 @@
 namespace {
 
 #include "device_common.h"
+#include "stage_common.h"
 #include "aux_kernels.h"
 #include "synth_kernels.h"
 
@@ -941,18 +942,19 @@ int ctr_find_clusters(ctr_handle* h, int32_t ndim, const double* pos, const int3
     if (!(separation[a] > 0.)) return fail(h, CTR_ERR_INVALID, "separation must be positive");
   if (N == 0) return CTR_OK;
   HIP_TRY(h, hipSetDevice(h->device));
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t sz_pos = al(sizeof(double) * (size_t)N * ndim), sz_fo = al(sizeof(int32_t) * (size_t)(n_frames + 1));
-  const size_t sz_i = al(sizeof(int32_t) * (size_t)N);
-  const size_t total = 2 * sz_pos + sz_fo + 3 * sz_i;
+  const size_t b_pos = sizeof(double) * (size_t)N * ndim, b_i = sizeof(int32_t) * (size_t)N;
+  size_t total = 0;
+  const size_t o_pos = carve(total, b_pos), o_spos = carve(total, b_pos),
+               o_fo = carve(total, sizeof(int32_t) * (size_t)(n_frames + 1)), o_label = carve(total, b_i),
+               o_count = carve(total, b_i), o_size = carve(total, b_i);
   if (int rc = reserve(h, h->buf, total, "cannot allocate device memory")) return rc;
   char* q = (char*)h->buf.ptr;
-  double* d_pos = (double*)q; q += sz_pos;
-  double* d_spos = (double*)q; q += sz_pos;
-  int32_t* d_fo = (int32_t*)q; q += sz_fo;
-  int32_t* d_label = (int32_t*)q; q += sz_i;
-  int32_t* d_count = (int32_t*)q; q += sz_i;
-  int32_t* d_size = (int32_t*)q;
+  double* d_pos = (double*)(q + o_pos);
+  double* d_spos = (double*)(q + o_spos);
+  int32_t* d_fo = (int32_t*)(q + o_fo);
+  int32_t* d_label = (int32_t*)(q + o_label);
+  int32_t* d_count = (int32_t*)(q + o_count);
+  int32_t* d_size = (int32_t*)(q + o_size);
   hipStream_t s = h->stream;
   HIP_TRY(h, hipMemcpyAsync(d_pos, pos, sizeof(double) * (size_t)N * ndim, hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemcpyAsync(d_fo, frame_offset, sizeof(int32_t) * (size_t)(n_frames + 1), hipMemcpyHostToDevice, s));

@@ -127,7 +127,7 @@ __device__ __forceinline__ bool fl_live(const LinkArgs& l, long long s) {
 }
 
 __device__ __forceinline__ int fl_root(const LinkArgs& l, long long s) {
-  const int lab = lnk_ld(&l.lab_s[s]);
+  const int lab = ld_agent(&l.lab_s[s]);
   return lab != LNK_NONE ? lab : (int)s;
 }
 
@@ -156,11 +156,11 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_merge_kernel(FlArgs a, int t) 
 
   lnk_components(l, v.d0, v.dl, v.w0, v.w1, tid, &s_changed);
   for (long long r = v.w0 + tid; r < v.dl; r += LNK_THREADS) {
-    lnk_st(&a.sn_ns[r], 0);
-    lnk_st(&a.sn_nd[r], 0);
-    lnk_st(&a.mrg[r], (int)r);
-    lnk_st(&a.m_ns[r], 0);
-    lnk_st(&a.m_nd[r], 0);
+    st_agent(&a.sn_ns[r], 0);
+    st_agent(&a.sn_nd[r], 0);
+    st_agent(&a.mrg[r], (int)r);
+    st_agent(&a.m_ns[r], 0);
+    st_agent(&a.m_nd[r], 0);
     a.qof[r] = -1;
   }
   if (tid == 0) s_total = 0;
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_merge_kernel(FlArgs a, int t) 
   for (long long s = v.w0 + tid; s < v.w1; s += LNK_THREADS)
     if (fl_live<ND>(l, s)) atomicAdd(&a.sn_ns[fl_root(l, s)], 1);
   for (long long i = v.d0 + tid; i < v.dl; i += LNK_THREADS)
-    if (l.ncand[i] > 0) atomicAdd(&a.sn_nd[lnk_ld(&l.lab_d[i])], 1);
+    if (l.ncand[i] > 0) atomicAdd(&a.sn_nd[ld_agent(&l.lab_d[i])], 1);
   __syncthreads();
 
   // ---- the 10 nearest sources within 2 of every source of a short sub-network (itself included)
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_merge_kernel(FlArgs a, int t) 
     int n = 0;
     if (fl_live<ND>(l, s)) {
       const int root = fl_root(l, s);
-      if (lnk_ld(&a.sn_ns[root]) - lnk_ld(&a.sn_nd[root]) > 0) {
+      if (ld_agent(&a.sn_ns[root]) - ld_agent(&a.sn_nd[root]) > 0) {
         double pd[ND], bd[LNK_MAXC];
         int br[LNK_MAXC];
 #pragma unroll
@@ -227,9 +227,9 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_merge_kernel(FlArgs a, int t) 
       const int n = a.nmnb[s];
       if (n == 0) continue;
       const int rs = fl_root(l, s);
-      int m = lnk_ld(&a.mrg[rs]);
+      int m = ld_agent(&a.mrg[rs]);
       for (int k = 0; k < n; ++k) {
-        const int o = lnk_ld(&a.mrg[fl_root(l, a.mnb[s * LNK_MAXC + k])]);
+        const int o = ld_agent(&a.mrg[fl_root(l, a.mnb[s * LNK_MAXC + k])]);
         m = o < m ? o : m;
       }
       if (atomicMin(&a.mrg[rs], m) > m) changed = true;
@@ -246,9 +246,9 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_merge_kernel(FlArgs a, int t) 
 
   // ---- sources and destinations per merged sub-network
   for (long long s = v.w0 + tid; s < v.w1; s += LNK_THREADS)
-    if (fl_live<ND>(l, s)) atomicAdd(&a.m_ns[lnk_ld(&a.mrg[fl_root(l, s)])], 1);
+    if (fl_live<ND>(l, s)) atomicAdd(&a.m_ns[ld_agent(&a.mrg[fl_root(l, s)])], 1);
   for (long long i = v.d0 + tid; i < v.dl; i += LNK_THREADS)
-    if (l.ncand[i] > 0) atomicAdd(&a.m_nd[lnk_ld(&a.mrg[lnk_ld(&l.lab_d[i])])], 1);
+    if (l.ncand[i] > 0) atomicAdd(&a.m_nd[ld_agent(&a.mrg[ld_agent(&l.lab_d[i])])], 1);
   __syncthreads();
 
   // ---- the short ones, in row order of their root, are the queries
@@ -257,8 +257,8 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_merge_kernel(FlArgs a, int t) 
     int ns = 0, nd = 0;
     bool is = false;
     if (r < v.dl) {
-      ns = lnk_ld(&a.m_ns[r]);
-      nd = lnk_ld(&a.m_nd[r]);
+      ns = ld_agent(&a.m_ns[r]);
+      nd = ld_agent(&a.m_nd[r]);
       is = ns - nd > 0;
     }
     const unsigned long long bal = __ballot(is);
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_merge_kernel(FlArgs a, int t) 
     a.q_soff[0] = 0;
     for (int q = 0; q < a.Q; ++q) {
       if (q < nq) {
-        const int ns = lnk_ld(&a.m_ns[a.q_root[q]]);
+        const int ns = ld_agent(&a.m_ns[a.q_root[q]]);
         at += ns <= LNK_MAX_SRC ? ns : 0;      // an oversize one asks nothing
       }
       a.q_soff[q + 1] = at;
@@ -297,9 +297,9 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_merge_kernel(FlArgs a, int t) 
   __syncthreads();
   for (long long s = v.w0 + tid; s < v.w1; s += LNK_THREADS) {
     if (!fl_live<ND>(l, s)) continue;
-    const int mr = lnk_ld(&a.mrg[fl_root(l, s)]);
+    const int mr = ld_agent(&a.mrg[fl_root(l, s)]);
     const int q = a.qof[mr];
-    if (q < 0 || lnk_ld(&a.m_ns[mr]) > LNK_MAX_SRC) continue;
+    if (q < 0 || ld_agent(&a.m_ns[mr]) > LNK_MAX_SRC) continue;
     const long long slot = a.q_soff[q] + atomicAdd(&a.q_fill[q], 1);
 #pragma unroll
     for (int d = 0; d < ND; ++d) a.q_spos[slot * ND + d] = l.pos[s * ND + d];
@@ -323,8 +323,8 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_solve_kernel(FlArgs a, int t) 
   const int nq = a.n_q[0];
 
   for (long long r = v.w0 + tid; r < v.dl; r += LNK_THREADS) {
-    lnk_st(&l.head_d[r], -1);
-    lnk_st(&l.head_s[r], -1);
+    st_agent(&l.head_d[r], -1);
+    st_agent(&l.head_s[r], -1);
   }
   for (int c = tid; c < a.Q * a.K; c += LNK_THREADS) a.claim[c] = -1;
   if (tid == 0) { s_nroots = 0; s_nclaimed = 0; }
@@ -333,27 +333,27 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_solve_kernel(FlArgs a, int t) 
   // ---- 1 x 1 sub-networks link here; the members of the others are chained to their root
   for (long long i = v.d0 + tid; i < v.dl; i += LNK_THREADS) {
     if (l.ncand[i] == 0) continue;
-    const int mr = lnk_ld(&a.mrg[lnk_ld(&l.lab_d[i])]);
-    if (lnk_ld(&a.m_ns[mr]) == 1 && lnk_ld(&a.m_nd[mr]) == 1) {
+    const int mr = ld_agent(&a.mrg[ld_agent(&l.lab_d[i])]);
+    if (ld_agent(&a.m_ns[mr]) == 1 && ld_agent(&a.m_nd[mr]) == 1) {
       const int c = l.cand_row[i * LNK_MAXC];
       l.link[i] = c;
       if (l.memory > 0) l.used[c] = 1;
       continue;
     }
-    lnk_st(&l.next_d[i], atomicExch(&l.head_d[mr], (int)i));
+    st_agent(&l.next_d[i], atomicExch(&l.head_d[mr], (int)i));
   }
   for (long long s = v.w0 + tid; s < v.w1; s += LNK_THREADS) {
     if (!fl_live<ND>(l, s)) continue;
-    const int mr = lnk_ld(&a.mrg[fl_root(l, s)]);
-    const int ns = lnk_ld(&a.m_ns[mr]), nd = lnk_ld(&a.m_nd[mr]);
+    const int mr = ld_agent(&a.mrg[fl_root(l, s)]);
+    const int ns = ld_agent(&a.m_ns[mr]), nd = ld_agent(&a.m_nd[mr]);
     if (ns == 1 && nd == 1) continue;
-    lnk_st(&l.next_s[s], atomicExch(&l.head_s[mr], (int)s));
+    st_agent(&l.next_s[s], atomicExch(&l.head_s[mr], (int)s));
   }
   for (long long r = v.w0 + tid; r < v.dl; r += LNK_THREADS) {
-    const int ns = lnk_ld(&a.m_ns[r]), nd = lnk_ld(&a.m_nd[r]);
+    const int ns = ld_agent(&a.m_ns[r]), nd = ld_agent(&a.m_nd[r]);
     if (ns < 1 || (ns == 1 && nd == 1)) continue;
     if (nd < 1 && a.qof[r] < 0) continue;      // short, but beyond the level's queries: lost
-    lnk_st(&l.roots[v.w0 + atomicAdd(&s_nroots, 1)], (int)r);
+    st_agent(&l.roots[v.w0 + atomicAdd(&s_nroots, 1)], (int)r);
   }
   __syncthreads();
 
@@ -362,10 +362,10 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_solve_kernel(FlArgs a, int t) 
   const int nroots = s_nroots;
   const double bound = (1. + 1e-7) * (1. + 1e-7);
   for (int ri = w; ri < nroots; ri += LNK_WAVES) {
-    const int root = lnk_ld(&l.roots[v.w0 + ri]);
+    const int root = ld_agent(&l.roots[v.w0 + ri]);
     int ns = 0, nd = 0;
     if (lane == 0) {   // members in ascending row order, whatever order they were chained in
-      for (int j = lnk_ld(&l.head_s[root]); j >= 0; j = lnk_ld(&l.next_s[j])) {
+      for (int j = ld_agent(&l.head_s[root]); j >= 0; j = ld_agent(&l.next_s[j])) {
         if (ns < LNK_MAX_SRC) {
           int q = ns;
           for (; q > 0 && s_src[w][q - 1] > j; --q) s_src[w][q] = s_src[w][q - 1];
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_solve_kernel(FlArgs a, int t) 
         }
         ++ns;
       }
-      for (int j = lnk_ld(&l.head_d[root]); j >= 0; j = lnk_ld(&l.next_d[j])) {
+      for (int j = ld_agent(&l.head_d[root]); j >= 0; j = ld_agent(&l.next_d[j])) {
         if (nd < LNK_MAX_DST) {
           int q = nd;
           for (; q > 0 && s_dst[w][q - 1] > j; --q) s_dst[w][q] = s_dst[w][q - 1];
@@ -504,23 +504,9 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_solve_kernel(FlArgs a, int t) 
 
 // one workgroup: o_off[t] = live rows of the levels before t
 __global__ __launch_bounds__(LNK_THREADS) void fl_offsets_kernel(FlArgs a) {
-  __shared__ long long s_part[LNK_THREADS];
-  const int tid = threadIdx.x;
-  const int per = (a.n_levels + LNK_THREADS - 1) / LNK_THREADS;
-  const long long b = (long long)tid * per;
-  const long long e = b + per < a.n_levels ? b + per : a.n_levels;
-  long long sum = 0;
-  for (long long t = b; t < e; ++t) sum += a.cnt[t];
-  s_part[tid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    long long run = 0;
-    for (int k = 0; k < LNK_THREADS; ++k) { const long long x = s_part[k]; s_part[k] = run; run += x; }
-    a.o_off[a.n_levels] = run;
-  }
-  __syncthreads();
-  long long run = s_part[tid];
-  for (long long t = b; t < e; ++t) { a.o_off[t] = run; run += a.cnt[t]; }
+  const long long n = workgroup_scan_n<LNK_THREADS, long long>(
+      a.n_levels, [&](long long t) { return a.cnt[t]; }, [&](long long t, long long before) { a.o_off[t] = before; });
+  if (threadIdx.x == 0) a.o_off[a.n_levels] = n;
 }
 
 template <int ND>
@@ -534,17 +520,8 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_emit_kernel(FlArgs a) {
     long long out = a.o_off[t] + local;
     if (local >= n_loc) {       // a relocated row: its rank in C order among those of the level
       int rank = 0;
-      for (long long j = s0 + n_loc; j < s0 + a.cnt[t]; ++j) {
-        if (j == i) continue;
-        int less = j < i ? 1 : 0;
-        bool decided = false;
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-          const double q = a.ppos[j * ND + d], p = a.ppos[i * ND + d];
-          if (!decided && q != p) { less = q < p ? 1 : 0; decided = true; }
-        }
-        rank += less;
-      }
+      for (long long j = s0 + n_loc; j < s0 + a.cnt[t]; ++j)
+        if (j != i) rank += lnk_row_before<ND>(a.ppos, j, i) ? 1 : 0;
       out = a.o_off[t] + n_loc + rank;
     }
 #pragma unroll

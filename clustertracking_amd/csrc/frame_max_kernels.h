@@ -1,7 +1,7 @@
 // frame_max_kernels.h -- the per-frame maximum of a frame block (the norm of refine.py:354 and
 // refine.py:325-331) and the one function that queues it.  Included inside the anonymous namespace
 // of the units that need it (ctrefine.hip through aux_kernels.h, tu_train.hip), after
-// device_common.h.
+// device_common.h and stage_common.h (ordered_key).
 #ifndef CTREFINE_FRAME_MAX_KERNELS_H
 #define CTREFINE_FRAME_MAX_KERNELS_H
 
@@ -9,18 +9,13 @@
 // Streams the frame block once: 16 B per lane per load, one ordered-u64 atomicMax
 // per workgroup.  HBM-bound.
 
-// Order-preserving map of a double to a u64.  A NaN has to win every maximum (NumPy's max
+// The ordered key of a double with a rule for NaN.  A NaN has to win every maximum (NumPy's max
 // propagates it), and by its bits only a NaN with the sign bit clear does: one with the sign bit
 // set -- what 0 * inf, inf - inf and 0 / 0 give on x86 -- would come out below -inf and be lost,
 // together with the maximum its lane had found.  So every NaN is encoded as the positive quiet NaN.
 __device__ __forceinline__ unsigned long long enc_f64(double x) {
-  if (x != x) return 0xfff8000000000000ull;   // = enc of 0x7ff8000000000000, above +inf
-  unsigned long long b = (unsigned long long)__double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dec_f64(unsigned long long e) {
-  unsigned long long b = (e >> 63) ? (e & 0x7fffffffffffffffull) : ~e;
-  return __longlong_as_double((long long)b);
+  if (x != x) return 0xfff8000000000000ull;   // = ordered_key of 0x7ff8000000000000, above +inf
+  return ordered_key(x);
 }
 
 template <typename T>
@@ -92,7 +87,7 @@ __global__ void __launch_bounds__(FM_THREADS) frame_max_kernel(const void* frame
 
 __global__ void frame_max_decode_kernel(const unsigned long long* enc, double* out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = dec_f64(enc[i]);
+  if (i < n) out[i] = ordered_unkey(enc[i]);
 }
 
 // bytes of a pixel of CTR_DTYPE_*; 0 for an unknown one

@@ -127,7 +127,7 @@ int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
 // message in *msg.  Their callers are run_stage (ctrefine.hip), for every ctr_<stage>_device, and
-// the two ctr_*_plan queries.
+// the two ctr_*_plan queries.  The device and host primitives they share are in stage_common.h.
 enum StageMode {
   STAGE_CHECK_SCALARS,   // the scalars alone, no pointer is looked at (ctr_*_plan); a stage whose
                          // launch decision needs no such form checks everything

@@ -1,5 +1,5 @@
 // link_kernels.h -- frame-to-frame linking on the device (ctr_link_device).
-// Included by tu_link.hip inside its anonymous namespace, after device_common.h, and by
+// Included by tu_link.hip inside its anonymous namespace, after device_common.h and stage_common.h, and by
 // tu_findlink.hip, whose loop (findlink_kernels.h) runs these kernels and the two device functions of
 // link_solve_kernel (lnk_components, lnk_hungarian) on a table that grows by the relocated rows.
 //
@@ -80,14 +80,6 @@ struct LinkArgs {
   long long* base;  // [n_levels + 1]
 };
 
-// words other lanes of the workgroup change through atomics: read them past the L1
-__device__ __forceinline__ int lnk_ld(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void lnk_st(int* p, int v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // the level of row i < off[n_levels]: the smallest t with off[t + 1] > i
 __device__ __forceinline__ int lnk_level_of(const long long* off, int n_levels, long long i) {
   int lo = 0, hi = n_levels - 1;
@@ -107,8 +99,8 @@ __device__ __forceinline__ void lnk_wave_sync() {
 
 __device__ __forceinline__ void lnk_report(int* status, int code, int level, int size) {
   if (atomicCAS(&status[0], 0, code) == 0) {
-    lnk_st(&status[1], level);
-    lnk_st(&status[2], size);
+    st_agent(&status[1], level);
+    st_agent(&status[2], size);
   }
 }
 
@@ -178,13 +170,13 @@ __device__ __forceinline__ void lnk_components(const LinkArgs& a, long long d0, 
                                                long long w1, int tid, int* s_changed) {
   // ---- initial state of this level's words
   for (long long s = w0 + tid; s < w1; s += LNK_THREADS) {
-    lnk_st(&a.lab_s[s], LNK_NONE);
-    lnk_st(&a.cnt_s[s], 0);
+    st_agent(&a.lab_s[s], LNK_NONE);
+    st_agent(&a.cnt_s[s], 0);
   }
   for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
-    lnk_st(&a.lab_d[i], (int)i);
-    lnk_st(&a.head_d[i], -1);
-    lnk_st(&a.head_s[i], -1);
+    st_agent(&a.lab_d[i], (int)i);
+    st_agent(&a.head_d[i], -1);
+    st_agent(&a.head_s[i], -1);
   }
   __syncthreads();
   for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
@@ -201,15 +193,15 @@ __device__ __forceinline__ void lnk_components(const LinkArgs& a, long long d0, 
     for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
       const int nc = a.ncand[i];
       if (nc == 0) continue;
-      const int mine = lnk_ld(&a.lab_d[i]);
+      const int mine = ld_agent(&a.lab_d[i]);
       int m = mine;
       for (int k = 0; k < nc; ++k) {
-        const int l = lnk_ld(&a.lab_s[a.cand_row[i * LNK_MAXC + k]]);
+        const int l = ld_agent(&a.lab_s[a.cand_row[i * LNK_MAXC + k]]);
         m = l < m ? l : m;
       }
       for (int k = 0; k < nc; ++k)
         if (atomicMin(&a.lab_s[a.cand_row[i * LNK_MAXC + k]], m) > m) changed = true;
-      if (m < mine) { lnk_st(&a.lab_d[i], m); changed = true; }
+      if (m < mine) { st_agent(&a.lab_d[i], m); changed = true; }
     }
     if (changed) *s_changed = 1;
     __syncthreads();
@@ -308,21 +300,21 @@ __global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int
     const int nc = a.ncand[i];
     if (nc == 0) continue;
     const int c = a.cand_row[i * LNK_MAXC];
-    if (nc == 1 && lnk_ld(&a.cnt_s[c]) == 1) {
+    if (nc == 1 && ld_agent(&a.cnt_s[c]) == 1) {
       a.link[i] = c;
       if (a.memory > 0) a.used[c] = 1;
-      lnk_st(&a.cnt_s[c], 0);          // not a member of a chained component
+      st_agent(&a.cnt_s[c], 0);          // not a member of a chained component
       continue;
     }
-    const int root = lnk_ld(&a.lab_d[i]);
-    if (root == (int)i) lnk_st(&a.roots[d0 + atomicAdd(&s_nroots, 1)], (int)i);
-    lnk_st(&a.next_d[i], atomicExch(&a.head_d[root], (int)i));
+    const int root = ld_agent(&a.lab_d[i]);
+    if (root == (int)i) st_agent(&a.roots[d0 + atomicAdd(&s_nroots, 1)], (int)i);
+    st_agent(&a.next_d[i], atomicExch(&a.head_d[root], (int)i));
   }
   __syncthreads();   // the 1 x 1 sources are marked (cnt_s = 0) before the sources are chained
   for (long long s = w0 + tid; s < w1; s += LNK_THREADS) {
-    if (lnk_ld(&a.cnt_s[s]) == 0) continue;
-    const int root = lnk_ld(&a.lab_s[s]);
-    lnk_st(&a.next_s[s], atomicExch(&a.head_s[root], (int)s));
+    if (ld_agent(&a.cnt_s[s]) == 0) continue;
+    const int root = ld_agent(&a.lab_s[s]);
+    st_agent(&a.next_s[s], atomicExch(&a.head_s[root], (int)s));
   }
   __syncthreads();
 
@@ -330,10 +322,10 @@ __global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int
   const int w = tid >> 6, lane = tid & 63;
   const int nroots = s_nroots;
   for (int ri = w; ri < nroots; ri += LNK_WAVES) {
-    const int root = lnk_ld(&a.roots[d0 + ri]);
+    const int root = ld_agent(&a.roots[d0 + ri]);
     int ns = 0, nd = 0;
     if (lane == 0) {   // members in ascending row order, whatever order they were chained in
-      for (int j = lnk_ld(&a.head_s[root]); j >= 0; j = lnk_ld(&a.next_s[j])) {
+      for (int j = ld_agent(&a.head_s[root]); j >= 0; j = ld_agent(&a.next_s[j])) {
         if (ns < LNK_MAX_SRC) {
           int q = ns;
           for (; q > 0 && s_src[w][q - 1] > j; --q) s_src[w][q] = s_src[w][q - 1];
@@ -341,7 +333,7 @@ __global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int
         }
         ++ns;
       }
-      for (int j = lnk_ld(&a.head_d[root]); j >= 0; j = lnk_ld(&a.next_d[j])) {
+      for (int j = ld_agent(&a.head_d[root]); j >= 0; j = ld_agent(&a.next_d[j])) {
         if (nd < LNK_MAX_DST) {
           int q = nd;
           for (; q > 0 && s_dst[w][q - 1] > j; --q) s_dst[w][q] = s_dst[w][q - 1];
@@ -386,6 +378,18 @@ __global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int
   }
 }
 
+// row j comes before row i: positions compared axis by axis; equal positions keep their row order
+// (a stable sort)
+template <int ND>
+__device__ __forceinline__ bool lnk_row_before(const double* pos, long long j, long long i) {
+#pragma unroll
+  for (int d = 0; d < ND; ++d) {
+    const double q = pos[j * ND + d], p = pos[i * ND + d];
+    if (q != p) return q < p;
+  }
+  return j < i;
+}
+
 template <int ND>
 __global__ __launch_bounds__(LNK_THREADS) void link_rank_kernel(LinkArgs a) {
   const long long stride = (long long)gridDim.x * LNK_THREADS;
@@ -399,20 +403,8 @@ __global__ __launch_bounds__(LNK_THREADS) void link_rank_kernel(LinkArgs a) {
     if (t == 0) {
       rank = (int)(i - d0);        // level 0 counts its rows (find_link.py:620-623)
     } else {
-      double p[ND];
-#pragma unroll
-      for (int d = 0; d < ND; ++d) p[d] = a.pos[i * ND + d];
-      for (long long j = d0; j < d1; ++j) {
-        if (a.link[j] >= 0 || j == i) continue;
-        int less = j < i ? 1 : 0;   // equal positions keep their row order (a stable sort)
-        bool decided = false;
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-          const double q = a.pos[j * ND + d];
-          if (!decided && q != p[d]) { less = q < p[d] ? 1 : 0; decided = true; }
-        }
-        rank += less;
-      }
+      for (long long j = d0; j < d1; ++j)
+        if (a.link[j] < 0 && j != i) rank += lnk_row_before<ND>(a.pos, j, i) ? 1 : 0;
     }
     a.rank[i] = rank;
     atomicAdd(&a.nbirth[t], 1);
@@ -421,24 +413,12 @@ __global__ __launch_bounds__(LNK_THREADS) void link_rank_kernel(LinkArgs a) {
 
 // one workgroup: base[t] = births of the levels before t; base[n_levels] = number of tracks
 __global__ __launch_bounds__(LNK_THREADS) void link_scan_kernel(LinkArgs a) {
-  __shared__ long long s_part[LNK_THREADS];
-  const int tid = threadIdx.x;
-  const int per = (a.n_levels + LNK_THREADS - 1) / LNK_THREADS;
-  const long long b = (long long)tid * per;
-  const long long e = b + per < a.n_levels ? b + per : a.n_levels;
-  long long sum = 0;
-  for (long long t = b; t < e; ++t) sum += a.nbirth[t];
-  s_part[tid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    long long run = 0;
-    for (int k = 0; k < LNK_THREADS; ++k) { const long long v = s_part[k]; s_part[k] = run; run += v; }
-    a.base[a.n_levels] = run;
-    *a.n_tracks = run;
+  const long long n = workgroup_scan_n<LNK_THREADS, long long>(
+      a.n_levels, [&](long long t) { return a.nbirth[t]; }, [&](long long t, long long before) { a.base[t] = before; });
+  if (threadIdx.x == 0) {
+    a.base[a.n_levels] = n;
+    *a.n_tracks = n;
   }
-  __syncthreads();
-  long long run = s_part[tid];
-  for (long long t = b; t < e; ++t) { a.base[t] = run; run += a.nbirth[t]; }
 }
 
 // anc[i] is always an ancestor of i (or i, a root): a value read while another lane replaces it
@@ -446,9 +426,9 @@ __global__ __launch_bounds__(LNK_THREADS) void link_scan_kernel(LinkArgs a) {
 __global__ __launch_bounds__(LNK_THREADS) void link_jump_kernel(LinkArgs a) {
   const long long stride = (long long)gridDim.x * LNK_THREADS;
   for (long long i = (long long)blockIdx.x * LNK_THREADS + threadIdx.x; i < a.n; i += stride) {
-    const int p = lnk_ld(&a.anc[i]);
-    const int q = lnk_ld(&a.anc[p]);
-    if (q != p) lnk_st(&a.anc[i], q);
+    const int p = ld_agent(&a.anc[i]);
+    const int q = ld_agent(&a.anc[p]);
+    if (q != p) st_agent(&a.anc[i], q);
   }
 }
 
@@ -461,30 +441,22 @@ __global__ __launch_bounds__(LNK_THREADS) void link_ids_kernel(LinkArgs a) {
 }
 
 // ---- host: the scratch of a call
-constexpr size_t LNK_ALIGN = 256;
-
-inline size_t lnk_carve(size_t& at, size_t bytes) {
-  const size_t here = at;
-  at += (bytes + LNK_ALIGN - 1) / LNK_ALIGN * LNK_ALIGN;
-  return here;
-}
-
 // lays the scratch arrays of LinkArgs out from `base` (nullptr: only the size is wanted; else the
 // bytes at the front that every call zeroes)
 inline size_t lnk_layout(LinkArgs& a, char* base, long long n, int ndim, long long n_levels) {
   size_t at = 0;
   const size_t N = (size_t)(n > 0 ? n : 1), L = (size_t)n_levels + 1;
   // the words that every call zeroes come first, in one block
-  a.used = (int*)(base + lnk_carve(at, N * sizeof(int)));
-  a.nbirth = (int*)(base + lnk_carve(at, L * sizeof(int)));
+  a.used = (int*)(base + carve(at, N * sizeof(int)));
+  a.nbirth = (int*)(base + carve(at, L * sizeof(int)));
   const size_t zeroed = at;
-  a.spos = (double*)(base + lnk_carve(at, N * ndim * sizeof(double)));
-  a.cand_d2 = (double*)(base + lnk_carve(at, N * LNK_MAXC * sizeof(double)));
-  a.cand_row = (int*)(base + lnk_carve(at, N * LNK_MAXC * sizeof(int)));
+  a.spos = (double*)(base + carve(at, N * ndim * sizeof(double)));
+  a.cand_d2 = (double*)(base + carve(at, N * LNK_MAXC * sizeof(double)));
+  a.cand_row = (int*)(base + carve(at, N * LNK_MAXC * sizeof(int)));
   int** per_row[] = {&a.ncand, &a.link, &a.lab_d, &a.lab_s, &a.cnt_s, &a.head_d, &a.head_s,
                      &a.next_d, &a.next_s, &a.roots, &a.rank, &a.anc};
-  for (int** p : per_row) *p = (int*)(base + lnk_carve(at, N * sizeof(int)));
-  a.base = (long long*)(base + lnk_carve(at, L * sizeof(long long)));
+  for (int** p : per_row) *p = (int*)(base + carve(at, N * sizeof(int)));
+  a.base = (long long*)(base + carve(at, L * sizeof(long long)));
   if (!base) return at;
   return zeroed;
 }

@@ -20,6 +20,7 @@
 constexpr int LOC_THREADS = 256;
 constexpr int LOC_TX = 64;                  // tile width = one wave = one mask word
 constexpr int LOC_CHUNK_WORDS = 4 * LOC_THREADS;   // mask words per compaction block
+constexpr int LOC_SCAN_THREADS = 1024;      // the one workgroup of loc_scan_kernel
 
 // ---- order-preserving keys ------------------------------------------------------------------
 template <typename T> struct LocKey;
@@ -405,43 +406,24 @@ loc_count_kernel(const unsigned long long* __restrict__ mask, long long W, int c
 
 // one workgroup: exclusive scan of the chunk counts in (frame, chunk) order -> chunk bases,
 // frame offsets and the total
-__global__ void __launch_bounds__(1024)
+__global__ void __launch_bounds__(LOC_SCAN_THREADS)
 loc_scan_kernel(const long long* __restrict__ count, long long n_chunks, int cpf, long long n_frames,
                 long long* __restrict__ base, int64_t* __restrict__ frame_offset, int64_t* __restrict__ total) {
-  __shared__ long long s[1024];
-  __shared__ long long carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (long long b0 = 0; b0 < n_chunks; b0 += 1024) {
-    const long long i = b0 + threadIdx.x;
-    const long long v = i < n_chunks ? count[i] : 0;
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const long long add = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0;
-      __syncthreads();
-      s[threadIdx.x] += add;
-      __syncthreads();
-    }
-    const long long excl = carry + s[threadIdx.x] - v;
-    if (i < n_chunks) {
-      base[i] = excl;
-      if (i % cpf == 0) frame_offset[i / cpf] = excl;
-    }
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = excl + v;
-    __syncthreads();
-  }
+  const long long n = workgroup_scan_n<LOC_SCAN_THREADS, long long>(
+      n_chunks, [&](long long i) { return count[i]; },
+      [&](long long i, long long before) {
+        base[i] = before;
+        if (i % cpf == 0) frame_offset[i / cpf] = before;
+      });
   if (threadIdx.x == 0) {
-    frame_offset[n_frames] = carry;
-    *total = carry;
+    frame_offset[n_frames] = n;
+    *total = n;
   }
 }
 
 __global__ void __launch_bounds__(LOC_THREADS)
 loc_write_kernel(const unsigned long long* __restrict__ mask, const LocGeom g, int cpf,
                  const long long* __restrict__ base, long long capacity, int32_t* __restrict__ pos) {
-  __shared__ long long s[LOC_THREADS];
   const long long frame = blockIdx.x / cpf, chunk = blockIdx.x % cpf;
   const unsigned long long* m = mask + frame * g.W;
   unsigned long long wd[4];
@@ -451,15 +433,8 @@ loc_write_kernel(const unsigned long long* __restrict__ mask, const LocGeom g, i
     wd[k] = w < g.W ? m[w] : 0ull;
     c += __popcll(wd[k]);
   }
-  s[threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 1; o < LOC_THREADS; o <<= 1) {
-    const long long add = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0;
-    __syncthreads();
-    s[threadIdx.x] += add;
-    __syncthreads();
-  }
-  long long row = base[blockIdx.x] + s[threadIdx.x] - c;
+  long long in_chunk;
+  long long row = base[blockIdx.x] + workgroup_scan<LOC_THREADS, long long>(c, in_chunk);
   for (int k = 0; k < 4; ++k) {
     unsigned long long bits = wd[k];
     if (!bits) continue;

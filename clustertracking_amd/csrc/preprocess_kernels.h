@@ -1,6 +1,6 @@
 // preprocess_kernels.h -- bandpass, lowpass and rescaling of whole frames on the device
 // (include/ctrefine.h: ctr_preprocess_device).  Included by tu_preprocess.hip inside
-// its anonymous namespace.
+// its anonymous namespace, after stage_common.h (ordered_key).
 //
 // Two separable stencils over the same pixels: a Gaussian (SciPy's correlate1d, symmetric order,
 // zero beyond the frame, float64) and a box (SciPy's uniform_filter1d in the pixel type, edge
@@ -45,15 +45,6 @@ template <> struct PreAcc<double> { typedef double type; };
 template <typename T> struct PreOut { typedef T type; };
 template <> struct PreOut<float> { typedef uint8_t type; };
 template <> struct PreOut<double> { typedef uint8_t type; };
-
-// order-preserving key of a float64 (any sign), so that an unsigned atomicMax finds the maximum
-__device__ __forceinline__ unsigned long long pre_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double pre_unkey(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
 
 // per-frame maximum: wavefront reduction, then one vector atomic per wavefront
 __device__ __forceinline__ void pre_max_commit(unsigned long long key, unsigned long long* slot) {
@@ -208,7 +199,7 @@ __global__ __launch_bounds__(PRE_THREADS) void pre_yx_kernel(const GIN* __restri
     const long long o = slice * plane + (long long)y * g.nx + x;
     if (out_mode == PRE_OUT_BAND) band[o] = v;
     else if (out_mode == PRE_OUT_SCALED) out[o] = pre_to_gamut<typename PreOut<T>::type>(v, sc);
-    const unsigned long long k = pre_key(v);
+    const unsigned long long k = ordered_key(v);   // never NaN: the threshold test made one 0
     key = k > key ? k : key;
   }
   if (maxkey) pre_max_commit(key, maxkey + frame);
@@ -222,7 +213,8 @@ __global__ __launch_bounds__(PRE_THREADS) void pre_plane_max_kernel(const S* __r
   const S* p = src + frame * E;
   unsigned long long key = 0;
   for (long long i = (long long)(blockIdx.x % bpf) * PRE_THREADS + threadIdx.x; i < E; i += (long long)bpf * PRE_THREADS) {
-    const unsigned long long k = pre_key((double)p[i]);
+    // the plain key: a NaN pixel has no defined result (include/ctrefine.h), so no rule for it
+    const unsigned long long k = ordered_key((double)p[i]);
     key = k > key ? k : key;
   }
   pre_max_commit(key, maxkey + frame);
@@ -234,7 +226,7 @@ __global__ void pre_scale_factor_kernel(const unsigned long long* __restrict__ m
                                         double* __restrict__ scale) {
   const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= n_frames) return;
-  const double m = pre_unkey(maxkey[f]);
+  const double m = ordered_unkey(maxkey[f]);
   scale[f] = m == 0. ? __longlong_as_double(0x7ff0000000000000LL) : gamut / m;
 }
 

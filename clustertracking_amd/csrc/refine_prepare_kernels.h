@@ -2,14 +2,13 @@
 // include/ctrefine.h has the rule): cluster labels, the grouped order, the clusters'
 // row ranges, the bounds and the feasibility of the box; and the scatter of the fit's results back
 // into input row order.  Included by tu_refine_prepare.hip inside its anonymous namespace, after
-// device_common.h (scaled_dist2).  The kernel boundary is the only synchronisation between
+// device_common.h and stage_common.h.  The kernel boundary is the only synchronisation between
 // workgroups; every loop is bounded by the launch's arguments or, for the rows of a frame, by offsets
 // that rp_setup_kernel has checked against them; integer atomicAdd / atomicMin only.
 #ifndef CTREFINE_REFINE_PREPARE_KERNELS_H
 #define CTREFINE_REFINE_PREPARE_KERNELS_H
 
 constexpr int RP_THREADS = 256;              // a workgroup of every kernel here: 4 wavefronts
-constexpr unsigned RP_MAX_GRID = 1u << 16;   // grid-stride kernels
 
 struct RpArgs {
   int ndim, np;
@@ -50,17 +49,6 @@ struct RpBounds {
   double abs[2 * CTR_MAX_PARAMS], diff[2 * CTR_MAX_PARAMS], rel[2 * CTR_MAX_PARAMS];
 };
 
-__device__ __forceinline__ int rp_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rp_store(int* p, int v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the labels of a frame belong to its workgroup alone
-__device__ __forceinline__ int rp_label(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
 // The caller's offsets, before any kernel follows one: from 0 to N, never falling.  Every row:
 // its scaled position (the division NumPy does for cKDTree(pos / separation)), its own label, no
 // member.  status[0] was zeroed in front of this kernel.
@@ -69,11 +57,9 @@ __global__ void __launch_bounds__(RP_THREADS) rp_setup_kernel(const RpArgs a) {
   const long long n = a.T + 1 > a.N ? a.T + 1 : a.N;
   bool bad = false;
   for (long long i = (long long)blockIdx.x * RP_THREADS + threadIdx.x; i < n; i += stride) {
-    if (i <= a.T) {
-      const long long o = a.frame_offset[i];
-      bad |= o < 0 || o > a.N || (i == 0 && o != 0) || (i == a.T && o != a.N);
-      if (i < a.T) bad |= a.frame_offset[i + 1] < o;
-    }
+    if (i <= a.T)
+      bad |= offsets_bad(a.frame_offset, i, a.T, a.N) || (i == 0 && a.frame_offset[0] != 0) ||
+             (i == a.T && a.frame_offset[i] != a.N);
     if (i < a.N) {
       for (int d = 0; d < a.ndim; ++d) a.spos[i * a.ndim + d] = a.pos[i * a.ndim + d] / a.sep[d];
       a.label[i] = (int)i;
@@ -81,58 +67,21 @@ __global__ void __launch_bounds__(RP_THREADS) rp_setup_kernel(const RpArgs a) {
     }
     if (i == 0) a.status[1] = a.np;
   }
-  if (bad) rp_store(a.status, CTR_PREPARE_BAD_TABLE);
+  if (bad) st_agent(a.status, CTR_PREPARE_BAD_TABLE);
 }
 
-// One workgroup per frame.  Labels: every row takes the smallest label among the rows within the
-// scaled distance 1 (tiles of RP_THREADS scaled positions through LDS; the labels themselves are
-// read where they live, so a sweep sees what it has already lowered) and then the label of that
-// label, which is a row of the same cluster with a label no larger; sweeps until one changes
-// nothing.  A label only falls and always names a row of the cluster, so the fixed point is the
-// smallest row of the connected component, and rows + 1 sweeps reach it on any input.  Then the
-// members per root, and per row its place in the frame's order by (label, row): the rows with a
-// smaller label, or the same label and a smaller index (tiles of labels through LDS).
+// One workgroup per frame.  Labels by label_frame (stage_common.h).  Then the members per root, and
+// per row its place in the frame's order by (label, row): the rows with a smaller label, or the
+// same label and a smaller index (tiles of labels through LDS).
 template <int ND>
 __global__ void __launch_bounds__(RP_THREADS) rp_label_kernel(const RpArgs a) {
   __shared__ double s_pos[RP_THREADS * ND];
   __shared__ int s_lab[RP_THREADS];
-  if (rp_load(a.status) != CTR_PREPARE_OK) return;
+  if (ld_agent(a.status) != CTR_PREPARE_OK) return;
   const int tid = threadIdx.x;
   for (long long f = blockIdx.x; f < a.T; f += gridDim.x) {
     const int r0 = (int)a.frame_offset[f], r1 = (int)a.frame_offset[f + 1];
-    for (int sweep = 0; sweep <= r1 - r0; ++sweep) {
-      bool changed = false;
-      for (int base = r0; base < r1; base += RP_THREADS) {
-        const int i = base + tid;
-        const bool act = i < r1;
-        double p[ND];
-#pragma unroll
-        for (int d = 0; d < ND; ++d) p[d] = act ? a.spos[(size_t)i * ND + d] : 0.;
-        const int mine = act ? rp_label(a.label + i) : 0;
-        int m = mine;
-        for (int tb = r0; tb < r1; tb += RP_THREADS) {
-          __syncthreads();
-          if (tb + tid < r1) {
-#pragma unroll
-            for (int d = 0; d < ND; ++d) s_pos[tid * ND + d] = a.spos[(size_t)(tb + tid) * ND + d];
-          }
-          __syncthreads();
-          const int n = r1 - tb < RP_THREADS ? r1 - tb : RP_THREADS;
-          if (act)
-            for (int q = 0; q < n; ++q)
-              if (scaled_dist2<ND>(p, s_pos + q * ND) <= 1.) {
-                const int lj = rp_label(a.label + tb + q);
-                m = lj < m ? lj : m;
-              }
-        }
-        if (act && m < mine) {
-          const int mm = rp_label(a.label + m);
-          __hip_atomic_store(a.label + i, mm < m ? mm : m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          changed = true;
-        }
-      }
-      if (!__syncthreads_or(changed ? 1 : 0)) break;
-    }
+    label_frame<ND, RP_THREADS>(a.spos, a.label, r0, r1, s_pos);
     for (int i = r0 + tid; i < r1; i += RP_THREADS) atomicAdd(a.count + a.label[i], 1);
     int roots = 0;
     for (int base = r0; base < r1; base += RP_THREADS) {
@@ -154,7 +103,7 @@ __global__ void __launch_bounds__(RP_THREADS) rp_label_kernel(const RpArgs a) {
       }
       roots += __syncthreads_count(act && li == i ? 1 : 0);
       if (!act) continue;
-      a.size[i] = rp_load(a.count + li);
+      a.size[i] = ld_agent(a.count + li);
       a.rank[i] = rank;
       a.order[r0 + rank] = i;
       if (li == i) a.local[i] = before;
@@ -167,36 +116,13 @@ __global__ void __launch_bounds__(RP_THREADS) rp_label_kernel(const RpArgs a) {
 // one workgroup: exclusive scan of the clusters per frame in place, n_clusters = their sum, and the
 // end of the last cluster's rows; a refused table has no cluster
 __global__ void __launch_bounds__(RP_THREADS) rp_scan_kernel(const RpArgs a) {
-  __shared__ int s_wave[RP_THREADS / 64], s_carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (rp_load(a.status) != CTR_PREPARE_OK) {
-    if (tid == 0) { *a.n_clusters = 0; a.feat_offset[0] = 0; }
+  if (ld_agent(a.status) != CTR_PREPARE_OK) {
+    if (threadIdx.x == 0) { *a.n_clusters = 0; a.feat_offset[0] = 0; }
     return;
   }
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
-  for (long long c = 0; c < a.T; c += RP_THREADS) {
-    const int v = c + tid < a.T ? a.cbase[c + tid] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = s_carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < RP_THREADS / 64; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    if (c + tid < a.T) a.cbase[c + tid] = before + incl - v;
-    __syncthreads();
-    if (tid == 0) s_carry += total;
-    __syncthreads();
-  }
-  if (tid == 0) { *a.n_clusters = s_carry; a.feat_offset[s_carry] = (int)a.N; }
+  const int C = workgroup_scan_n<RP_THREADS, int>(
+      a.T, [&](long long i) { return a.cbase[i]; }, [&](long long i, int before) { a.cbase[i] = before; });
+  if (threadIdx.x == 0) { *a.n_clusters = C; a.feat_offset[C] = (int)a.N; }
 }
 
 // np.fmax / np.fmin as NumPy's scalar loop writes them: the other operand where one is NaN
@@ -239,7 +165,7 @@ __device__ __forceinline__ void rp_bounds(double p, const RpBounds& b, int k, do
 // One workgroup per frame: the roots write their cluster's row range and frame, every value of the
 // frame's rows goes to its place in the grouped order with its bounds.
 __global__ void __launch_bounds__(RP_THREADS) rp_tables_kernel(const RpArgs a, const RpBounds b) {
-  if (rp_load(a.status) != CTR_PREPARE_OK) return;
+  if (ld_agent(a.status) != CTR_PREPARE_OK) return;
   const int tid = threadIdx.x, np = a.np;
   for (long long f = blockIdx.x; f < a.T; f += gridDim.x) {
     const int r0 = (int)a.frame_offset[f], r1 = (int)a.frame_offset[f + 1];
@@ -266,7 +192,7 @@ __global__ void __launch_bounds__(RP_THREADS) rp_tables_kernel(const RpArgs a, c
 // prepare_batch's check of the box: per row for a parameter of mode var, after the loosest bound
 // over the cluster for a shared one; the smallest offending parameter goes to status[1]
 __global__ void __launch_bounds__(RP_THREADS) rp_feasible_kernel(const RpArgs a) {
-  if (rp_load(a.status) == CTR_PREPARE_BAD_TABLE) return;
+  if (ld_agent(a.status) == CTR_PREPARE_BAD_TABLE) return;
   const long long stride = (long long)gridDim.x * RP_THREADS;
   const int C = *a.n_clusters, np = a.np;
   int worst = np;
@@ -291,7 +217,7 @@ __global__ void __launch_bounds__(RP_THREADS) rp_feasible_kernel(const RpArgs a)
   }
   if (worst < np) {
     atomicMin(a.status + 1, worst);
-    rp_store(a.status, CTR_PREPARE_INFEASIBLE);
+    st_agent(a.status, CTR_PREPARE_INFEASIBLE);
   }
 }
 

@@ -7,26 +7,14 @@
 
 namespace {
 
+#include "stage_common.h"
 #include "cluster_track_kernels.h"
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-unsigned stride_grid(long long n) {
-  const long long g = (n + CTK_THREADS - 1) / CTK_THREADS;
-  return g < 1 ? 1u : g > (long long)CTK_MAX_GRID ? CTK_MAX_GRID : (unsigned)g;
-}
 
 int ceil_log2(long long n) {
   int l = 0;
   while ((1LL << l) < n) ++l;
   return l;
 }
-
-#define CTK_TRY(call)                                                              \
-  do {                                                                             \
-    const hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) { *msg = hipGetErrorString(e_); return CTR_ERR_DEVICE; } \
-  } while (0)
 
 }  // namespace
 
@@ -45,9 +33,9 @@ int ctr_cluster_tracks_launch(const ctr_cluster_tracks* c, StageRun* stage, cons
   // a tree with an edge to another tree is merged within two rounds; one more round hooks nothing
   const int L = ceil_log2(P), R = 2 * L + 2, J = L + 1;
   const long long nb = (P + CTK_THREADS - 1) / CTK_THREADS;
-  const size_t o_flags = 0, o_A = o_flags + align_up(4 * (size_t)R * (J + 1)), o_B = o_A + align_up(4 * (size_t)P),
-               o_size = o_B + align_up(4 * (size_t)P), o_num = o_size + align_up(4 * (size_t)P),
-               o_bs = o_num + align_up(4 * (size_t)P), total = o_bs + align_up(4 * (size_t)(nb + 1));
+  size_t total = 0;
+  const size_t o_flags = carve(total, 4 * (size_t)R * (J + 1)), o_A = carve(total, 4 * (size_t)P), o_B = carve(total, 4 * (size_t)P),
+               o_size = carve(total, 4 * (size_t)P), o_num = carve(total, 4 * (size_t)P), o_bs = carve(total, 4 * (size_t)(nb + 1));
   if (plan) { plan->scratch_bytes = (long long)total; plan->max_rounds = R; plan->jumps_per_round = J; }
   if (stage->mode == STAGE_CHECK_SCALARS) return CTR_OK;
   if (!c->status) { *msg = "null status"; return CTR_ERR_INVALID; }
@@ -76,13 +64,13 @@ int ctr_cluster_tracks_launch(const ctr_cluster_tracks* c, StageRun* stage, cons
   a.status = c->status;
   const dim3 block(CTK_THREADS);
   if (c->phase == CTR_TRACKS_PAIRS) {
-    CTK_TRY(hipMemsetAsync(c->status, 0, sizeof(int32_t), s));
+    STAGE_TRY(hipMemsetAsync(c->status, 0, sizeof(int32_t), s));
     long long n = a.T + 1 > a.N ? a.T + 1 : a.N;
     n = M > n ? M : n;
-    hipLaunchKernelGGL(ctk_setup_kernel, dim3(stride_grid(n)), block, 0, s, a, 1);
+    hipLaunchKernelGGL(ctk_setup_kernel, dim3(stride_grid(n, CTK_THREADS)), block, 0, s, a, 1);
     if (a.T > 0 && a.N > 0)
-      hipLaunchKernelGGL(ctk_groups_kernel, dim3(a.T < (long long)CTK_MAX_GRID ? (unsigned)a.T : CTK_MAX_GRID), block, 0, s, a);
-    CTK_TRY(hipGetLastError());
+      hipLaunchKernelGGL(ctk_groups_kernel, dim3(frame_grid(a.T)), block, 0, s, a);
+    STAGE_TRY(hipGetLastError());
     return CTR_OK;
   }
   a.flags = (int*)(ws + o_flags);
@@ -96,8 +84,8 @@ int ctr_cluster_tracks_launch(const ctr_cluster_tracks* c, StageRun* stage, cons
   a.n_tracks = c->n_tracks;
   a.n_members = c->n_members;
   a.n_rounds = c->n_rounds;
-  CTK_TRY(hipMemsetAsync(ws + o_flags, 0, align_up(4 * (size_t)R * (J + 1)), s));
-  const dim3 gP(stride_grid(P)), gM(stride_grid(M));
+  STAGE_TRY(hipMemsetAsync(ws + o_flags, 0, o_A - o_flags, s));
+  const dim3 gP(stride_grid(P, CTK_THREADS)), gM(stride_grid(M, CTK_THREADS));
   hipLaunchKernelGGL(ctk_init_kernel, gP, block, 0, s, a);
   bool synced = false;
   for (int r = 0; r < R && M > 0 && P > 1; ++r) {
@@ -105,20 +93,20 @@ int ctr_cluster_tracks_launch(const ctr_cluster_tracks* c, StageRun* stage, cons
     for (int j = 0; j < J; ++j) hipLaunchKernelGGL(ctk_jump_kernel, gP, block, 0, s, a, r, j);
     if (c->check_every > 0 && (r + 1) % c->check_every == 0) {
       int hooked = 0;
-      CTK_TRY(hipMemcpyAsync(&hooked, a.flags + (size_t)r * (J + 1), sizeof(int), hipMemcpyDeviceToHost, s));
-      CTK_TRY(hipStreamSynchronize(s));
+      STAGE_TRY(hipMemcpyAsync(&hooked, a.flags + (size_t)r * (J + 1), sizeof(int), hipMemcpyDeviceToHost, s));
+      STAGE_TRY(hipStreamSynchronize(s));
       synced = true;
       if (!hooked) break;
     }
   }
-  hipLaunchKernelGGL(ctk_verify_kernel, dim3(stride_grid(M > P ? M : P)), block, 0, s, a);
+  hipLaunchKernelGGL(ctk_verify_kernel, dim3(stride_grid(M > P ? M : P, CTK_THREADS)), block, 0, s, a);
   hipLaunchKernelGGL(ctk_count_kernel, gP, block, 0, s, a);
   if (nb > 0) hipLaunchKernelGGL(ctk_blocksum_kernel, dim3((unsigned)nb), block, 0, s, a);
   hipLaunchKernelGGL(ctk_scan_kernel, dim3(1), block, 0, s, a, nb);
   if (nb > 0) hipLaunchKernelGGL(ctk_number_kernel, dim3((unsigned)nb), block, 0, s, a);
   hipLaunchKernelGGL(ctk_assign_kernel, gP, block, 0, s, a);
-  CTK_TRY(hipGetLastError());
-  if (synced) CTK_TRY(hipStreamSynchronize(s));
+  STAGE_TRY(hipGetLastError());
+  if (synced) STAGE_TRY(hipStreamSynchronize(s));
   return CTR_OK;
 }
 
@@ -155,18 +143,18 @@ int ctr_track_positions_launch(const ctr_track_positions* p, StageRun* stage, co
   a.pos_out = p->pos_out;
   a.status = p->status;
   const dim3 block(CTK_THREADS);
-  CTK_TRY(hipMemsetAsync(p->status, 0, sizeof(int32_t), s));
+  STAGE_TRY(hipMemsetAsync(p->status, 0, sizeof(int32_t), s));
   long long n = a.T + 1 > a.N ? a.T + 1 : a.N;
   n = a.P > n ? a.P : n;
-  hipLaunchKernelGGL(ctk_setup_kernel, dim3(stride_grid(n)), block, 0, s, a, 0);
+  hipLaunchKernelGGL(ctk_setup_kernel, dim3(stride_grid(n, CTK_THREADS)), block, 0, s, a, 0);
   if (cells > 0) {
-    const dim3 gT(a.T < (long long)CTK_MAX_GRID ? (unsigned)a.T : CTK_MAX_GRID);
-    hipLaunchKernelGGL(ctk_fill_kernel, dim3(stride_grid(cells * a.cs * a.ndim)), block, 0, s, a);
+    const dim3 gT(frame_grid(a.T));
+    hipLaunchKernelGGL(ctk_fill_kernel, dim3(stride_grid(cells * a.cs * a.ndim, CTK_THREADS)), block, 0, s, a);
     if (a.N > 0) {
       hipLaunchKernelGGL(ctk_present_kernel, gT, block, 0, s, a);
       hipLaunchKernelGGL(ctk_scatter_kernel, gT, block, 0, s, a);
     }
   }
-  CTK_TRY(hipGetLastError());
+  STAGE_TRY(hipGetLastError());
   return CTR_OK;
 }

@@ -13,6 +13,7 @@
 namespace {
 
 #include "device_common.h"
+#include "stage_common.h"
 #include "link_kernels.h"
 #include "findlink_kernels.h"
 
@@ -22,27 +23,27 @@ size_t layout(FlArgs& a, char* base, int ndim, long long n_levels) {
   size_t at = lnk_layout(a.l, nullptr, a.ncap, ndim, n_levels);
   const size_t zeroed = base ? lnk_layout(a.l, base, a.ncap, ndim, n_levels) : 0;
   const size_t N = (size_t)a.ncap, L = (size_t)n_levels + 1, Q = (size_t)a.Q, K = (size_t)a.K, Z = (size_t)a.nsz;
-  a.start = (long long*)(base + lnk_carve(at, L * sizeof(long long)));
-  a.cnt = (int*)(base + lnk_carve(at, L * sizeof(int)));
-  a.ppos = (double*)(base + lnk_carve(at, N * ndim * sizeof(double)));
-  a.pmass = (double*)(base + lnk_carve(at, N * sizeof(double)));
-  a.psignal = (double*)(base + lnk_carve(at, N * sizeof(double)));
-  a.psize = (double*)(base + lnk_carve(at, N * Z * sizeof(double)));
-  a.pparticle = (long long*)(base + lnk_carve(at, N * sizeof(long long)));
+  a.start = (long long*)(base + carve(at, L * sizeof(long long)));
+  a.cnt = (int*)(base + carve(at, L * sizeof(int)));
+  a.ppos = (double*)(base + carve(at, N * ndim * sizeof(double)));
+  a.pmass = (double*)(base + carve(at, N * sizeof(double)));
+  a.psignal = (double*)(base + carve(at, N * sizeof(double)));
+  a.psize = (double*)(base + carve(at, N * Z * sizeof(double)));
+  a.pparticle = (long long*)(base + carve(at, N * sizeof(long long)));
   int** per_row[] = {&a.preloc, &a.pquery, &a.sn_ns, &a.sn_nd, &a.mrg, &a.m_ns, &a.m_nd, &a.qof, &a.nmnb};
-  for (int** p : per_row) *p = (int*)(base + lnk_carve(at, N * sizeof(int)));
-  a.mnb = (int*)(base + lnk_carve(at, N * LNK_MAXC * sizeof(int)));
-  a.q_soff = (long long*)(base + lnk_carve(at, (Q + 1) * sizeof(long long)));
-  a.q_frame = (long long*)(base + lnk_carve(at, Q * sizeof(long long)));
-  a.q_spos = (double*)(base + lnk_carve(at, Q * LNK_MAX_SRC * ndim * sizeof(double)));
+  for (int** p : per_row) *p = (int*)(base + carve(at, N * sizeof(int)));
+  a.mnb = (int*)(base + carve(at, N * LNK_MAXC * sizeof(int)));
+  a.q_soff = (long long*)(base + carve(at, (Q + 1) * sizeof(long long)));
+  a.q_frame = (long long*)(base + carve(at, Q * sizeof(long long)));
+  a.q_spos = (double*)(base + carve(at, Q * LNK_MAX_SRC * ndim * sizeof(double)));
   int** per_query[] = {&a.q_root, &a.q_short, &a.q_fill, &a.r_found, &a.r_status};
-  for (int** p : per_query) *p = (int*)(base + lnk_carve(at, Q * sizeof(int)));
-  a.n_q = (int*)(base + lnk_carve(at, sizeof(int)));
-  a.r_pos = (int*)(base + lnk_carve(at, Q * K * ndim * sizeof(int)));
-  a.r_mass = (double*)(base + lnk_carve(at, Q * K * sizeof(double)));
-  a.r_signal = (double*)(base + lnk_carve(at, Q * K * sizeof(double)));
-  a.r_size = (double*)(base + lnk_carve(at, Q * K * Z * sizeof(double)));
-  a.claim = (int*)(base + lnk_carve(at, Q * K * sizeof(int)));
+  for (int** p : per_query) *p = (int*)(base + carve(at, Q * sizeof(int)));
+  a.n_q = (int*)(base + carve(at, sizeof(int)));
+  a.r_pos = (int*)(base + carve(at, Q * K * ndim * sizeof(int)));
+  a.r_mass = (double*)(base + carve(at, Q * K * sizeof(double)));
+  a.r_signal = (double*)(base + carve(at, Q * K * sizeof(double)));
+  a.r_size = (double*)(base + carve(at, Q * K * Z * sizeof(double)));
+  a.claim = (int*)(base + carve(at, Q * K * sizeof(int)));
   return base ? zeroed : at;
 }
 

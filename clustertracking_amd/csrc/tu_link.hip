@@ -10,6 +10,7 @@
 namespace {
 
 #include "device_common.h"
+#include "stage_common.h"
 #include "link_kernels.h"
 
 template <int ND>

@@ -12,6 +12,7 @@
 
 namespace {
 
+#include "stage_common.h"
 #include "locate_kernels.h"
 
 constexpr size_t LOC_LDS_MAX = 64 * 1024;
@@ -66,7 +67,7 @@ int run(const ctr_locate* l, const LocGeom& g, hipStream_t s, const char** msg) 
     }
     hipLaunchKernelGGL(loc_count_kernel, dim3((unsigned)(cpf * F)), dim3(LOC_THREADS), 0, s,
                        (const unsigned long long*)keep, g.W, cpf, count);
-    hipLaunchKernelGGL(loc_scan_kernel, dim3(1), dim3(1024), 0, s, (const long long*)count, (long long)cpf * F, cpf,
+    hipLaunchKernelGGL(loc_scan_kernel, dim3(1), dim3(LOC_SCAN_THREADS), 0, s, (const long long*)count, (long long)cpf * F, cpf,
                        F, base, l->frame_offset, l->total);
     hipLaunchKernelGGL(loc_write_kernel, dim3((unsigned)(cpf * F)), dim3(LOC_THREADS), 0, s,
                        (const unsigned long long*)keep, g, cpf, (const long long*)base, (long long)l->capacity,

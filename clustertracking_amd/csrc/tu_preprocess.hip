@@ -13,6 +13,7 @@
 
 namespace {
 
+#include "stage_common.h"
 #include "preprocess_kernels.h"
 
 constexpr size_t PRE_LDS_MAX = 64 * 1024;

@@ -12,20 +12,8 @@
 namespace {
 
 #include "device_common.h"
+#include "stage_common.h"
 #include "refine_prepare_kernels.h"
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-unsigned stride_grid(long long n) {
-  const long long g = (n + RP_THREADS - 1) / RP_THREADS;
-  return g < 1 ? 1u : g > (long long)RP_MAX_GRID ? RP_MAX_GRID : (unsigned)g;
-}
-
-#define RP_TRY(call)                                                               \
-  do {                                                                             \
-    const hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) { *msg = hipGetErrorString(e_); return CTR_ERR_DEVICE; } \
-  } while (0)
 
 }  // namespace
 
@@ -47,9 +35,9 @@ int ctr_refine_prepare_launch(const ctr_refine_prepare* r, StageRun* stage, cons
         *msg = "modes must be const, var or cluster"; return CTR_ERR_INVALID;
       }
   } else if (r->n_clusters > N) { *msg = "more clusters than features"; return CTR_ERR_INVALID; }
-  const size_t o_spos = 0, o_count = o_spos + align_up(8 * (size_t)N * r->ndim), o_rank = o_count + align_up(4 * (size_t)N),
-               o_local = o_rank + align_up(4 * (size_t)N), o_cbase = o_local + align_up(4 * (size_t)N),
-               total = batch ? o_cbase + align_up(4 * (size_t)(T + 1)) : 0;
+  size_t at = 0;
+  const size_t o_spos = carve(at, 8 * (size_t)N * r->ndim), o_count = carve(at, 4 * (size_t)N), o_rank = carve(at, 4 * (size_t)N),
+               o_local = carve(at, 4 * (size_t)N), o_cbase = carve(at, 4 * (size_t)(T + 1)), total = batch ? at : 0;
   if (scratch_bytes) *scratch_bytes = (long long)total;
   if (stage->mode == STAGE_CHECK_SCALARS) return CTR_OK;
   if (batch) {
@@ -81,8 +69,8 @@ int ctr_refine_prepare_launch(const ctr_refine_prepare* r, StageRun* stage, cons
     if (N == 0) return CTR_OK;
     a.fit_params = r->fit_params; a.fit_cost = r->fit_cost; a.fit_std = r->fit_std;
     a.params_out = r->params_out; a.cost_out = r->cost_out; a.std_out = r->std_out;
-    hipLaunchKernelGGL(rp_scatter_kernel, dim3(stride_grid(N * a.np)), block, 0, s, a);
-    RP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rp_scatter_kernel, dim3(stride_grid(N * a.np, RP_THREADS)), block, 0, s, a);
+    STAGE_TRY(hipGetLastError());
     return CTR_OK;
   }
   char* ws = (char*)stage->scratch;
@@ -104,20 +92,20 @@ int ctr_refine_prepare_launch(const ctr_refine_prepare* r, StageRun* stage, cons
   a.n_clusters = r->n_clusters_out;
   a.params = r->params; a.low = r->low; a.high = r->high;
   a.status = r->status;
-  RP_TRY(hipMemsetAsync(r->status, 0, 2 * sizeof(int32_t), s));
-  hipLaunchKernelGGL(rp_setup_kernel, dim3(stride_grid(T + 1 > N ? T + 1 : N)), block, 0, s, a);
-  const dim3 gT(T < (long long)RP_MAX_GRID ? (unsigned)T : RP_MAX_GRID);
+  STAGE_TRY(hipMemsetAsync(r->status, 0, 2 * sizeof(int32_t), s));
+  hipLaunchKernelGGL(rp_setup_kernel, dim3(stride_grid(T + 1 > N ? T + 1 : N, RP_THREADS)), block, 0, s, a);
+  const dim3 gT(frame_grid(T));
   if (T > 0 && N > 0) {
     if (r->ndim == 2) hipLaunchKernelGGL(rp_label_kernel<2>, gT, block, 0, s, a);
     else hipLaunchKernelGGL(rp_label_kernel<3>, gT, block, 0, s, a);
   } else if (T > 0) {
-    RP_TRY(hipMemsetAsync(a.cbase, 0, 4 * (size_t)T, s));   // frames without a row: no cluster
+    STAGE_TRY(hipMemsetAsync(a.cbase, 0, 4 * (size_t)T, s));   // frames without a row: no cluster
   }
   hipLaunchKernelGGL(rp_scan_kernel, dim3(1), block, 0, s, a);
   if (T > 0 && N > 0) {
     hipLaunchKernelGGL(rp_tables_kernel, gT, block, 0, s, a, b);
-    hipLaunchKernelGGL(rp_feasible_kernel, dim3(stride_grid(N)), block, 0, s, a);
+    hipLaunchKernelGGL(rp_feasible_kernel, dim3(stride_grid(N, RP_THREADS)), block, 0, s, a);
   }
-  RP_TRY(hipGetLastError());
+  STAGE_TRY(hipGetLastError());
   return CTR_OK;
 }

@@ -13,6 +13,7 @@
 namespace {
 
 #include "device_common.h"
+#include "stage_common.h"
 #include "locate_kernels.h"
 #include "characterize_kernels.h"
 #include "relocate_kernels.h"

@@ -8,6 +8,7 @@
 namespace {
 
 #include "device_common.h"
+#include "stage_common.h"
 #include "frame_max_kernels.h"
 #include "train_kernels.h"
 
@@ -25,8 +26,6 @@ const void* accumulate_kernel(int ndim, int iso, int fit) {
   if (ndim == 2) return iso ? accumulate_fit<2, true>(fit) : accumulate_fit<2, false>(fit);
   return iso ? accumulate_fit<3, true>(fit) : accumulate_fit<3, false>(fit);
 }
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -86,9 +85,9 @@ int ctr_train_launch(const ctr_train* t, StageRun* stage, const char** msg) {
   // scratch: frame maxima (encoded, decoded), the partials table, the state blocks, cluster ->
   // problem, the finished words and their count
   const size_t nF = (size_t)t->n_frames, P = (size_t)t->n_problems, C = (size_t)t->n_clusters;
-  const size_t o_enc = 0, o_fmax = o_enc + align_up(8 * nF), o_part = o_fmax + align_up(8 * nF),
-               o_state = o_part + align_up(8 * C * TRN_K), o_prob = o_state + align_up(8 * P * TS_SIZE),
-               o_done = o_prob + align_up(4 * C), total = o_done + align_up(4 * (P + 1));
+  size_t total = 0;
+  const size_t o_enc = carve(total, 8 * nF), o_fmax = carve(total, 8 * nF), o_part = carve(total, 8 * C * TRN_K),
+               o_state = carve(total, 8 * P * TS_SIZE), o_prob = carve(total, 4 * C), o_done = carve(total, 4 * (P + 1));
   stage->scratch_bytes = P > 0 ? total : 0;
   if (stage->mode != STAGE_LAUNCH || P == 0) return CTR_OK;
 
@@ -116,18 +115,12 @@ int ctr_train_launch(const ctr_train* t, StageRun* stage, const char** msg) {
   a.done = (int*)(ws + o_done);
   a.n_done = a.done + P;
 
-#define TRN_TRY(call)                                                              \
-  do {                                                                             \
-    const hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) { *msg = hipGetErrorString(e_); return CTR_ERR_DEVICE; } \
-  } while (0)
-
   // a cluster that no problem owns keeps -1 and is passed over
-  if (C) TRN_TRY(hipMemsetAsync(ws + o_prob, 0xff, 4 * C, s));
-  TRN_TRY(hipMemsetAsync(ws + o_done, 0, 4 * (P + 1), s));
+  if (C) STAGE_TRY(hipMemsetAsync(ws + o_prob, 0xff, 4 * C, s));
+  STAGE_TRY(hipMemsetAsync(ws + o_done, 0, 4 * (P + 1), s));
   if (nF) {
     bool too_large = false;
-    TRN_TRY(queue_frame_max(t->frames, t->frame_dtype, t->n_frames, E, (unsigned long long*)(ws + o_enc),
+    STAGE_TRY(queue_frame_max(t->frames, t->frame_dtype, t->n_frames, E, (unsigned long long*)(ws + o_enc),
                             (double*)(ws + o_fmax), s, &too_large));
     if (too_large) { *msg = "frame block too large for one launch"; return CTR_ERR_INVALID; }
   }
@@ -139,18 +132,17 @@ int ctr_train_launch(const ctr_train* t, StageRun* stage, const char** msg) {
   for (int i = 0; i <= t->solver_maxiter; ++i) {
     if (C) {
       void* args[] = {&a};
-      TRN_TRY(hipLaunchKernel(acc, dim3((unsigned)C), dim3(TRN_THREADS), args, 0, s));
+      STAGE_TRY(hipLaunchKernel(acc, dim3((unsigned)C), dim3(TRN_THREADS), args, 0, s));
     }
     hipLaunchKernelGGL(train_step_kernel, dim3((unsigned)P), dim3(TRN_STEP_THREADS), 0, s, a);
     if (t->check_every > 0 && (i + 1) % t->check_every == 0 && i < t->solver_maxiter) {
       int n_done = 0;
-      TRN_TRY(hipMemcpyAsync(&n_done, a.n_done, sizeof(int), hipMemcpyDeviceToHost, s));
-      TRN_TRY(hipStreamSynchronize(s));
+      STAGE_TRY(hipMemcpyAsync(&n_done, a.n_done, sizeof(int), hipMemcpyDeviceToHost, s));
+      STAGE_TRY(hipStreamSynchronize(s));
       if (n_done >= (long long)P) break;
     }
   }
-  TRN_TRY(hipGetLastError());
-  if (t->check_every > 0) TRN_TRY(hipStreamSynchronize(s));
-#undef TRN_TRY
+  STAGE_TRY(hipGetLastError());
+  if (t->check_every > 0) STAGE_TRY(hipStreamSynchronize(s));
   return CTR_OK;
 }

@@ -17,6 +17,7 @@ Case = collections.namedtuple('Case', 'frames pos off signal size background kw'
 Prepared = collections.namedtuple('Prepared', 'label cluster_size order feat_offset frame_index params low high')
 
 SHAPE_2D, SHAPE_3D = (64, 64), (16, 32, 32)
+MANY_FRAMES_T = (255, 256, 257, 513)      # frames of the cases MANY_FRAMES
 
 
 def prepare(pos, frame_offset, params0, separation, ff, bounds, radius):
@@ -212,6 +213,14 @@ def cases():
     out['shared_loosest'] = _case(SHAPE_2D, [3], two, 2., diameter=9, separation=6., background=5.,
                                   bounds=dict(background=(10., nan), background_diff=(nan, 1.)))._replace(
         background=np.array([5., 20., 20.]))
+    # many frames of 0 to 2 rows close enough to join now and then: the clusters per frame are scanned
+    # in chunks of 256 frames (a seed of their own; the frames carry nothing, the stage never reads them)
+    for n_frames in MANY_FRAMES_T:
+        own = np.random.RandomState(n_frames)
+        off = np.r_[0, np.cumsum(own.randint(0, 3, n_frames))].astype(np.int64)
+        out['frames_%d' % n_frames] = Case(np.zeros((n_frames,) + SHAPE_2D, dtype=np.uint8),
+                                           own.uniform(28., 34., (off[-1], 2)), off, 90., 1., 2.,
+                                           dict(diameter=5, separation=2.5))
 
     # ---- fitted ----
     frame = np.array([[12., 12.], [12., 50.], [30., 12.], [30., 17.], [48., 12.], [48., 17.], [52., 14.5],
@@ -235,5 +244,6 @@ def cases():
 
 PREPARE = ('tile_edges', 'no_frame', 'no_row', 'chain', 'straddle', 'exact_tie', 'pythagoras', 'aniso_3d',
            'bounds_all', 'bounds_none', 'nan_start', 'shared_loosest')
+MANY_FRAMES = tuple('frames_%d' % n for n in MANY_FRAMES_T)
 INFEASIBLE = dict(infeasible_var='signal', infeasible_shared='background')
 REFINE = ('gauss_2d', 'gauss_3d', 'ring', 'dimer', 'noise_size', 'large_70', 'outside')

@@ -3,7 +3,8 @@
 
 Launch geometry under test: every kernel runs workgroups of 256 threads (4 wavefronts of 64); a frame
 goes through LDS in tiles of 256 rows (255 / 256 / 257 rows per frame), the tracks are numbered per
-block of 256 particles by wavefront ballots (P = 63 / 64 / 65 and 255 / 256 / 257)."""
+block of 256 particles by wavefront ballots (P = 63 / 64 / 65 and 255 / 256 / 257), the block counts are scanned by one
+workgroup in chunks of 256 blocks (P = 65 535 / 65 536 / 65 537 / 131 073)."""
 import functools
 import sys
 
@@ -106,10 +107,11 @@ def test_rows_per_frame_at_the_tile(engine, rows):
         assert got.n_tracks == n_groups and (block.present == cs).all()
 
 
-@pytest.mark.parametrize('P', [63, 64, 65, 255, 256, 257, 600])
+@pytest.mark.parametrize('P', [63, 64, 65, 255, 256, 257, 600, 65535, 65536, 65537, 131073])
 def test_particles_at_the_wavefront_and_workgroup(engine, P):
     """every second pair of neighbours bonded, ids shuffled: the roots fall on both sides of the
-    ballot and block boundaries of the numbering"""
+    ballot and block boundaries of the numbering; from 65 536 particles on the scan of the block
+    counts (256, 256, 257 and 513 blocks) takes more than one chunk of its workgroup"""
     rng = np.random.RandomState(P)
     ids = rng.permutation(P).astype(np.int64)
     pairs = ids[:P // 2 * 2].reshape(-1, 2)[::2]

@@ -42,6 +42,15 @@ def test_seeded_videos(engine, index):
     check(frames, kw)
 
 
+def test_many_levels(engine):
+    """257 frames of 24 x 24 pixels with two features, one of them in and out of the margin: the
+    offsets of the frames' live rows and the first ids of the levels are scanned by one workgroup in
+    chunks of 256 levels"""
+    frames = F.video((24, 24), 257, 2, 257, drift=0.2, size=1.2, margin=3, centres=[[8., 9.], [15., 16.]])
+    got, want = check(frames, dict(diameter=5, separation=6, search_range=3, minmass=100))
+    assert len(got.frame_offset) == 258 and got.frame_offset[-1] >= 257
+
+
 @pytest.mark.parametrize('name', sorted(EDGE))
 def test_edge_cases(engine, name):
     frames, kw = EDGE[name]

@@ -1,6 +1,7 @@
 """Feature location on the MI355X (ctr_locate_maxima_device): equal to the
 reference's grey_dilation on every fixture, to the SciPy composition on seeded random frames,
 frame by frame inside a batch, and good enough to start refine_leastsq from."""
+import functools
 import zlib
 
 import numpy as np
@@ -81,6 +82,27 @@ def test_batch_equals_single_frames():
         rows = f[f['frame'] == t][['y', 'x']].values
         np.testing.assert_array_equal(rows, one.reshape(-1, 2).astype(np.float64))
     assert not (f['frame'] == 3).any()
+
+
+@functools.lru_cache(maxsize=None)
+def _tiny_frames():
+    """2049 frames of 16 x 16 pixels (one chunk of mask words each) and the composition frame by frame"""
+    rng = np.random.RandomState(16)
+    frames = np.stack([_frame(rng, (16, 16), np.uint8, rng.randint(0, 3)) for _ in range(2049)])
+    frames[[5, 1023, 1024]] = 0
+    return frames, [_locate.compose(f, 4, 50).reshape(-1, 2) for f in frames]
+
+
+@pytest.mark.parametrize('n_frames', [1023, 1024, 1025, 2049])
+def test_batch_equals_single_frames_at_the_chunk_of_the_scan(n_frames):
+    """the chunk counts are scanned by one workgroup of 1024, one chunk per frame here: one frame
+    short of its width, the width, one over, two and one over"""
+    frames, single = _tiny_frames()
+    pos, off, _ = find.locate_arrays(frames[:n_frames], 4, percentile=50)
+    want = np.concatenate(single[:n_frames])
+    assert off.tolist() == np.r_[0, np.cumsum([len(s) for s in single[:n_frames]])].tolist()
+    np.testing.assert_array_equal(pos.astype(np.int64), want.astype(np.int64))
+    assert len(want) > n_frames // 2 and any(len(s) == 0 for s in single[:n_frames])
 
 
 def test_torch_frames_from_draw_frames():

@@ -5,7 +5,8 @@ output, doubles included.
 Launch geometry under test: one workgroup of 256 threads per frame, the rows of a frame through LDS
 in tiles of 256 (frames of 0, 1, 255, 256 and 257 rows; a cluster on both sides of the tile's edge
 and one thread stride apart), sweeps until nothing changes (a shuffled chain of 40), the scan of the
-clusters per frame (an empty frame between populated ones, no frame at all)."""
+clusters per frame (an empty frame between populated ones, no frame at all; 255, 256, 257 and 513
+frames: one short of a chunk of the scan's workgroup, a chunk, one over, two and one over)."""
 import functools
 
 import numpy as np
@@ -42,7 +43,7 @@ def _equal(got, want, n_params):
         np.testing.assert_array_equal(t.cpu().numpy(), getattr(want, name), err_msg=name)
 
 
-@pytest.mark.parametrize('name', yard.PREPARE + yard.REFINE)
+@pytest.mark.parametrize('name', yard.PREPARE + yard.MANY_FRAMES + yard.REFINE)
 def test_equals_the_yardstick(engine, name):
     case = yard.cases()[name]
     ff, got = _device(case)

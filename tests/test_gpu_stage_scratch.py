@@ -37,11 +37,11 @@ def test_diffusion_scratch_grows_and_is_shared(engine):
         C.assert_matches((interval[at], {k: v[at] for k, v in det.items()}), res, B, what=at)
 
 
-def _walkers(rng, n, n_levels):
+def _walkers(rng, n, n_levels, step=0.5):
     pos = rng.uniform(0., 400., (n, 2))
     levels = []
     for _ in range(n_levels):
-        pos = pos + rng.normal(0., 0.5, pos.shape)
+        pos = pos + rng.normal(0., step, pos.shape)
         levels.append(pos[rng.permutation(n)])
     return np.concatenate(levels), np.arange(n_levels + 1) * n, levels
 
@@ -56,3 +56,14 @@ def test_link_scratch_grows(engine):
     for got, (_, _, levels) in ((first, small), (grown, large)):
         assert (got == np.concatenate(lk.link_levels(levels, 3.))).all()
         assert got.max() == len(levels[0]) - 1                  # every walker keeps its track
+
+
+@pytest.mark.parametrize('n_levels', [255, 256, 257, 513])
+def test_link_levels_at_the_chunk_of_the_scan(engine, n_levels):
+    """three walkers whose steps leave the search range now and then, so tracks start at many levels:
+    the first ids of the levels are scanned by one workgroup in chunks of 256 levels"""
+    pos, off, levels = _walkers(np.random.RandomState(n_levels), 3, n_levels, step=1.5)
+    want = np.concatenate(lk.link_levels(levels, 3.))
+    assert want[-3:].max() > n_levels // 20               # tracks still start near the end
+    got = lk.link_arrays(pos, off, 3.)
+    assert got.dtype == np.int64 and (got == want).all()
