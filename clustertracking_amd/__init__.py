@@ -19,6 +19,9 @@ from .utils import ArrayReader, RefineException
 from . import constraints, artificial, link, motion, motion_ci, preprocessing
 from .motion_ci import diffusion_tensor_ci, bootstrap_indices
 from .cluster_tracks import cluster_tracks, cluster_tracks_arrays, track_positions, track_positions_arrays
+from . import drift
+from .drift import (compute_drift, subtract_drift, filter_stubs, compute_drift_arrays, subtract_drift_arrays,
+                    filter_stubs_arrays)
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -28,7 +31,9 @@ __all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', '
            'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'link_arrays', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',
            'write_back', 'motion', 'motion_ci', 'diffusion_tensor_ci', 'bootstrap_indices',
-           'cluster_tracks', 'cluster_tracks_arrays', 'track_positions', 'track_positions_arrays']
+           'cluster_tracks', 'cluster_tracks_arrays', 'track_positions', 'track_positions_arrays',
+           'drift', 'compute_drift', 'subtract_drift', 'filter_stubs', 'compute_drift_arrays', 'subtract_drift_arrays',
+           'filter_stubs_arrays']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

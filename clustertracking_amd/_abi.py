@@ -262,6 +262,36 @@ class TrackPositions(C.Structure):
     ]
 
 
+DRIFT_OK, DRIFT_BAD_TABLE = 0, 1                               # status[0] of the three drift calls
+
+
+class Drift(C.Structure):
+    """``ctr_drift`` (include/ctrefine.h): the drift of a linked video, frame by frame."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('smoothing', C.c_int32),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('particle', C.c_void_p),
+        ('drift', C.c_void_p), ('n_pairs', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
+class DriftSubtract(C.Structure):
+    """``ctr_drift_subtract`` (include/ctrefine.h): positions minus the drift of their frame."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('reserved0', C.c_int32), ('n_frames', C.c_int64), ('n_features', C.c_int64),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('drift', C.c_void_p),
+        ('pos_out', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
+class FilterStubs(C.Structure):
+    """``ctr_filter_stubs`` (include/ctrefine.h): unlink the rows of short tracks."""
+    _fields_ = [
+        ('threshold', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64),
+        ('particle', C.c_void_p), ('particle_out', C.c_void_p), ('count', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
 PREPARE_BATCH, PREPARE_SCATTER = 0, 1                          # ctr_refine_prepare.mode
 PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
 

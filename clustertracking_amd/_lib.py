@@ -55,6 +55,9 @@ SIGNATURES = {
     'ctr_cluster_tracks_device': _stage(_abi.ClusterTracks),
     'ctr_cluster_tracks_plan': (C.c_int, [_P(_abi.ClusterTracks), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
     'ctr_track_positions_device': _stage(_abi.TrackPositions),
+    'ctr_drift_device': _stage(_abi.Drift),
+    'ctr_drift_subtract_device': _stage(_abi.DriftSubtract),
+    'ctr_filter_stubs_device': _stage(_abi.FilterStubs),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
     'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
@@ -365,6 +368,9 @@ for _name, _symbol, _too_large in (
         ('train_device', 'ctr_train_device', False),
         ('cluster_tracks_device', 'ctr_cluster_tracks_device', False),
         ('track_positions_device', 'ctr_track_positions_device', False),
+        ('drift_device', 'ctr_drift_device', False),
+        ('drift_subtract_device', 'ctr_drift_subtract_device', False),
+        ('filter_stubs_device', 'ctr_filter_stubs_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 

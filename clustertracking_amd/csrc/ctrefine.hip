@@ -120,6 +120,7 @@ struct ctr_handle {
   Scratch train;   // ctr_train_device: frame maxima, partial sums, solver state
   Scratch tracks;  // ctr_cluster_tracks_device: labels, member counts, the words of the rounds
   Scratch prepare; // ctr_refine_prepare_device: scaled positions, member counts, ranks, clusters per frame
+  Scratch drift;   // ctr_drift_device: the step of every frame
 };
 
 namespace {
@@ -478,7 +479,7 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1077,6 +1078,18 @@ int ctr_cluster_tracks_plan(const ctr_cluster_tracks* c, int64_t* scratch_bytes,
 
 int ctr_track_positions_device(ctr_handle* h, const ctr_track_positions* p, void* hip_stream) {
   return run_stage("ctr_track_positions_device", h, nullptr, p, hip_stream, ctr_track_positions_launch);
+}
+
+int ctr_drift_device(ctr_handle* h, const ctr_drift* d, void* hip_stream) {
+  return run_stage("ctr_drift_device", h, &ctr_handle::drift, d, hip_stream, ctr_drift_launch);
+}
+
+int ctr_drift_subtract_device(ctr_handle* h, const ctr_drift_subtract* d, void* hip_stream) {
+  return run_stage("ctr_drift_subtract_device", h, nullptr, d, hip_stream, ctr_drift_subtract_launch);
+}
+
+int ctr_filter_stubs_device(ctr_handle* h, const ctr_filter_stubs* d, void* hip_stream) {
+  return run_stage("ctr_filter_stubs_device", h, nullptr, d, hip_stream, ctr_filter_stubs_launch);
 }
 
 int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream) {

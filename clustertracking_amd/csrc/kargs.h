@@ -122,7 +122,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
-// tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare)
+// tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -193,5 +193,9 @@ int ctr_track_positions_launch(const ctr_track_positions* p, StageRun* stage, co
 // scaled positions, member counts, ranks, clusters per frame): the scratch goes to *scratch_bytes
 // (may be null) without the need of a device
 int ctr_refine_prepare_launch(const ctr_refine_prepare* r, StageRun* stage, const char** msg, long long* scratch_bytes);
+// drift of a linked video (drift_kernels.h; scratch of the first: the step of every frame)
+int ctr_drift_launch(const ctr_drift* d, StageRun* stage, const char** msg);
+int ctr_drift_subtract_launch(const ctr_drift_subtract* d, StageRun* stage, const char** msg);
+int ctr_filter_stubs_launch(const ctr_filter_stubs* d, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

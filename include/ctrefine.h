@@ -1058,6 +1058,93 @@ typedef struct ctr_track_positions {
 } ctr_track_positions;
 int ctr_track_positions_device(ctr_handle* h, const ctr_track_positions* p, void* hip_stream);
 
+/* ---- drift of a linked video: compute, subtract, drop stubs (ABI 8, additions) ----
+ * The step between the linker and the cluster tracks / the motion stage: ctr_diffusion_device takes a
+ * second moment, mean(x x^T) / (2 dt), not a covariance, so a common drift of v px per frame adds
+ * v^2 lag^2 / (2 dt) to its translational entries.  The reference leaves the step to trackpy
+ * (compute_drift, subtract_drift, filter_stubs on the linked table); the rule here is this project's
+ * dense restatement of trackpy's published rule, tests/_drift.py restates it in NumPy.
+ * Input: N rows sorted by frame; frame_offset [T + 1] (0 <= off[t] <= off[t + 1] <= N, rows [off[t],
+ * off[t + 1]) are frame t); particle [N], dense ids 0 .. P - 1, a negative id is an unlinked row and
+ * is ignored; pos [N, ndim], ndim 2 or 3.
+ *   1. pairs: row i of frame t >= 1 and row j of frame t - 1 form a pair of frame t when
+ *      particle[i] == particle[j] >= 0.  Where several rows of frame t - 1 carry that id, j is the
+ *      lowest such row (the linker never makes such a table; the clause makes the result defined).
+ *      Every row i of frame t that has a match counts.
+ *   2. step: n_pairs[t] is the number of pairs of frame t, n_pairs[0] = 0; dx[t] the mean of
+ *      pos[i] - pos[j] over the pairs of frame t.
+ *   3. smoothing s >= 0: 0 and 1 mean none, sm[t] = dx[t] where n_pairs[t] > 0, else 0.  Otherwise
+ *      sm[t] is the mean of dx[u] over the frames u in [max(1, t - s + 1), t] with n_pairs[u] > 0,
+ *      and 0 where there is none.
+ *   4. drift: drift[0] = 0, drift[t] = drift[t - 1] + sm[t].  Out: drift [T, ndim], n_pairs [T].
+ *   5. subtraction: pos_out[i] = pos[i] - drift[frame of i], one subtraction per coordinate: NumPy's
+ *      bytes for the same drift.  A row in no frame (before off[0], from off[T] on) is copied.
+ *   6. stubs: count[p] is the number of rows with particle == p; a row whose particle has
+ *      count < threshold gets particle -1.  No row is removed and no id renumbered, so the result
+ *      goes into ctr_cluster_tracks_device and into 1, which ignore negative ids.  Out:
+ *      particle_out [N], count [P], exact integers.
+ * Against trackpy: its drift table has no row for the first frame nor for a frame without pairs, its
+ * subtract_drift leaves the rows of such frames unshifted, and its rolling window counts table rows,
+ * not frames.  Here the drift is carried forward through a frame without pairs and n_pairs says
+ * which frames those are; on a table where every frame t >= 1 has a pair the values of the frames
+ * t >= 1 are trackpy's.
+ * A table is refused when frame_offset is not as above or a particle >= P: a kernel checks that
+ * before any other follows an index, status[0] = CTR_DRIFT_BAD_TABLE, and then drift and pos_out
+ * are NaN, n_pairs and count 0, particle_out -1.
+ * Launches of ctr_drift_device: the check; one workgroup of 256 threads per frame t for 1 and 2 -- the
+ * rows of frame t - 1 pass through LDS in tiles of 2048 rows, ascending, each an open-addressing
+ * table of 4096 slots (particle << 32 | row, 32 KiB) in which a repeated particle keeps its lowest
+ * row; a row of frame t without a match yet probes the tile, so the first tile that answers gives
+ * the lowest row and a frame of any row count costs rows x tiles.  A thread adds the displacements
+ * of its rows in ascending row order, the workgroup adds the threads' sums in a binary tree: no
+ * float atomics, the same bytes on every run.  Then one workgroup for 3 and 4: sm[t] in ascending u,
+ * the running sum per coordinate by a workgroup scan in chunks of 256 frames.  Scratch of the
+ * handle: dx, 8 ndim T bytes.  ctr_drift_subtract_device: the check, then one grid-stride kernel
+ * over the rows, the frame of a row by bisection of frame_offset; pos_out may be pos.
+ * ctr_filter_stubs_device: the check, an int32 histogram by atomicAdd, an apply pass; particle_out
+ * may be particle.  Descriptors are checked before the handle, as for ctr_characterize_device.
+ * Device pointers; asynchronous on `hip_stream`. */
+#define CTR_DRIFT_OK 0
+#define CTR_DRIFT_BAD_TABLE 1
+typedef struct ctr_drift {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t smoothing;               /* s >= 0 */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P <= 2^31 - 2 */
+  const double* pos;               /* [N, ndim] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const int64_t* particle;         /* [N] */
+  double* drift;                   /* [T, ndim] out */
+  int32_t* n_pairs;                /* [T] out */
+  int32_t* status;                 /* [1] out */
+} ctr_drift;
+int ctr_drift_device(ctr_handle* h, const ctr_drift* d, void* hip_stream);
+
+typedef struct ctr_drift_subtract {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t reserved0;
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  const double* pos;               /* [N, ndim] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const double* drift;             /* [T, ndim] */
+  double* pos_out;                 /* [N, ndim] out; may be pos */
+  int32_t* status;                 /* [1] out */
+} ctr_drift_subtract;
+int ctr_drift_subtract_device(ctr_handle* h, const ctr_drift_subtract* d, void* hip_stream);
+
+typedef struct ctr_filter_stubs {
+  int64_t threshold;               /* >= 1 */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P <= 2^31 - 2 */
+  const int64_t* particle;         /* [N] */
+  int64_t* particle_out;           /* [N] out; may be particle */
+  int32_t* count;                  /* [P] out */
+  int32_t* status;                 /* [1] out */
+} ctr_filter_stubs;
+int ctr_filter_stubs_device(ctr_handle* h, const ctr_filter_stubs* d, void* hip_stream);
+
 /* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
  * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
  * (find_clusters, the stable sort by (frame, cluster), FitFunctions.feature_bounds, the feasibility
