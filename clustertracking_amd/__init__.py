@@ -22,6 +22,8 @@ from .cluster_tracks import cluster_tracks, cluster_tracks_arrays, track_positio
 from . import drift
 from .drift import (compute_drift, subtract_drift, filter_stubs, compute_drift_arrays, subtract_drift_arrays,
                     filter_stubs_arrays)
+from . import msd
+from .msd import msd_arrays, emsd_arrays, imsd, emsd
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -33,7 +35,7 @@ __all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', '
            'write_back', 'motion', 'motion_ci', 'diffusion_tensor_ci', 'bootstrap_indices',
            'cluster_tracks', 'cluster_tracks_arrays', 'track_positions', 'track_positions_arrays',
            'drift', 'compute_drift', 'subtract_drift', 'filter_stubs', 'compute_drift_arrays', 'subtract_drift_arrays',
-           'filter_stubs_arrays']
+           'filter_stubs_arrays', 'msd', 'msd_arrays', 'emsd_arrays', 'imsd', 'emsd']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

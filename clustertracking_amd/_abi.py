@@ -292,7 +292,34 @@ class FilterStubs(C.Structure):
     ]
 
 
-PREPARE_BATCH, PREPARE_SCATTER = 0, 1                          # ctr_refine_prepare.mode
+MSD_OK, MSD_BAD_TABLE = 0, 1                                   # status[0] of ctr_msd_device and ctr_emsd_device
+MSD_TILE, MSD_CHUNK = 2048, 256        # frames of a span dense in LDS; ids per partial of the ensemble
+
+
+class Msd(C.Structure):
+    """``ctr_msd`` (include/ctrefine.h): the mean squared displacement of every reported particle."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('reserved0', C.c_int32), ('max_lagtime', C.c_int64),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64), ('n_select', C.c_int64),
+        ('mpp', C.c_double * MAX_NDIM),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('particle', C.c_void_p), ('order', C.c_void_p),
+        ('select', C.c_void_p),
+        ('msd', C.c_void_p), ('mean_d', C.c_void_p), ('mean_d2', C.c_void_p), ('n', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
+class Emsd(C.Structure):
+    """``ctr_emsd`` (include/ctrefine.h): the mean squared displacement of the ensemble."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('reserved0', C.c_int32), ('max_lagtime', C.c_int64),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64),
+        ('mpp', C.c_double * MAX_NDIM),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('particle', C.c_void_p), ('order', C.c_void_p),
+        ('msd', C.c_void_p), ('mean_d', C.c_void_p), ('mean_d2', C.c_void_p), ('n', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
+PREPARE_BATCH, PREPARE_SCATTER = 0, 1                         # ctr_refine_prepare.mode
 PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
 
 

@@ -58,6 +58,8 @@ SIGNATURES = {
     'ctr_drift_device': _stage(_abi.Drift),
     'ctr_drift_subtract_device': _stage(_abi.DriftSubtract),
     'ctr_filter_stubs_device': _stage(_abi.FilterStubs),
+    'ctr_msd_device': _stage(_abi.Msd),
+    'ctr_emsd_device': _stage(_abi.Emsd),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
     'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
@@ -371,6 +373,8 @@ for _name, _symbol, _too_large in (
         ('drift_device', 'ctr_drift_device', False),
         ('drift_subtract_device', 'ctr_drift_subtract_device', False),
         ('filter_stubs_device', 'ctr_filter_stubs_device', False),
+        ('msd_device', 'ctr_msd_device', False),
+        ('emsd_device', 'ctr_emsd_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 

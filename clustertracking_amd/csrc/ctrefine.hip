@@ -121,6 +121,7 @@ struct ctr_handle {
   Scratch tracks;  // ctr_cluster_tracks_device: labels, member counts, the words of the rounds
   Scratch prepare; // ctr_refine_prepare_device: scaled positions, member counts, ranks, clusters per frame
   Scratch drift;   // ctr_drift_device: the step of every frame
+  Scratch msd;     // ctr_msd_device, ctr_emsd_device: the sorted rows, row ranges, partials of the chunks
 };
 
 namespace {
@@ -479,7 +480,7 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1090,6 +1091,14 @@ int ctr_drift_subtract_device(ctr_handle* h, const ctr_drift_subtract* d, void* 
 
 int ctr_filter_stubs_device(ctr_handle* h, const ctr_filter_stubs* d, void* hip_stream) {
   return run_stage("ctr_filter_stubs_device", h, nullptr, d, hip_stream, ctr_filter_stubs_launch);
+}
+
+int ctr_msd_device(ctr_handle* h, const ctr_msd* d, void* hip_stream) {
+  return run_stage("ctr_msd_device", h, &ctr_handle::msd, d, hip_stream, ctr_msd_launch);
+}
+
+int ctr_emsd_device(ctr_handle* h, const ctr_emsd* d, void* hip_stream) {
+  return run_stage("ctr_emsd_device", h, &ctr_handle::msd, d, hip_stream, ctr_emsd_launch);
 }
 
 int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream) {

@@ -1145,6 +1145,109 @@ typedef struct ctr_filter_stubs {
 } ctr_filter_stubs;
 int ctr_filter_stubs_device(ctr_handle* h, const ctr_filter_stubs* d, void* hip_stream);
 
+/* ---- mean squared displacement of linked particles (ABI 8, additions) ----
+ * The squared displacement of a linked table against lag time, of every particle and of the
+ * ensemble: what the reference's users compute with trackpy (msd, imsd, emsd) before they trust a
+ * diffusion tensor; it calibrates D, it shows a residual drift v as |v|^2 k^2 at lag k, and it tells
+ * stuck particles from free ones.  The rule is this project's dense restatement of trackpy's
+ * published rule with gaps; tests/_msd.py restates it with plain loops.
+ * Input: the tables of the drift calls above -- N rows sorted by frame, frame_offset [T + 1], particle
+ * [N] with dense ids 0 .. P - 1 and negative = unlinked, pos [N, ndim], ndim 2 or 3 -- and
+ * max_lagtime L >= 1 (the lags k = 1 .. L, in frames), mpp per axis.  A row before off[0] or from
+ * off[T] on is in no frame and does not exist for this rule.
+ *   1. of several rows of one frame with the same id >= 0 only the lowest row exists (clause 1 of the
+ *      drift rule);
+ *   2. rows i (frame t) and j (frame t + k) with particle[i] == particle[j] == p >= 0 are a pair of
+ *      (p, k); a frame in between that p misses makes no difference;
+ *   3. d = (pos[j] - pos[i]) * mpp, per coordinate: the subtraction first;
+ *   4. n[p, k] is the number of pairs of (p, k);
+ *   5. mean_d[p, k, a] is the mean of d_a over them;
+ *   6. mean_d2[p, k, a] is the mean of d_a^2, the square rounded before it is added;
+ *   7. msd[p, k] = mean_d2[p, k, 0] + mean_d2[p, k, 1] (+ mean_d2[p, k, 2]), added in that order;
+ *   8. lagt[k] = k / fps (the Python layer's: the device works in frames);
+ *   9. where n == 0 the means and msd are NaN: k beyond the track's span, a particle with one row,
+ *      an id without rows;
+ *  10. ensemble: the same four quantities over the pairs of all particles pooled (trackpy's emsd:
+ *      the mean of the per-particle values weighted by n); its n[k] is int64.
+ * Against trackpy: its msd reindexes a track by frame and takes NaN where a frame is missing, which
+ * is clause 2; its imsd returns msd alone and drops nothing else; its emsd pools with the weights n
+ * as clause 10 does.  trackpy's 'N' column of msd is an effective number of independent
+ * measurements, not a pair count; n here is the pair count.  Clause 1 has no counterpart (the
+ * linker never makes such a table; the clause makes the result defined).
+ * `order` [N] is the caller's stable ascending sort of the rows by particle (torch's or any other):
+ * rows are in frame order, so that is (particle, frame, row) order.  A table is refused
+ * (status[0] = CTR_MSD_BAD_TABLE; then the means and msd are NaN and every n is 0, and no kernel
+ * follows an index of the table) when frame_offset is not monotone within [0, N], a particle >= P,
+ * or `order` is not that sort (an entry outside [0, N), ids not ascending, rows of an id not
+ * ascending).  `select`: the M ids to report, or null for 0 .. M - 1; an id outside [0, P) is an id
+ * without rows.
+ * Launches, 256 threads each.  The check.  msd_rows: one thread per sorted row -- the frame of the
+ * row by bisection of frame_offset, into a code (the frame, or a negative word for a row that does
+ * not exist: repeated, or in no frame), the positions gathered into sorted order, and the first and
+ * last sorted row of every id where the id changes: no histogram and no scan.
+ * ctr_msd_device then runs msd_particle, one workgroup per reported id: a track whose span (last -
+ * first + 1 frames) is at most CTR_MSD_TILE = 2048 is staged in LDS dense by frame, coordinates
+ * and a presence byte, and for lag k a thread visits frames f, f + 256, ... and adds where f and
+ * f + k are both present; a longer span is read from the sorted rows in global memory, where the
+ * partner of row i at lag k is row i + k when the track has no gap there and else is found by
+ * bisection of the codes.  No track is refused for its length.  A thread adds its terms in frame
+ * order; the workgroup adds the threads' sums in a fixed tree (shuffles in the wavefront, then the
+ * four wavefronts): no float atomics, the same bytes on every call; lags beyond the span are
+ * written without a reduction.  ctr_emsd_device runs msd_chunk, one workgroup per CTR_MSD_CHUNK =
+ * 256 consecutive ids: their rows are consecutive sorted rows, which it walks as the long-span
+ * path does, and writes one partial (sums and a count per lag) per chunk; then msd_pool adds the
+ * partials in chunk order.  The chunk is a constant, not a function of the grid; where the chunks
+ * are few the launch lets several workgroups share the lags of a chunk, each lag still summed by
+ * one workgroup in the same order, so the bytes do not depend on that either.  Scratch of the
+ * handle: 4 N (codes) + 4 N (ids) + 8 ndim N (positions) + 8 P (row ranges) bytes, and for the
+ * ensemble 8 (2 ndim + 1) L ceil(P / 256) more; nothing proportional to P L.
+ * Descriptors are checked before the handle.  Device pointers; asynchronous on `hip_stream`. */
+#define CTR_MSD_OK 0
+#define CTR_MSD_BAD_TABLE 1
+#define CTR_MSD_TILE 2048            /* frames of a track's span that msd_particle stages in LDS */
+#define CTR_MSD_CHUNK 256            /* particle ids per partial of the ensemble */
+typedef struct ctr_msd {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t reserved0;
+  int64_t max_lagtime;             /* L >= 1 */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P <= 2^31 - 2 */
+  int64_t n_select;                /* M: the ids reported */
+  double mpp[CTR_MAX_NDIM];        /* per axis, finite */
+  const double* pos;               /* [N, ndim] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const int64_t* particle;         /* [N] */
+  const int64_t* order;            /* [N]: the rows in a stable ascending sort by particle */
+  const int64_t* select;           /* [M] ids, or null: 0 .. M - 1 */
+  double* msd;                     /* [M, L] out */
+  double* mean_d;                  /* [M, L, ndim] out */
+  double* mean_d2;                 /* [M, L, ndim] out */
+  int32_t* n;                      /* [M, L] out */
+  int32_t* status;                 /* [1] out */
+} ctr_msd;
+int ctr_msd_device(ctr_handle* h, const ctr_msd* d, void* hip_stream);
+
+typedef struct ctr_emsd {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t reserved0;
+  int64_t max_lagtime;             /* L >= 1 */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P <= 2^31 - 2 */
+  double mpp[CTR_MAX_NDIM];        /* per axis, finite */
+  const double* pos;               /* [N, ndim] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const int64_t* particle;         /* [N] */
+  const int64_t* order;            /* [N]: as in ctr_msd */
+  double* msd;                     /* [L] out */
+  double* mean_d;                  /* [L, ndim] out */
+  double* mean_d2;                 /* [L, ndim] out */
+  int64_t* n;                      /* [L] out */
+  int32_t* status;                 /* [1] out */
+} ctr_emsd;
+int ctr_emsd_device(ctr_handle* h, const ctr_emsd* d, void* hip_stream);
+
 /* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
  * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
  * (find_clusters, the stable sort by (frame, cluster), FitFunctions.feature_bounds, the feasibility
