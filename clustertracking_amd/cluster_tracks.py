@@ -28,8 +28,7 @@ import collections
 
 import numpy as np
 
-from . import _abi, _lib
-from .motion import _is_tensor
+from . import _abi, _lib, _tables
 
 ClusterTracks = collections.namedtuple('ClusterTracks', ['track_of_particle', 'n_tracks', 'n_members', 'status'])
 TrackPositions = collections.namedtuple('TrackPositions', ['pos', 'present'])
@@ -44,31 +43,6 @@ def _check_sizes(cluster_size, min_frames=1):
     if isinstance(min_frames, bool) or int(min_frames) != min_frames or min_frames < 1:
         raise ValueError("min_frames must be an integer >= 1, not %r" % (min_frames,))
     return int(cluster_size), int(min_frames)
-
-
-def _column(x, n, what, dtype=np.int64):
-    """a 1-D table column: a tensor as it is (checked later against the device), else an ndarray"""
-    if _is_tensor(x):
-        if x.dim() != 1 or (n is not None and x.shape[0] != n):
-            raise ValueError("%s must be one-dimensional%s, not %s"
-                             % (what, '' if n is None else ' with %d entries' % n, tuple(x.shape)))
-        return x
-    x = np.asarray(x)
-    if x.ndim != 1 or (n is not None and len(x) != n):
-        raise ValueError("%s must be one-dimensional%s, not %s"
-                         % (what, '' if n is None else ' with %d entries' % n, x.shape))
-    if x.dtype.kind not in 'iu':
-        raise ValueError("%s must hold integers, not %s" % (what, x.dtype))
-    return np.ascontiguousarray(x, dtype=dtype)
-
-
-def _on(x, dev, dtype, what):
-    import torch
-    if _is_tensor(x):
-        if x.device != dev or x.dtype != dtype:
-            raise ValueError("a %s tensor is %s on %s" % (what, str(dtype).replace('torch.', ''), dev))
-        return x.contiguous()
-    return torch.from_numpy(x).to(dev)
 
 
 def descriptor(phase, cluster_size, min_frames, n_frames, n_features, n_particles, check_every=0):
@@ -103,31 +77,19 @@ def cluster_tracks_arrays(frame_offset, particle, cluster, cluster_size, min_fra
     check_every = CHECK_EVERY if check_every is None else int(check_every)
     if check_every < 0:
         raise ValueError("check_every must be >= 0")
-    as_tensor = _is_tensor(particle)
-    frame_offset = _column(frame_offset, None, 'frame_offset')
-    if frame_offset.shape[0] < 1:
-        raise ValueError("frame_offset must have T + 1 >= 1 entries")
-    particle = _column(particle, None, 'particle')
+    as_tensor = _tables.is_tensor(particle)
+    frame_offset, n_frames = _tables.offsets(frame_offset)
+    particle = _tables.column(particle, None, 'particle')
     n = int(particle.shape[0])
-    cluster = _column(cluster, n, 'cluster')
-    if n_particles is None:
-        n_particles = (int(particle.max()) + 1 if n else 0) if not as_tensor else None
-    elif int(n_particles) != n_particles or n_particles < 0:
-        raise ValueError("n_particles must be an integer >= 0")
-    if n_particles is not None:
-        n_particles = max(int(n_particles), 0)
-        if n_particles > 2 ** 31 - 2:
-            raise ValueError("more than 2^31 - 2 particles")
-    n_frames = int(frame_offset.shape[0]) - 1
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
-        off_t = _on(frame_offset, dev, torch.int64, 'frame_offset')
-        par_t = _on(particle, dev, torch.int64, 'particle')
-        clu_t = _on(cluster, dev, torch.int64, 'cluster')
+    cluster = _tables.column(cluster, n, 'cluster')
+    particle, n_particles = _tables.particles(particle, n, n_particles)
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        off_t = _tables.on_device(frame_offset, dev, torch.int64, 'frame_offset')
+        par_t = _tables.on_device(particle, dev, torch.int64, 'particle')
+        clu_t = _tables.on_device(cluster, dev, torch.int64, 'cluster')
         if n_particles is None:
-            n_particles = max(int(par_t.max().item()) + 1, 0) if n else 0
+            n_particles = _tables.count_particles(par_t, n)
         keys = torch.empty(n * (cluster_size - 1), dtype=torch.int64, device=dev)
         track_of = torch.empty(n_particles, dtype=torch.int32, device=dev)
         members = torch.empty(n_particles // 2, dtype=torch.int32, device=dev)
@@ -161,29 +123,21 @@ def track_positions_arrays(pos, frame_offset, particle, track_of_particle, n_tra
     ``motion.orientation_arrays``.  A refused table (offsets, a particle >= P, a track >= n_tracks)
     raises ``ValueError`` for ndarrays; for tensors it leaves every cell NaN and ``present`` 0."""
     cluster_size, _ = _check_sizes(cluster_size)
-    as_tensor = _is_tensor(pos)
-    if not as_tensor:
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-    if len(pos.shape) != 2 or pos.shape[1] not in (2, 3):
-        raise ValueError("pos must be [N, ndim] with ndim 2 or 3, not %s" % (tuple(pos.shape),))
-    n, ndim = int(pos.shape[0]), int(pos.shape[1])
-    frame_offset = _column(frame_offset, None, 'frame_offset')
-    if frame_offset.shape[0] < 1:
-        raise ValueError("frame_offset must have T + 1 >= 1 entries")
-    particle = _column(particle, n, 'particle')
-    track_of_particle = _column(track_of_particle, None, 'track_of_particle', np.int32)
+    as_tensor = _tables.is_tensor(pos)
+    pos, n, ndim = _tables.positions(pos)
+    frame_offset, n_frames = _tables.offsets(frame_offset)
+    particle = _tables.column(particle, n, 'particle')
+    track_of_particle = _tables.column(track_of_particle, None, 'track_of_particle', np.int32)
     n_particles = int(track_of_particle.shape[0])
     if isinstance(n_tracks, bool) or int(n_tracks) != n_tracks or n_tracks < 0 or 2 * n_tracks > n_particles:
         raise ValueError("n_tracks must be an integer in [0, P / 2], not %r" % (n_tracks,))
-    n_tracks, n_frames = int(n_tracks), int(frame_offset.shape[0]) - 1
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
-        pos_t = _on(pos, dev, torch.float64, 'pos')
-        off_t = _on(frame_offset, dev, torch.int64, 'frame_offset')
-        par_t = _on(particle, dev, torch.int64, 'particle')
-        trk_t = _on(track_of_particle, dev, torch.int32, 'track_of_particle')
+    n_tracks = int(n_tracks)
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        pos_t = _tables.on_device(pos, dev, torch.float64, 'pos')
+        off_t = _tables.on_device(frame_offset, dev, torch.int64, 'frame_offset')
+        par_t = _tables.on_device(particle, dev, torch.int64, 'particle')
+        trk_t = _tables.on_device(track_of_particle, dev, torch.int32, 'track_of_particle')
         out = torch.empty((n_tracks, n_frames, cluster_size, ndim), dtype=torch.float64, device=dev)
         present = torch.empty((n_tracks, n_frames), dtype=torch.int32, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -194,45 +148,14 @@ def track_positions_arrays(pos, frame_offset, particle, track_of_particle, n_tra
         d.track_of_particle, d.pos = trk_t.data_ptr() or None, pos_t.data_ptr() or None
         d.present, d.pos_out, d.status = present.data_ptr() or None, out.data_ptr() or None, status.data_ptr()
         eng.on_current_stream(eng.track_positions_device, d, dev=dev)
-        if as_tensor:
-            return TrackPositions(out, present)
-        if int(status.item()) != _abi.TRACKS_OK:
-            raise ValueError("track_positions_arrays: frame_offset must rise within [0, N], particle must be "
-                             "below P and track_of_particle below n_tracks")
-        return TrackPositions(out.cpu().numpy(), present.cpu().numpy())
-
-
-def _table(f, pos_columns, t_column):
-    """the rows of ``f`` sorted by frame: (order, frame_offset, first_frame, dense particle, cluster, pos)"""
-    for col in ('particle', 'cluster', t_column):
-        if col not in f:
-            raise ValueError("the table has no %r column%s" % (
-                col, {'particle': ': link it first (find_link, link_df)',
-                      'cluster': ': label it first (find_clusters)'}.get(col, '')))
-    if pos_columns is None:
-        pos_columns = ['z', 'y', 'x'] if 'z' in f else ['y', 'x']
-    missing = [c for c in pos_columns if c not in f]
-    if missing or len(pos_columns) not in (2, 3):
-        raise ValueError("pos_columns must name 2 or 3 columns of the table, not %r" % (pos_columns,))
-    if len(f) == 0:
-        raise ValueError("an empty table has no frames")
-    for col in ('particle', 'cluster', t_column):
-        if np.asarray(f[col].values).dtype.kind not in 'iu':
-            raise ValueError("the %r column must hold integers, not %s" % (col, f[col].values.dtype))
-    frames = f[t_column].values.astype(np.int64)
-    order = np.argsort(frames, kind='stable')
-    first = int(frames.min())
-    length = int(frames.max()) - first + 1
-    offset = np.searchsorted(frames[order] - first, np.arange(length + 1), side='left').astype(np.int64)
-    ids, dense = np.unique(f['particle'].values[order], return_inverse=True)
-    cluster = f['cluster'].values[order].astype(np.int64)
-    pos = np.ascontiguousarray(f[list(pos_columns)].values[order], dtype=np.float64)
-    return order, offset, first, ids, dense.astype(np.int64).reshape(-1), cluster, pos
+        return TrackPositions(*_tables.results(
+            as_tensor, status, _abi.TRACKS_OK, "track_positions_arrays: frame_offset must rise within [0, N], particle "
+            "must be below P and track_of_particle below n_tracks", out, present))
 
 
 def _tracks_of_table(f, cluster_size, min_frames, pos_columns, t_column, device):
     cluster_size, min_frames = _check_sizes(cluster_size, min_frames)
-    order, offset, first, ids, dense, cluster, pos = _table(f, pos_columns, t_column)
+    order, offset, first, ids, dense, _, pos, cluster = _tables.frame_sorted(f, pos_columns, t_column, extra=('cluster',))
     res = cluster_tracks_arrays(offset, dense, cluster, cluster_size, min_frames, device, n_particles=len(ids))
     if res.status != _abi.TRACKS_OK:
         raise _lib.EngineError("cluster_tracks: the components did not settle within the round bound (status %d)"

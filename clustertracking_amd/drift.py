@@ -31,53 +31,12 @@ import collections
 
 import numpy as np
 
-from . import _abi, _lib
-from .cluster_tracks import _column, _on
-from .motion import _is_tensor
+from . import _abi, _tables
 
 Drift = collections.namedtuple('Drift', ['drift', 'n_pairs', 'status'])
 Stubs = collections.namedtuple('Stubs', ['particle', 'count'])
 
 _REFUSED = "frame_offset must rise within [0, N] and particle must be below n_particles"
-
-
-def _integer(value, least, what):
-    if isinstance(value, bool) or int(value) != value or value < least or value > 2 ** 31 - 1:
-        raise ValueError("%s must be an integer >= %d, not %r" % (what, least, value))
-    return int(value)
-
-
-def _positions(pos, what='pos'):
-    """(pos, N, ndim) of a float64 [N, ndim] table: a tensor as it is, else a contiguous ndarray"""
-    if not _is_tensor(pos):
-        pos = np.asarray(pos)
-        if pos.dtype.kind not in 'fiu':
-            raise ValueError("%s must hold numbers, not %s" % (what, pos.dtype))
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-    if len(pos.shape) != 2 or pos.shape[1] not in (2, 3):
-        raise ValueError("%s must be [N, ndim] with ndim 2 or 3, not %s" % (what, tuple(pos.shape)))
-    return pos, int(pos.shape[0]), int(pos.shape[1])
-
-
-def _offsets(frame_offset):
-    frame_offset = _column(frame_offset, None, 'frame_offset')
-    if frame_offset.shape[0] < 1:
-        raise ValueError("frame_offset must have T + 1 >= 1 entries")
-    return frame_offset, int(frame_offset.shape[0]) - 1
-
-
-def _particles(particle, n, n_particles):
-    """(particle, P or None): None where a tensor has to be read for it"""
-    particle = _column(particle, n, 'particle')
-    if n_particles is None:
-        if _is_tensor(particle):
-            return particle, None
-        n_particles = max(int(particle.max()) + 1, 0) if particle.shape[0] else 0
-    elif isinstance(n_particles, bool) or int(n_particles) != n_particles or n_particles < 0:
-        raise ValueError("n_particles must be an integer >= 0")
-    if n_particles > 2 ** 31 - 2:
-        raise ValueError("more than 2^31 - 2 particles")
-    return particle, int(n_particles)
 
 
 def compute_drift_arrays(pos, frame_offset, particle, smoothing=0, n_particles=None, device=0):
@@ -94,22 +53,18 @@ def compute_drift_arrays(pos, frame_offset, particle, smoothing=0, n_particles=N
     tensors status is ``_abi.DRIFT_BAD_TABLE``, drift NaN and n_pairs 0.  Unlike trackpy's table the
     result has a row for frame 0 (zero) and for a frame without pairs (the drift carried forward,
     ``n_pairs == 0``).  The same bytes on every call."""
-    smoothing = _integer(smoothing, 0, 'smoothing')
-    pos, n, ndim = _positions(pos)
-    as_tensor = _is_tensor(pos)
-    frame_offset, n_frames = _offsets(frame_offset)
-    particle, n_particles = _particles(particle, n, n_particles)
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
-        pos_t = _on(pos, dev, torch.float64, 'pos')
-        off_t = _on(frame_offset, dev, torch.int64, 'frame_offset')
-        par_t = _on(particle, dev, torch.int64, 'particle')
+    smoothing = _tables.integer(smoothing, 0, 'smoothing')
+    pos, n, ndim = _tables.positions(pos)
+    as_tensor = _tables.is_tensor(pos)
+    frame_offset, n_frames = _tables.offsets(frame_offset)
+    particle, n_particles = _tables.particles(particle, n, n_particles)
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        pos_t = _tables.on_device(pos, dev, torch.float64, 'pos')
+        off_t = _tables.on_device(frame_offset, dev, torch.int64, 'frame_offset')
+        par_t = _tables.on_device(particle, dev, torch.int64, 'particle')
         if n_particles is None:
-            n_particles = max(int(par_t.max().item()) + 1, 0) if n else 0
-            if n_particles > 2 ** 31 - 2:
-                raise ValueError("more than 2^31 - 2 particles")
+            n_particles = _tables.count_particles(par_t, n)
         drift = torch.empty((n_frames, ndim), dtype=torch.float64, device=dev)
         n_pairs = torch.empty(n_frames, dtype=torch.int32, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -118,11 +73,8 @@ def compute_drift_arrays(pos, frame_offset, particle, smoothing=0, n_particles=N
         d.pos, d.frame_offset, d.particle = pos_t.data_ptr() or None, off_t.data_ptr(), par_t.data_ptr() or None
         d.drift, d.n_pairs, d.status = drift.data_ptr() or None, n_pairs.data_ptr() or None, status.data_ptr()
         eng.on_current_stream(eng.drift_device, d, dev=dev)
-        if as_tensor:
-            return Drift(drift, n_pairs, status)
-        if int(status.item()) != _abi.DRIFT_OK:
-            raise ValueError("compute_drift_arrays: " + _REFUSED)
-        return Drift(drift.cpu().numpy(), n_pairs.cpu().numpy(), _abi.DRIFT_OK)
+        out = _tables.results(as_tensor, status, _abi.DRIFT_OK, "compute_drift_arrays: " + _REFUSED, drift, n_pairs)
+        return Drift(*out, status if as_tensor else _abi.DRIFT_OK)
 
 
 def subtract_drift_arrays(pos, frame_offset, drift, device=0):
@@ -135,19 +87,17 @@ def subtract_drift_arrays(pos, frame_offset, drift, device=0):
     for a tensor.  Refused offsets raise ``ValueError`` for ndarrays and give NaN for tensors.  Unlike
     trackpy's ``subtract_drift`` every frame is shifted, frame 0 (by zero) and a frame without pairs
     (by the drift carried forward) included."""
-    pos, n, ndim = _positions(pos)
-    as_tensor = _is_tensor(pos)
-    frame_offset, n_frames = _offsets(frame_offset)
-    drift, n_drift, ndim_drift = _positions(drift, 'drift')
+    pos, n, ndim = _tables.positions(pos)
+    as_tensor = _tables.is_tensor(pos)
+    frame_offset, n_frames = _tables.offsets(frame_offset)
+    drift, n_drift, ndim_drift = _tables.positions(drift, 'drift')
     if (n_drift, ndim_drift) != (n_frames, ndim):
         raise ValueError("drift must be [T, ndim] = [%d, %d], not [%d, %d]" % (n_frames, ndim, n_drift, ndim_drift))
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
-        pos_t = _on(pos, dev, torch.float64, 'pos')
-        off_t = _on(frame_offset, dev, torch.int64, 'frame_offset')
-        drift_t = _on(drift, dev, torch.float64, 'drift')
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        pos_t = _tables.on_device(pos, dev, torch.float64, 'pos')
+        off_t = _tables.on_device(frame_offset, dev, torch.int64, 'frame_offset')
+        drift_t = _tables.on_device(drift, dev, torch.float64, 'drift')
         out = torch.empty((n, ndim), dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         d = _abi.DriftSubtract()
@@ -155,11 +105,8 @@ def subtract_drift_arrays(pos, frame_offset, drift, device=0):
         d.pos, d.frame_offset, d.drift = pos_t.data_ptr() or None, off_t.data_ptr(), drift_t.data_ptr() or None
         d.pos_out, d.status = out.data_ptr() or None, status.data_ptr()
         eng.on_current_stream(eng.drift_subtract_device, d, dev=dev)
-        if as_tensor:
-            return out
-        if int(status.item()) != _abi.DRIFT_OK:
-            raise ValueError("subtract_drift_arrays: frame_offset must rise within [0, N]")
-        return out.cpu().numpy()
+        return _tables.results(as_tensor, status, _abi.DRIFT_OK,
+                               "subtract_drift_arrays: frame_offset must rise within [0, N]", out)[0]
 
 
 def filter_stubs_arrays(particle, threshold=100, n_particles=None, device=0):
@@ -172,19 +119,15 @@ def filter_stubs_arrays(particle, threshold=100, n_particles=None, device=0):
     does that for a table).  ndarrays for an ndarray, tensors (no host copy, no synchronisation with
     a given P) for a tensor.  A particle >= P raises ``ValueError`` for ndarrays; for tensors every row
     then gets -1 and every count is 0."""
-    threshold = _integer(threshold, 1, 'threshold')
-    as_tensor = _is_tensor(particle)
-    particle, n_particles = _particles(particle, None, n_particles)
+    threshold = _tables.integer(threshold, 1, 'threshold')
+    as_tensor = _tables.is_tensor(particle)
+    particle, n_particles = _tables.particles(particle, None, n_particles)
     n = int(particle.shape[0])
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
-        par_t = _on(particle, dev, torch.int64, 'particle')
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        par_t = _tables.on_device(particle, dev, torch.int64, 'particle')
         if n_particles is None:
-            n_particles = max(int(par_t.max().item()) + 1, 0) if n else 0
-            if n_particles > 2 ** 31 - 2:
-                raise ValueError("more than 2^31 - 2 particles")
+            n_particles = _tables.count_particles(par_t, n)
         out = torch.empty(n, dtype=torch.int64, device=dev)
         count = torch.empty(n_particles, dtype=torch.int32, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -193,38 +136,8 @@ def filter_stubs_arrays(particle, threshold=100, n_particles=None, device=0):
         d.particle, d.particle_out = par_t.data_ptr() or None, out.data_ptr() or None
         d.count, d.status = count.data_ptr() or None, status.data_ptr()
         eng.on_current_stream(eng.filter_stubs_device, d, dev=dev)
-        if as_tensor:
-            return Stubs(out, count)
-        if int(status.item()) != _abi.DRIFT_OK:
-            raise ValueError("filter_stubs_arrays: particle must be below n_particles")
-        return Stubs(out.cpu().numpy(), count.cpu().numpy())
-
-
-def _table(f, pos_columns, t_column, with_pos=True):
-    """the rows of ``f`` sorted by frame: (order, frame_offset, first_frame, ids, dense particle, pos_columns, pos)"""
-    for col in ('particle', t_column):
-        if col not in f:
-            raise ValueError("the table has no %r column%s"
-                             % (col, ': link it first (find_link, link_df)' if col == 'particle' else ''))
-    if with_pos:
-        if pos_columns is None:
-            pos_columns = ['z', 'y', 'x'] if 'z' in f else ['y', 'x']
-        pos_columns = list(pos_columns)
-        if [c for c in pos_columns if c not in f] or len(pos_columns) not in (2, 3):
-            raise ValueError("pos_columns must name 2 or 3 columns of the table, not %r" % (pos_columns,))
-    if len(f) == 0:
-        raise ValueError("an empty table has no frames")
-    for col in ('particle', t_column):
-        if np.asarray(f[col].values).dtype.kind not in 'iu':
-            raise ValueError("the %r column must hold integers, not %s" % (col, f[col].values.dtype))
-    frames = f[t_column].values.astype(np.int64)
-    order = np.argsort(frames, kind='stable')
-    first = int(frames.min())
-    length = int(frames.max()) - first + 1
-    offset = np.searchsorted(frames[order] - first, np.arange(length + 1), side='left').astype(np.int64)
-    ids, dense = np.unique(f['particle'].values[order], return_inverse=True)
-    pos = np.ascontiguousarray(f[pos_columns].values[order], dtype=np.float64) if with_pos else None
-    return order, offset, first, ids, dense.astype(np.int64).reshape(-1), pos_columns, pos
+        return Stubs(*_tables.results(as_tensor, status, _abi.DRIFT_OK,
+                                      "filter_stubs_arrays: particle must be below n_particles", out, count))
 
 
 def compute_drift(f, smoothing=0, pos_columns=None, t_column='frame', device=0):
@@ -236,8 +149,8 @@ def compute_drift(f, smoothing=0, pos_columns=None, t_column='frame', device=0):
     has a row for the first frame (zero) and for a frame without pairs (``n_pairs == 0``, the drift
     carried forward), and ``smoothing`` counts frames, not table rows; see the module's text."""
     import pandas as pd
-    smoothing = _integer(smoothing, 0, 'smoothing')
-    _, offset, first, ids, dense, pos_columns, pos = _table(f, pos_columns, t_column)
+    smoothing = _tables.integer(smoothing, 0, 'smoothing')
+    _, offset, first, ids, dense, pos_columns, pos = _tables.frame_sorted(f, pos_columns, t_column)
     res = compute_drift_arrays(pos, offset, dense, smoothing, n_particles=len(ids), device=device)
     out = pd.DataFrame(res.drift, columns=pos_columns,
                        index=pd.RangeIndex(first, first + len(res.drift), name=t_column))
@@ -253,7 +166,7 @@ def subtract_drift(f, drift=None, smoothing=0, pos_columns=None, t_column='frame
     trackpy's ``subtract_drift`` no frame stays unshifted."""
     if drift is None:
         drift = compute_drift(f, smoothing, pos_columns, t_column, device)
-    order, offset, first, _, _, pos_columns, pos = _table(f, pos_columns, t_column)
+    order, offset, first, _, _, pos_columns, pos = _tables.frame_sorted(f, pos_columns, t_column)
     if [c for c in pos_columns if c not in drift]:
         raise ValueError("the drift table has no columns %r" % (pos_columns,))
     frames = np.arange(first, first + len(offset) - 1)
@@ -273,8 +186,8 @@ def subtract_drift(f, drift=None, smoothing=0, pos_columns=None, t_column='frame
 def filter_stubs(f, threshold=100, t_column='frame', device=0):
     """The rows of ``f`` whose particle has at least ``threshold`` rows, as trackpy's ``filter_stubs``.
     Particle ids of any integer type (mapped through their sorted unique values)."""
-    threshold = _integer(threshold, 1, 'threshold')
-    _, _, _, ids, dense, _, _ = _table(f, None, t_column, with_pos=False)
+    threshold = _tables.integer(threshold, 1, 'threshold')
+    _, _, _, ids, dense, _, _ = _tables.frame_sorted(f, None, t_column, with_pos=False)
     # dense follows the sorted rows; the count of a particle does not depend on the order
     res = filter_stubs_arrays(dense, threshold, n_particles=len(ids), device=device)
     keep = res.count[np.searchsorted(ids, f['particle'].values)] >= threshold

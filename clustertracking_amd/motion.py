@@ -24,11 +24,9 @@ is :func:`clustertracking_amd.motion_ci.diffusion_tensor_ci`, a module of its ow
 There is no CPU fallback: without the library or a GPU the calls raise ``EngineError``; argument
 errors are raised before that.
 """
-import sys
-
 import numpy as np
 
-from . import _abi, _lib
+from . import _abi, _tables
 
 # reference motion.py:137-145, in its order
 PERMUTATIONS = {
@@ -37,11 +35,6 @@ PERMUTATIONS = {
     4: ((0, 1, 2, 3), (0, 2, 3, 1), (0, 3, 1, 2), (1, 0, 2, 3), (1, 2, 3, 0), (1, 3, 0, 2),
         (2, 0, 1, 3), (2, 1, 3, 0), (2, 3, 0, 1), (3, 0, 1, 2), (3, 1, 2, 0), (3, 2, 0, 1)),
 }
-
-
-def _is_tensor(x):
-    torch = sys.modules.get('torch')
-    return torch is not None and isinstance(x, torch.Tensor)
 
 
 def _check_geometry(cluster_size, ndim):
@@ -68,16 +61,6 @@ def _weights(sizes, cluster_size, ndim):
     return sizes ** ndim
 
 
-def _to_device(x, dev, dtype, what):
-    """a contiguous tensor of ``dtype`` on ``dev`` from an ndarray, or the tensor itself (checked)"""
-    import torch
-    if _is_tensor(x):
-        if x.device != dev or x.dtype != dtype:
-            raise ValueError("a %s tensor is %s on %s" % (what, str(dtype).replace('torch.', ''), dev))
-        return x.contiguous()
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-
-
 def orientation_arrays(pos, cluster_size, ndim, mpp=1., sizes=None, angles=None, device=0):
     """Centre of mass and bases of tracked clusters (``ctr_orientation_device``).
 
@@ -91,7 +74,7 @@ def orientation_arrays(pos, cluster_size, ndim, mpp=1., sizes=None, angles=None,
     _check_geometry(cluster_size, ndim)
     cluster_size = int(cluster_size)
     n_perm = len(PERMUTATIONS[cluster_size])
-    as_tensor = _is_tensor(pos)
+    as_tensor = _tables.is_tensor(pos)
     if not as_tensor:
         pos = np.asarray(pos, dtype=np.float64)
     if pos.ndim != 4 or pos.shape[2] != cluster_size or pos.shape[3] != ndim:
@@ -106,17 +89,15 @@ def orientation_arrays(pos, cluster_size, ndim, mpp=1., sizes=None, angles=None,
         if angles is None:
             raise ValueError("angles is required for 3D dimers: [T, P, F] radians, the azimuth that the "
                              "reference draws at random")
-        if not _is_tensor(angles):
+        if not _tables.is_tensor(angles):
             angles = np.asarray(angles, dtype=np.float64)
         if tuple(angles.shape) != (n_tracks, n_perm, n_frames):
             raise ValueError("angles must be [T, P, F] = %s, not %s"
                              % ((n_tracks, n_perm, n_frames), tuple(angles.shape)))
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
-        pos_t = _to_device(pos, dev, torch.float64, 'pos')
-        ang_t = _to_device(angles, dev, torch.float64, 'angles') if needs_angles else None
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        pos_t = _tables.on_device(pos, dev, torch.float64, 'pos')
+        ang_t = _tables.on_device(angles, dev, torch.float64, 'angles') if needs_angles else None
         com = torch.empty((n_tracks, n_frames, 3), dtype=torch.float64, device=dev)
         bases = torch.empty((n_tracks, n_perm, n_frames, 3, 3), dtype=torch.float64, device=dev)
         if n_tracks * n_frames:
@@ -194,29 +175,18 @@ def _lag_list(lagtime):
     return scalar, lags
 
 
-def diffusion_tensor(positions, orientations, lagtime=1, fps=1., ndim=3, pool_tracks=False, return_counts=False,
-                     device=0):
-    """Diffusion tensor from positions and bases (``ctr_diffusion_device``), for every track and
-    every lag of a sweep in one call.
-
-    positions: ``[F, 3]`` or ``[T, F, 3]``; orientations: ``[F, 3, 3]``, ``[P, F, 3, 3]`` or, with
-    tracked positions, ``[T, P, F, 3, 3]`` (what :func:`orientation_arrays` returns).  lagtime: an
-    int (frames), or a sequence, which adds a lag axis; ``lag >= F`` gives a NaN tensor.  ndim 2
-    keeps x, y translation and z rotation (3 x 3), ndim 3 gives 6 x 6.
-    Returns ``tensor [T][, n_lags], D, D``: with the reference's argument shapes the reference's
-    shape.  ``pool_tracks``: the mean over the rows of all tracks (the count-weighted mean of the
-    per-track tensors) instead of the track axis.  ``return_counts``: also the number of rows that
-    entered each mean, int64 ``[T][, n_lags]``.  ndarrays in give ndarrays, tensors on
-    ``cuda:device`` give tensors (no host copy)."""
+def diffusion_inputs(positions, orientations, lagtime, fps, ndim):
+    """The arguments that :func:`diffusion_tensor` and ``motion_ci.diffusion_tensor_ci`` share, checked:
+    ``(positions, orientations, as_tensor, scalar_lag, lags, tracked, n_tracks, n_frames, n_perm)``."""
     if ndim not in (2, 3):
         raise ValueError("ndim must be 2 or 3, not %r" % (ndim,))
     scalar_lag, lags = _lag_list(lagtime)
     if not (np.isfinite(fps) and fps > 0):
         raise ValueError("fps must be positive")
-    as_tensor = _is_tensor(positions) or _is_tensor(orientations)
-    if not _is_tensor(positions):
+    as_tensor = _tables.is_tensor(positions) or _tables.is_tensor(orientations)
+    if not _tables.is_tensor(positions):
         positions = np.asarray(positions, dtype=np.float64)
-    if not _is_tensor(orientations):
+    if not _tables.is_tensor(orientations):
         orientations = np.asarray(orientations, dtype=np.float64)
     psh, osh = tuple(positions.shape), tuple(orientations.shape)
     tracked = len(psh) == 3
@@ -232,13 +202,30 @@ def diffusion_tensor(positions, orientations, lagtime=1, fps=1., ndim=3, pool_tr
         raise ValueError("positions %s and orientations %s do not describe the same tracks and frames" % (psh, osh))
     if n_perm < 1:
         raise ValueError("orientations hold no permutation")
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
+    return positions, orientations, as_tensor, scalar_lag, lags, tracked, n_tracks, n_frames, n_perm
+
+
+def diffusion_tensor(positions, orientations, lagtime=1, fps=1., ndim=3, pool_tracks=False, return_counts=False,
+                     device=0):
+    """Diffusion tensor from positions and bases (``ctr_diffusion_device``), for every track and
+    every lag of a sweep in one call.
+
+    positions: ``[F, 3]`` or ``[T, F, 3]``; orientations: ``[F, 3, 3]``, ``[P, F, 3, 3]`` or, with
+    tracked positions, ``[T, P, F, 3, 3]`` (what :func:`orientation_arrays` returns).  lagtime: an
+    int (frames), or a sequence, which adds a lag axis; ``lag >= F`` gives a NaN tensor.  ndim 2
+    keeps x, y translation and z rotation (3 x 3), ndim 3 gives 6 x 6.
+    Returns ``tensor [T][, n_lags], D, D``: with the reference's argument shapes the reference's
+    shape.  ``pool_tracks``: the mean over the rows of all tracks (the count-weighted mean of the
+    per-track tensors) instead of the track axis.  ``return_counts``: also the number of rows that
+    entered each mean, int64 ``[T][, n_lags]``.  ndarrays in give ndarrays, tensors on
+    ``cuda:device`` give tensors (no host copy)."""
+    positions, orientations, as_tensor, scalar_lag, lags, tracked, n_tracks, n_frames, n_perm = diffusion_inputs(
+        positions, orientations, lagtime, fps, ndim)
     D = 3 if ndim == 2 else 6
-    with torch.cuda.device(dev):
-        pos_t = _to_device(positions, dev, torch.float64, 'positions')
-        ori_t = _to_device(orientations, dev, torch.float64, 'orientations')
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        pos_t = _tables.on_device(positions, dev, torch.float64, 'positions')
+        ori_t = _tables.on_device(orientations, dev, torch.float64, 'orientations')
         lag_t = torch.from_numpy(lags).to(dev)
         tensor = torch.empty((n_tracks, len(lags), D, D), dtype=torch.float64, device=dev)
         counts = torch.empty((n_tracks, len(lags)), dtype=torch.int64, device=dev)

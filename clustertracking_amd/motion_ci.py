@@ -18,8 +18,8 @@ import statistics
 
 import numpy as np
 
-from . import _abi, _lib
-from .motion import _is_tensor, _lag_list, _to_device
+from . import _abi, _tables
+from .motion import diffusion_inputs
 
 _MASK64 = (1 << 64) - 1
 _GOLDEN = 0x9E3779B97F4A7C15
@@ -107,39 +107,15 @@ def diffusion_tensor_ci(positions, orientations, lagtime=1, fps=1., ndim=3, alph
     if n_samples > _abi.DIFFUSION_CI_MAX_SAMPLES:
         raise ValueError("n_samples must be at most %d" % _abi.DIFFUSION_CI_MAX_SAMPLES)
     seed = _check_seed(seed)
-    if ndim not in (2, 3):
-        raise ValueError("ndim must be 2 or 3, not %r" % (ndim,))
-    scalar_lag, lags = _lag_list(lagtime)
-    if not (np.isfinite(fps) and fps > 0):
-        raise ValueError("fps must be positive")
-    as_tensor = _is_tensor(positions) or _is_tensor(orientations)
-    if not _is_tensor(positions):
-        positions = np.asarray(positions, dtype=np.float64)
-    if not _is_tensor(orientations):
-        orientations = np.asarray(orientations, dtype=np.float64)
-    psh, osh = tuple(positions.shape), tuple(orientations.shape)
-    tracked = len(psh) == 3
-    if len(psh) not in (2, 3) or psh[-1] != 3:
-        raise ValueError("positions must be [F, 3] or [T, F, 3], not %s" % (psh,))
-    if osh[-2:] != (3, 3) or len(osh) not in ((5,) if tracked else (3, 4)):
-        raise ValueError("orientations must be %s, not %s"
-                         % ("[T, P, F, 3, 3]" if tracked else "[F, 3, 3] or [P, F, 3, 3]", osh))
-    n_frames = psh[-2]
-    n_tracks = psh[0] if tracked else 1
-    n_perm = osh[-4] if len(osh) >= 4 else 1
-    if osh[-3] != n_frames or (tracked and osh[0] != n_tracks):
-        raise ValueError("positions %s and orientations %s do not describe the same tracks and frames" % (psh, osh))
-    if n_perm < 1:
-        raise ValueError("orientations hold no permutation")
+    positions, orientations, as_tensor, scalar_lag, lags, tracked, n_tracks, n_frames, n_perm = diffusion_inputs(
+        positions, orientations, lagtime, fps, ndim)
     pooled = bool(tracked and pool_tracks)
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
     D, K = 3 if ndim == 2 else 6, len(alphas)
     lead = (len(lags),) if pooled else (n_tracks, len(lags))
-    with torch.cuda.device(dev):
-        pos_t = _to_device(positions, dev, torch.float64, 'positions')
-        ori_t = _to_device(orientations, dev, torch.float64, 'orientations')
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        pos_t = _tables.on_device(positions, dev, torch.float64, 'positions')
+        ori_t = _tables.on_device(orientations, dev, torch.float64, 'orientations')
         lag_t = torch.from_numpy(lags).to(dev)
         interval = torch.empty(lead + (K, D, D), dtype=torch.float64, device=dev)
         ranks = torch.empty(lead + (K, D, D), dtype=torch.int64, device=dev)

@@ -35,10 +35,7 @@ import math
 
 import numpy as np
 
-from . import _abi, _lib
-from .cluster_tracks import _on
-from .drift import _integer, _offsets, _particles, _positions, _table
-from .motion import _is_tensor
+from . import _abi, _tables
 
 MSD = collections.namedtuple('MSD', ['lagt', 'msd', 'mean_d', 'mean_d2', 'n', 'status'])
 EMSD = collections.namedtuple('EMSD', ['lagt', 'msd', 'mean_d', 'mean_d2', 'n', 'status'])
@@ -61,7 +58,7 @@ def _scales(mpp, fps, ndim):
 
 def _selection(particles, n_particles):
     """None, a tensor as it is, or an ascending int64 ndarray of ids within [0, P) (P where it is known)"""
-    if particles is None or _is_tensor(particles):
+    if particles is None or _tables.is_tensor(particles):
         if particles is not None and particles.dim() != 1:
             raise ValueError("particles must be one-dimensional, not %s" % (tuple(particles.shape),))
         return particles
@@ -81,26 +78,24 @@ def _below(particles, n_particles):
 
 
 def _inputs(pos, frame_offset, particle, max_lagtime, mpp, fps, n_particles):
-    max_lagtime = _integer(max_lagtime, 1, 'max_lagtime')
+    max_lagtime = _tables.integer(max_lagtime, 1, 'max_lagtime')
     if max_lagtime > 2 ** 31 - 3:
         raise ValueError("max_lagtime must be an integer below 2^31 - 2")
-    pos, n, ndim = _positions(pos)
+    pos, n, ndim = _tables.positions(pos)
     scale, fps = _scales(mpp, fps, ndim)
-    frame_offset, n_frames = _offsets(frame_offset)
-    particle, n_particles = _particles(particle, n, n_particles)
+    frame_offset, n_frames = _tables.offsets(frame_offset)
+    particle, n_particles = _tables.particles(particle, n, n_particles)
     return pos, n, ndim, frame_offset, n_frames, particle, n_particles, max_lagtime, scale, fps
 
 
 def _device_table(pos, frame_offset, particle, n, n_particles, dev):
     """the three tables on the device, the rows in a stable ascending sort by particle, and P"""
     import torch
-    pos_t = _on(pos, dev, torch.float64, 'pos')
-    off_t = _on(frame_offset, dev, torch.int64, 'frame_offset')
-    par_t = _on(particle, dev, torch.int64, 'particle')
+    pos_t = _tables.on_device(pos, dev, torch.float64, 'pos')
+    off_t = _tables.on_device(frame_offset, dev, torch.int64, 'frame_offset')
+    par_t = _tables.on_device(particle, dev, torch.int64, 'particle')
     if n_particles is None:
-        n_particles = max(int(par_t.max().item()) + 1, 0) if n else 0
-        if n_particles > 2 ** 31 - 2:
-            raise ValueError("more than 2^31 - 2 particles")
+        n_particles = _tables.count_particles(par_t, n)
     # rows are in frame order: one stable sort by particle gives (particle, frame, row) order
     order = torch.sort(par_t, stable=True)[1] if n else par_t
     return pos_t, off_t, par_t, order, n_particles
@@ -144,15 +139,13 @@ def msd_arrays(pos, frame_offset, particle, max_lagtime=100, mpp=1., fps=1., par
     counts pairs.  The same bytes on every call."""
     pos, n, ndim, frame_offset, n_frames, particle, n_particles, max_lagtime, scale, fps = _inputs(
         pos, frame_offset, particle, max_lagtime, mpp, fps, n_particles)
-    as_tensor = _is_tensor(pos)
+    as_tensor = _tables.is_tensor(pos)
     particles = _selection(particles, n_particles)
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
+    with _tables.stage(device) as (eng, dev):
+        import torch
         pos_t, off_t, par_t, order, n_particles = _device_table(pos, frame_offset, particle, n, n_particles, dev)
         _below(particles, n_particles)
-        select = None if particles is None else _on(particles, dev, torch.int64, 'particles')
+        select = None if particles is None else _tables.on_device(particles, dev, torch.int64, 'particles')
         m = n_particles if select is None else int(select.shape[0])
         msd = torch.empty((m, max_lagtime), dtype=torch.float64, device=dev)
         mean_d = torch.empty((m, max_lagtime, ndim), dtype=torch.float64, device=dev)
@@ -167,11 +160,8 @@ def msd_arrays(pos, frame_offset, particle, max_lagtime=100, mpp=1., fps=1., par
         d.msd, d.mean_d, d.mean_d2 = msd.data_ptr() or None, mean_d.data_ptr() or None, mean_d2.data_ptr() or None
         d.n, d.status = count.data_ptr() or None, status.data_ptr()
         eng.on_current_stream(eng.msd_device, d, dev=dev)
-        if as_tensor:
-            return MSD(lagt, msd, mean_d, mean_d2, count, status)
-        if int(status.item()) != _abi.MSD_OK:
-            raise ValueError("msd_arrays: " + _REFUSED)
-        return MSD(*(x.cpu().numpy() for x in (lagt, msd, mean_d, mean_d2, count)), _abi.MSD_OK)
+        out = _tables.results(as_tensor, status, _abi.MSD_OK, "msd_arrays: " + _REFUSED, lagt, msd, mean_d, mean_d2, count)
+        return MSD(*out, status if as_tensor else _abi.MSD_OK)
 
 
 def emsd_arrays(pos, frame_offset, particle, max_lagtime=100, mpp=1., fps=1., n_particles=None, device=0):
@@ -186,11 +176,9 @@ def emsd_arrays(pos, frame_offset, particle, max_lagtime=100, mpp=1., fps=1., n_
     every lag and ``n`` counts pairs."""
     pos, n, ndim, frame_offset, n_frames, particle, n_particles, max_lagtime, scale, fps = _inputs(
         pos, frame_offset, particle, max_lagtime, mpp, fps, n_particles)
-    as_tensor = _is_tensor(pos)
-    eng = _lib.default_engine(device)     # EngineError without a library or a GPU
-    import torch
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
+    as_tensor = _tables.is_tensor(pos)
+    with _tables.stage(device) as (eng, dev):
+        import torch
         pos_t, off_t, par_t, order, n_particles = _device_table(pos, frame_offset, particle, n, n_particles, dev)
         msd = torch.empty(max_lagtime, dtype=torch.float64, device=dev)
         mean_d = torch.empty((max_lagtime, ndim), dtype=torch.float64, device=dev)
@@ -203,16 +191,13 @@ def emsd_arrays(pos, frame_offset, particle, max_lagtime=100, mpp=1., fps=1., n_
         d.msd, d.mean_d, d.mean_d2 = msd.data_ptr(), mean_d.data_ptr(), mean_d2.data_ptr()
         d.n, d.status = count.data_ptr(), status.data_ptr()
         eng.on_current_stream(eng.emsd_device, d, dev=dev)
-        if as_tensor:
-            return EMSD(lagt, msd, mean_d, mean_d2, count, status)
-        if int(status.item()) != _abi.MSD_OK:
-            raise ValueError("emsd_arrays: " + _REFUSED)
-        return EMSD(*(x.cpu().numpy() for x in (lagt, msd, mean_d, mean_d2, count)), _abi.MSD_OK)
+        out = _tables.results(as_tensor, status, _abi.MSD_OK, "emsd_arrays: " + _REFUSED, lagt, msd, mean_d, mean_d2, count)
+        return EMSD(*out, status if as_tensor else _abi.MSD_OK)
 
 
 def _checked(mpp, fps, max_lagtime, f, pos_columns):
     """argument errors of the table forms that do not need the table sorted"""
-    _integer(max_lagtime, 1, 'max_lagtime')
+    _tables.integer(max_lagtime, 1, 'max_lagtime')
     ndim = len(pos_columns) if pos_columns is not None else (3 if 'z' in f else 2)
     if ndim in (2, 3):
         _scales(mpp, fps, ndim)
@@ -228,7 +213,7 @@ def imsd(f, mpp, fps, max_lagtime=100, pos_columns=None, t_column='frame', devic
     for every lag up to ``max_lagtime``, NaN where a track is too short."""
     import pandas as pd
     _checked(mpp, fps, max_lagtime, f, pos_columns)
-    _, offset, _, ids, dense, pos_columns, pos = _table(f, pos_columns, t_column)
+    _, offset, _, ids, dense, pos_columns, pos = _tables.frame_sorted(f, pos_columns, t_column)
     res = msd_arrays(pos, offset, dense, max_lagtime, mpp, fps, n_particles=len(ids), device=device)
     return pd.DataFrame(res.msd.T, index=pd.Index(res.lagt, name='lagt'), columns=pd.Index(ids, name='particle'))
 
@@ -241,7 +226,7 @@ def emsd(f, mpp, fps, max_lagtime=100, detail=False, pos_columns=None, t_column=
     is a row for every lag up to ``max_lagtime``, NaN where no track is long enough."""
     import pandas as pd
     _checked(mpp, fps, max_lagtime, f, pos_columns)
-    _, offset, _, ids, dense, pos_columns, pos = _table(f, pos_columns, t_column)
+    _, offset, _, ids, dense, pos_columns, pos = _tables.frame_sorted(f, pos_columns, t_column)
     res = emsd_arrays(pos, offset, dense, max_lagtime, mpp, fps, n_particles=len(ids), device=device)
     if not detail:
         return pd.Series(res.msd, index=pd.Index(res.lagt, name='lagt'), name='msd')

@@ -13,10 +13,10 @@ import logging
 import numpy as np
 
 from . import _abi
+from ._tables import is_tensor
 from .constraints import engine_constraint
 from .find import find_clusters
 from .fitfunc import FitFunctions
-from .motion import _is_tensor
 from .utils import (ArrayReader, guess_pos_columns, is_isotropic,
                     validate_tuple)
 
@@ -285,7 +285,7 @@ def _check_tables(frames, pos, frame_offset):
     if len(frame_offset.shape) != 1 or frame_offset.shape[0] != n_frames + 1:
         raise ValueError("frame_offset must have one entry per frame and one more (%d), not %s"
                          % (n_frames + 1, tuple(frame_offset.shape)))
-    if not _is_tensor(frame_offset):
+    if not is_tensor(frame_offset):
         if frame_offset.dtype.kind not in 'iu':
             raise ValueError("frame_offset must hold integers, not %s" % frame_offset.dtype)
         if frame_offset[0] != 0 or frame_offset[-1] != n or np.any(np.diff(frame_offset.astype(np.int64)) < 0):
@@ -303,7 +303,7 @@ def _start_values(ff, pos_t, columns, n, dev):
             cols.append(pos_t[:, ff.pos_columns.index(name)])
             continue
         v = columns[name]
-        if _is_tensor(v):
+        if is_tensor(v):
             if v.device != dev:
                 raise ValueError("the %r tensor must be on %s" % (name, dev))
             v = v.to(torch.float64)
@@ -367,7 +367,7 @@ def prepare_arrays(pos, frame_offset, params0, separation, ff, bounds=None, radi
     dev = torch.device('cuda', device)
     templates = ff.validate_bounds(bounds, radius=radius)
     with torch.cuda.device(dev):
-        pos_t, off_t, par_t = (x if _is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=t)).to(dev)
+        pos_t, off_t, par_t = (x if is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=t)).to(dev)
                                for x, t in ((pos, np.float64), (frame_offset, np.int64), (params0, np.float64)))
         if pos_t.dim() != 2 or pos_t.shape[1] not in (2, 3) or tuple(par_t.shape) != (pos_t.shape[0], ff.n_params):
             raise ValueError("pos must be [N, ndim] and params0 [N, %d]" % ff.n_params)
@@ -415,12 +415,12 @@ def refine_arrays(frames, pos, frame_offset, diameter, separation=None, signal=N
     ndarray that decreases or does not run from 0 to N (a tensor's offsets are checked by the stage's
     first kernel and refused at the synchronisation).  ``ValueError("SLSQP Error: ...")`` for a lower
     bound above its upper bound, as ``prepare_batch``.  ``EngineError`` without a library or a GPU."""
-    as_tensor = _is_tensor(pos)
+    as_tensor = is_tensor(pos)
     if not hasattr(frames, 'shape'):
         frames = np.asarray(frames)
     if not as_tensor:
         pos = np.asarray(pos)
-    if not _is_tensor(frame_offset):
+    if not is_tensor(frame_offset):
         frame_offset = np.asarray(frame_offset)
     ndim, n, n_frames = _check_tables(frames, pos, frame_offset)
     diameter, radius, isotropic, separation, ff, cons = _check_options(
@@ -456,7 +456,7 @@ def refine_arrays(frames, pos, frame_offset, diameter, separation=None, signal=N
     from .find import _device_frames
     eng = _lib.default_engine(device)     # EngineError without a library or a GPU
     import torch
-    if not _is_tensor(frames) and frames.dtype not in _abi.DTYPE_CODES:
+    if not is_tensor(frames) and frames.dtype not in _abi.DTYPE_CODES:
         frames = frames.astype(np.float64)     # as HostBatch: refine.py:58
     frames_t, pix = _device_frames(frames, device, None)
     dev = frames_t.device
@@ -468,7 +468,7 @@ def refine_arrays(frames, pos, frame_offset, diameter, separation=None, signal=N
             pos_t = pos.contiguous()
         else:
             pos_t = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.float64)).to(dev)
-        if _is_tensor(frame_offset):
+        if is_tensor(frame_offset):
             if frame_offset.device != dev or frame_offset.dtype != torch.int64:
                 raise ValueError("a frame_offset tensor is int64 on %s" % dev)
             off_t = frame_offset.contiguous()
@@ -521,4 +521,4 @@ def refine_arrays(frames, pos, frame_offset, diameter, separation=None, signal=N
                            cl_status, n_rounds, n_iter, feat_offset.clone())
         if as_tensor:
             return res
-        return RefineResult(*(x.cpu().numpy() if _is_tensor(x) else x for x in res))
+        return RefineResult(*(x.cpu().numpy() if is_tensor(x) else x for x in res))

@@ -14,7 +14,7 @@ import pytest
 import _cases
 import _cluster_tracks as yard
 import clustertracking_amd as ct
-from clustertracking_amd import _abi, _lib
+from clustertracking_amd import _abi, _lib, _tables
 
 ctmod = sys.modules['clustertracking_amd.cluster_tracks']     # ct.cluster_tracks is the function
 
@@ -186,6 +186,19 @@ def test_value_errors_before_the_engine(monkeypatch):
         ct.track_positions_arrays(pos, off, par[:1], np.zeros(2, np.int32), 1, 2)
     with pytest.raises(ValueError, match='n_tracks'):
         ct.track_positions_arrays(pos, off, par, np.zeros(2, np.int32), 2, 2)
+    # the rules of the shared front-end (_tables), as drift and msd have them
+    for P in (True, -1, 1.5):
+        with pytest.raises(ValueError, match='n_particles must be an integer >= 0'):
+            ct.cluster_tracks_arrays(off, par, clu, 2, n_particles=P)
+    with pytest.raises(ValueError, match=r'more than 2\^31 - 2 particles'):
+        ct.cluster_tracks_arrays(off, par, clu, 2, n_particles=2 ** 31 - 1)
+    for bad in (pos > 0, pos.astype(str)):
+        with pytest.raises(ValueError, match='pos must hold numbers, not '):
+            ct.track_positions_arrays(bad, off, par, np.zeros(2, np.int32), 1, 2)
+    import torch
+    assert _tables.count_particles(torch.tensor([0, 2 ** 31 - 3]), 2) == 2 ** 31 - 2
+    with pytest.raises(ValueError, match=r'more than 2\^31 - 2 particles'):       # an id read from a tensor
+        _tables.count_particles(torch.tensor([0, 2 ** 31 - 2]), 2)
     f = pd.DataFrame({'frame': [0, 0], 'y': [1., 2.], 'x': [3., 4.], 'cluster': [0, 0], 'particle': [0, 1]})
     for fn in (ct.cluster_tracks, ct.track_positions):
         with pytest.raises(ValueError, match="'particle'"):
