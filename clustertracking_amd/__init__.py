@@ -24,6 +24,8 @@ from .drift import (compute_drift, subtract_drift, filter_stubs, compute_drift_a
                     filter_stubs_arrays)
 from . import msd
 from .msd import msd_arrays, emsd_arrays, imsd, emsd
+from . import static
+from .static import pair_correlation_arrays, pair_correlation
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -35,7 +37,8 @@ __all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', '
            'write_back', 'motion', 'motion_ci', 'diffusion_tensor_ci', 'bootstrap_indices',
            'cluster_tracks', 'cluster_tracks_arrays', 'track_positions', 'track_positions_arrays',
            'drift', 'compute_drift', 'subtract_drift', 'filter_stubs', 'compute_drift_arrays', 'subtract_drift_arrays',
-           'filter_stubs_arrays', 'msd', 'msd_arrays', 'emsd_arrays', 'imsd', 'emsd']
+           'filter_stubs_arrays', 'msd', 'msd_arrays', 'emsd_arrays', 'imsd', 'emsd',
+           'static', 'pair_correlation_arrays', 'pair_correlation']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

@@ -319,6 +319,27 @@ class Emsd(C.Structure):
     ]
 
 
+PCF_OK, PCF_BAD_TABLE = 0, 1                                   # status[0] of ctr_pair_correlation_device
+PCF_MAX_BINS = 2048                    # edge2 and the histogram of a workgroup are in LDS
+PCF_EDGE_NONE, PCF_EDGE_INTERIOR, PCF_EDGE_ARC = 0, 1, 2       # ctr_pair_correlation.edge
+PCF_EDGE_CODES = {'none': PCF_EDGE_NONE, 'interior': PCF_EDGE_INTERIOR, 'arc': PCF_EDGE_ARC}
+PCF_PAIRS_ALL, PCF_PAIRS_SAME, PCF_PAIRS_OTHER = 0, 1, 2       # ctr_pair_correlation.pairs
+PCF_PAIRS_CODES = {'all': PCF_PAIRS_ALL, 'same': PCF_PAIRS_SAME, 'other': PCF_PAIRS_OTHER}
+
+
+class PairCorrelation(C.Structure):
+    """``ctr_pair_correlation`` (include/ctrefine.h): the pair correlation function of a feature table."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('edge', C.c_int32), ('pairs', C.c_int32), ('reserved0', C.c_int32),
+        ('n_bins', C.c_int64), ('n_frames', C.c_int64), ('n_features', C.c_int64),
+        ('dr', C.c_double), ('mpp', C.c_double * MAX_NDIM),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('group', C.c_void_p),
+        ('box', C.c_void_p), ('edge2', C.c_void_p), ('shell', C.c_void_p),
+        ('g', C.c_void_p), ('g_frame', C.c_void_p), ('count', C.c_void_p), ('weight', C.c_void_p),
+        ('n_ref', C.c_void_p), ('n_rows', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
 PREPARE_BATCH, PREPARE_SCATTER = 0, 1                         # ctr_refine_prepare.mode
 PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
 

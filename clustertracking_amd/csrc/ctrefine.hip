@@ -122,6 +122,7 @@ struct ctr_handle {
   Scratch prepare; // ctr_refine_prepare_device: scaled positions, member counts, ranks, clusters per frame
   Scratch drift;   // ctr_drift_device: the step of every frame
   Scratch msd;     // ctr_msd_device, ctr_emsd_device: the sorted rows, row ranges, partials of the chunks
+  Scratch pcf;     // ctr_pair_correlation_device: the work items of the frames, their partial weights
 };
 
 namespace {
@@ -480,7 +481,7 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1099,6 +1100,10 @@ int ctr_msd_device(ctr_handle* h, const ctr_msd* d, void* hip_stream) {
 
 int ctr_emsd_device(ctr_handle* h, const ctr_emsd* d, void* hip_stream) {
   return run_stage("ctr_emsd_device", h, &ctr_handle::msd, d, hip_stream, ctr_emsd_launch);
+}
+
+int ctr_pair_correlation_device(ctr_handle* h, const ctr_pair_correlation* d, void* hip_stream) {
+  return run_stage("ctr_pair_correlation_device", h, &ctr_handle::pcf, d, hip_stream, ctr_pair_correlation_launch);
 }
 
 int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream) {

@@ -122,7 +122,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
-// tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd)
+// tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd, tu_pair_corr)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -201,5 +201,8 @@ int ctr_filter_stubs_launch(const ctr_filter_stubs* d, StageRun* stage, const ch
 // range of every id and, for the ensemble, a partial per chunk of ids)
 int ctr_msd_launch(const ctr_msd* d, StageRun* stage, const char** msg);
 int ctr_emsd_launch(const ctr_emsd* d, StageRun* stage, const char** msg);
+// pair correlation function of a feature table (pair_corr_kernels.h; scratch: the first work item of
+// every frame and, for the arc correction, a partial weight per work item)
+int ctr_pair_correlation_launch(const ctr_pair_correlation* d, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

@@ -1248,6 +1248,103 @@ typedef struct ctr_emsd {
 } ctr_emsd;
 int ctr_emsd_device(ctr_handle* h, const ctr_emsd* d, void* hip_stream);
 
+/* ---- pair correlation function g(r) of a feature table (ABI 8, additions) ----
+ * The structure of a frame, where the calls above describe dynamics: the bond length inside a
+ * cluster is the first peak of g(r) over the pairs of one cluster, `separation` is the gap behind
+ * it, and crowding is g(r) between clusters.  The reference's users take it from trackpy
+ * (static.pair_correlation_2d / _3d), one kd-tree query per particle and frame; this is an all-pairs
+ * distance histogram per frame and an edge correction per reference row.  The rule is the project's
+ * own dense rule; tests/_pair_correlation.py restates it in NumPy.  Parity with trackpy is not
+ * pinned; it differs in: a ratio estimator (the pooled g is a ratio of sums over the frames, not a
+ * mean of per-particle ratios), the radius of the correction (the middle of the bin), one box for all
+ * frames, coincident rows counted, and a result per frame.
+ * Input: pos [N, ndim], ndim 2 or 3, rows sorted by frame; frame_offset [T + 1]; group [N] or null;
+ * B bins of width dr; mpp per axis, > 0; box [2, ndim] (lo, then hi) in scaled units; edge2 [B + 1]
+ * and shell [B], which the host computes once (clause 1) so that the kernel and the yardstick
+ * compare with the same doubles.
+ *   1. Bins.  B = ceil(cutoff / dr) (the Python layer's); r_edges[b] = b * dr for b = 0 .. B;
+ *      edge2 = r_edges * r_edges; shell[b] = pi * (edge2[b + 1] - edge2[b]) for ndim 2 and
+ *      4/3 * pi * (r_edges[b + 1]^3 - r_edges[b]^3) for ndim 3.
+ *   2. Scaling.  q = pos * mpp per axis, one rounding; everything below is in these units.
+ *   3. Box.  `boundary` of the Python layer, [[lo...], [hi...]] in pixels, times mpp; by default the
+ *      minimum and the maximum of q over all rows of the call, NaN ignored (+inf and -inf where there
+ *      is none): one box for all frames.  V = the product over the axes, in axis order, of hi_a - lo_a.
+ *   4. A row exists when every coordinate is finite and within [lo_a, hi_a].  n_rows[t] counts the
+ *      existing rows of frame t; rho_t = (n_rows[t] - 1) / V.
+ *   5. Reference rows.  CTR_PCF_EDGE_NONE and _ARC: every existing row.  _INTERIOR: the existing
+ *      rows with q_a - lo_a >= r_edges[B] and hi_a - q_a >= r_edges[B] on every axis.  n_ref[t]
+ *      counts them.
+ *   6. Pairs.  A reference row i and an existing row j != i of the same frame are a pair, ordered:
+ *      two reference rows count each other.  CTR_PCF_PAIRS_SAME: also group[i] == group[j] >= 0;
+ *      _OTHER: the pairs that fail that; so count_all == count_same + count_other in every bin.
+ *   7. Binning.  d2 = the sum over the axes, in axis order, of (q_j - q_i)_a squared, every
+ *      product and sum rounded on its own.  The pair falls in bin b iff edge2[b] <= d2 < edge2[b + 1];
+ *      with d2 >= edge2[B] in none; coincident distinct rows (d2 == 0) in bin 0.  count[t, b], int64.
+ *   8. Weight.  weight[t, b] = the sum over the reference rows of frame t, in row order, of phi_i(b).
+ *      _NONE and _INTERIOR: phi = 1, weight[t, b] = n_ref[t].  _ARC (ndim 2): phi_i(b) is the
+ *      fraction of the circle of radius R = r_edges[b] + dr / 2 around row i that lies inside the
+ *      box: the quadrant angles of the four quadrants -- wall distance a along axis 0 in (hi_0 - q_0,
+ *      q_0 - lo_0), b' along axis 1 in (hi_1 - q_1, q_1 - lo_1), added in the order (a, b') = (first,
+ *      first), (first, second), (second, first), (second, second) -- divided by 2 pi.  The quadrant
+ *      angle is pi / 2 when a >= R and b' >= R and max(0, asin(min(b' / R, 1)) - acos(min(a / R, 1)))
+ *      otherwise.  A row further than R from every wall gets exactly 1.0 without trigonometry.
+ *   9. g_frame[t, b] = count[t, b] / ((rho_t * shell[b]) * weight[t, b]); NaN where the denominator
+ *      is not positive and finite: an empty or one-row frame, a degenerate box (V = 0 makes it
+ *      infinite), no reference row.
+ *  10. g[b] = the sum of count[t, b] over t divided by the sum over t, in frame order, of the
+ *      positive finite denominators of clause 9; NaN where no frame has one.
+ * A frame_offset that is not monotone within [0, N] is refused: status[0] = CTR_PCF_BAD_TABLE, g,
+ * g_frame and weight NaN, count, n_ref and n_rows 0, and no kernel follows an offset.
+ * Launches, 256 threads each.  pcf_check.  pcf_frames, one workgroup per frame: n_rows, n_ref, the
+ * counts zeroed.  pcf_items, one workgroup: the exclusive scan of ceil(rows / 256) over the frames.
+ * pcf_pairs: a work item is a frame and a tile of 256 of its rows; their number is known on the
+ * device alone, so T + N / 256 workgroups (its upper bound) are launched, each finds its item in the
+ * scan by bisection and the surplus leaves.  A thread keeps its reference row in registers and walks
+ * the frame's rows, staged 256 at a time in LDS with their group ids; the bin is guessed from
+ * sqrt(d2) / dr and corrected against edge2 (in LDS); the workgroup's histogram, 32-bit LDS atomics,
+ * is added to count[t, :] with 64-bit atomics.  _ARC: one thread per bin then walks the tile's
+ * reference rows in row order and writes the partial weight of the work item to scratch.
+ * pcf_finish, one thread per (t, b): the frame's partials added in item order, g_frame.  pcf_pool,
+ * one thread per bin walking the frames in order: g.  Sums of doubles in a fixed order, integer
+ * atomics only: the same bytes on every call.  (_ARC: weight is the sum of the tiles' sums, each in
+ * row order.)  All pairs of a frame are visited; there is no cell list.
+ * Scratch of the handle: 8 (T + 1) bytes and for _ARC 8 B (T + N / 256) more.
+ * Descriptors are checked before the handle.  Device pointers; asynchronous on `hip_stream`. */
+#define CTR_PCF_OK 0
+#define CTR_PCF_BAD_TABLE 1
+#define CTR_PCF_MAX_BINS 2048        /* edge2 and the histogram of a workgroup are in LDS */
+#define CTR_PCF_EDGE_NONE 0
+#define CTR_PCF_EDGE_INTERIOR 1
+#define CTR_PCF_EDGE_ARC 2
+#define CTR_PCF_PAIRS_ALL 0
+#define CTR_PCF_PAIRS_SAME 1
+#define CTR_PCF_PAIRS_OTHER 2
+typedef struct ctr_pair_correlation {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t edge;                    /* CTR_PCF_EDGE_*; _ARC with ndim 2 only */
+  int32_t pairs;                   /* CTR_PCF_PAIRS_* */
+  int32_t reserved0;
+  int64_t n_bins;                  /* B, 1 .. CTR_PCF_MAX_BINS */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  double dr;                       /* > 0 */
+  double mpp[CTR_MAX_NDIM];        /* per axis, > 0 */
+  const double* pos;               /* [N, ndim] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const int64_t* group;            /* [N], or null with CTR_PCF_PAIRS_ALL */
+  const double* box;               /* [2, ndim]: lo, hi */
+  const double* edge2;             /* [B + 1] */
+  const double* shell;             /* [B] */
+  double* g;                       /* [B] out */
+  double* g_frame;                 /* [T, B] out */
+  int64_t* count;                  /* [T, B] out */
+  double* weight;                  /* [T, B] out */
+  int64_t* n_ref;                  /* [T] out */
+  int64_t* n_rows;                 /* [T] out */
+  int32_t* status;                 /* [1] out */
+} ctr_pair_correlation;
+int ctr_pair_correlation_device(ctr_handle* h, const ctr_pair_correlation* d, void* hip_stream);
+
 /* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
  * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
  * (find_clusters, the stable sort by (frame, cluster), FitFunctions.feature_bounds, the feasibility
