@@ -319,6 +319,25 @@ class Emsd(C.Structure):
     ]
 
 
+VANHOVE_OK, VANHOVE_BAD_TABLE = 0, 1                           # status[0] of ctr_vanhove_device
+VANHOVE_MAX_LAGS, VANHOVE_MAX_HALF_BINS = 64, 1024     # lags of a call; half the bins of a coordinate (counters in LDS)
+
+
+class Vanhove(C.Structure):
+    """``ctr_vanhove`` (include/ctrefine.h): the van Hove displacement distributions of the ensemble."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('n_lags', C.c_int32), ('half_bins', C.c_int64),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64),
+        ('bin_width', C.c_double), ('mpp', C.c_double * MAX_NDIM), ('lag', C.c_int64 * VANHOVE_MAX_LAGS),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('particle', C.c_void_p), ('order', C.c_void_p),
+        ('edges', C.c_void_p), ('edge2', C.c_void_p),
+        ('count', C.c_void_p), ('below', C.c_void_p), ('above', C.c_void_p), ('density', C.c_void_p),
+        ('count_r', C.c_void_p), ('above_r', C.c_void_p), ('density_r', C.c_void_p), ('n', C.c_void_p),
+        ('mean_d', C.c_void_p), ('mean_d2', C.c_void_p), ('mean_d4', C.c_void_p), ('alpha2', C.c_void_p),
+        ('status', C.c_void_p),
+    ]
+
+
 PCF_OK, PCF_BAD_TABLE = 0, 1                                   # status[0] of ctr_pair_correlation_device
 PCF_MAX_BINS = 2048                    # edge2 and the histogram of a workgroup are in LDS
 PCF_EDGE_NONE, PCF_EDGE_INTERIOR, PCF_EDGE_ARC = 0, 1, 2       # ctr_pair_correlation.edge

@@ -60,6 +60,7 @@ SIGNATURES = {
     'ctr_filter_stubs_device': _stage(_abi.FilterStubs),
     'ctr_msd_device': _stage(_abi.Msd),
     'ctr_emsd_device': _stage(_abi.Emsd),
+    'ctr_vanhove_device': _stage(_abi.Vanhove),
     'ctr_pair_correlation_device': _stage(_abi.PairCorrelation),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
     'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
@@ -376,6 +377,7 @@ for _name, _symbol, _too_large in (
         ('filter_stubs_device', 'ctr_filter_stubs_device', False),
         ('msd_device', 'ctr_msd_device', False),
         ('emsd_device', 'ctr_emsd_device', False),
+        ('vanhove_device', 'ctr_vanhove_device', False),
         ('pair_correlation_device', 'ctr_pair_correlation_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))

@@ -121,7 +121,7 @@ struct ctr_handle {
   Scratch tracks;  // ctr_cluster_tracks_device: labels, member counts, the words of the rounds
   Scratch prepare; // ctr_refine_prepare_device: scaled positions, member counts, ranks, clusters per frame
   Scratch drift;   // ctr_drift_device: the step of every frame
-  Scratch msd;     // ctr_msd_device, ctr_emsd_device: the sorted rows, row ranges, partials of the chunks
+  Scratch msd;     // ctr_msd_device, ctr_emsd_device, ctr_vanhove_device: the sorted rows, row ranges, partials of the chunks
   Scratch pcf;     // ctr_pair_correlation_device: the work items of the frames, their partial weights
 };
 
@@ -1100,6 +1100,10 @@ int ctr_msd_device(ctr_handle* h, const ctr_msd* d, void* hip_stream) {
 
 int ctr_emsd_device(ctr_handle* h, const ctr_emsd* d, void* hip_stream) {
   return run_stage("ctr_emsd_device", h, &ctr_handle::msd, d, hip_stream, ctr_emsd_launch);
+}
+
+int ctr_vanhove_device(ctr_handle* h, const ctr_vanhove* d, void* hip_stream) {
+  return run_stage("ctr_vanhove_device", h, &ctr_handle::msd, d, hip_stream, ctr_vanhove_launch);
 }
 
 int ctr_pair_correlation_device(ctr_handle* h, const ctr_pair_correlation* d, void* hip_stream) {

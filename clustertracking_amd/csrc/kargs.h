@@ -201,6 +201,9 @@ int ctr_filter_stubs_launch(const ctr_filter_stubs* d, StageRun* stage, const ch
 // range of every id and, for the ensemble, a partial per chunk of ids)
 int ctr_msd_launch(const ctr_msd* d, StageRun* stage, const char** msg);
 int ctr_emsd_launch(const ctr_emsd* d, StageRun* stage, const char** msg);
+// van Hove displacement distributions (vanhove_kernels.h, in tu_msd; scratch: the sorted rows as above
+// and a partial of the three moments per chunk of ids and lag)
+int ctr_vanhove_launch(const ctr_vanhove* d, StageRun* stage, const char** msg);
 // pair correlation function of a feature table (pair_corr_kernels.h; scratch: the first work item of
 // every frame and, for the arc correction, a partial weight per work item)
 int ctr_pair_correlation_launch(const ctr_pair_correlation* d, StageRun* stage, const char** msg);

@@ -1248,6 +1248,96 @@ typedef struct ctr_emsd {
 } ctr_emsd;
 int ctr_emsd_device(ctr_handle* h, const ctr_emsd* d, void* hip_stream);
 
+/* ---- van Hove displacement distributions of linked particles (ABI 8, an addition) ----
+ * The histogram of the displacements at a lag, per coordinate and radial, pooled over all
+ * particles: what the reference's users take from trackpy's motion.vanhove to see whether the
+ * displacements are Gaussian, which every diffusion coefficient of this library assumes (the D of
+ * the ensemble's MSD, the tensor of ctr_diffusion_device).  Stuck particles and wrong links put
+ * weight in the tails, a residual drift shifts the centre, clusters near a wall give heavy tails
+ * long before the MSD bends.  The rule is this project's own dense rule; tests/_vanhove.py restates
+ * it with plain loops.  Input: the tables of the MSD calls above, `order` included, and K lags.
+ *   1. - 3. are clauses 1 to 3 of the MSD rule, unchanged: of several rows of one frame with the same
+ *      id >= 0 only the lowest exists; rows i (frame t) and j (frame t + k) of one id >= 0 are a pair
+ *      of lag k whatever is missing in between; d_a = (pos[j, a] - pos[i, a]) * mpp_a, one
+ *      subtraction and one product: the same double as there;
+ *   4. lags: lag[0 .. K - 1], ascending distinct integers >= 1 and <= 2^31 - 3, 1 <= K <=
+ *      CTR_VANHOVE_MAX_LAGS = 64; host values, inline in the descriptor, checked by the launch;
+ *   5. bins per coordinate: H = half_bins = ceil(max_disp / bin_width), 1 <= H <=
+ *      CTR_VANHOVE_MAX_HALF_BINS = 1024, B = 2 H bins; edges[b] = (b - H) * bin_width for b = 0 .. 2 H,
+ *      computed by the caller in float64 with one rounding each (so they are symmetric and edges[H]
+ *      is 0.0) and handed over; d_a is in bin b iff edges[b] <= d_a < edges[b + 1]; d_a < edges[0]
+ *      counts in below[k, a], d_a >= edges[2 H] in above[k, a]; a NaN compares false everywhere: it is
+ *      in no bin and in neither tail.  The device guesses the bin by a product with 1 / bin_width;
+ *      the comparison with the edges decides;
+ *   6. radial bins: r_edges[b] = b * bin_width for b = 0 .. H, edge2 = r_edges * r_edges (the
+ *      caller's, handed over); d2 is the sum over the axes, in axis order, of d_a * d_a, every product
+ *      and every sum rounded on its own; the pair is in radial bin b iff edge2[b] <= d2 < edge2[b + 1];
+ *      d2 >= edge2[H] counts in above_r[k]; a NaN d2 nowhere;
+ *   7. counts: n[k] is the number of pairs of lag k over all ids; count[k, a, b], below, above,
+ *      count_r and above_r are int64 and exact.  On finite positions count[k, a].sum() + below[k, a]
+ *      + above[k, a] == n[k] for every a, and count_r[k].sum() + above_r[k] == n[k];
+ *   8. moments: mean_d[k, a], mean_d2[k, a], mean_d4[k, a] are the means over the pairs of d_a, of
+ *      rn(d_a d_a) and of rn(rn(d_a^2) rn(d_a^2)).  They are summed as the ensemble's MSD sums: per
+ *      chunk of CTR_MSD_CHUNK consecutive ids, the chunk's sorted rows strided over the workgroup of
+ *      256, the wavefront's tree, (0 + 1) + (2 + 3) over the wavefronts, then the chunks in chunk
+ *      order.  A thread adds a term of d and of d^2 to its running sum as msd_chunk_kernel is compiled
+ *      to add it, the product and the addition in one fused operation (fma(mpp, diff, sum), fma(d,
+ *      d, sum): one rounding where the plain sum has two); d^4 is rounded, then added.  So mean_d and
+ *      mean_d2 are bit for bit those of ctr_emsd_device at the same lag;
+ *   9. alpha2[k, a] = mean_d4 / (3 * (mean_d2 * mean_d2)) - 1, every operation rounded on its own:
+ *      the one-dimensional non-Gaussian parameter, 0 for a Gaussian, -2/3 for a single value;
+ *  10. density[k, a, b] = count / (n[k] * bin_width); density_r[k, b] = count_r / (n[k] * bin_width),
+ *      per unit r, not divided by the shell.  Where n[k] == 0 (a lag beyond every span, an empty
+ *      table, unlinked rows only) the densities, the means and alpha2 are NaN and the counts 0;
+ *  11. a refused table (status[0] = CTR_VANHOVE_BAD_TABLE: what ctr_emsd_device refuses): the
+ *      floats NaN, the counts and n 0, and no kernel follows an index of the table.
+ * Against trackpy's vanhove: bins are given by a width and a reach, not by a count over the data's
+ * range; the tails are counted rather than dropped; the ensemble only (a histogram per particle is
+ * P B numbers); all coordinates and the radial part in one call; several lags in one call.
+ * Launches, 256 threads each.  The check and the sorted rows of the MSD calls; vanhove_clear zeroes
+ * the int64 tables; vanhove_bin, one workgroup per (chunk, lag): uint32 counters in LDS, ndim (2 H +
+ * 2) + H + 1 of them (a chunk has fewer than 2^31 rows), integer LDS atomics, the moments in
+ * registers; one partial per (chunk, lag) and the non-zero counters added to the int64 tables with
+ * integer atomics: any order gives the same bytes; vanhove_finish, one workgroup per lag: the
+ * partials in chunk order, clauses 8 to 10.  No float atomics.  Scratch of the handle (the block of
+ * the MSD calls): the sorted rows as there and 8 (3 ndim + 1) K ceil(P / 256) bytes of partials.
+ * Descriptors are checked before the handle.  Device pointers; asynchronous on `hip_stream`. */
+#define CTR_VANHOVE_OK 0
+#define CTR_VANHOVE_BAD_TABLE 1
+#define CTR_VANHOVE_MAX_LAGS 64
+#define CTR_VANHOVE_MAX_HALF_BINS 1024
+typedef struct ctr_vanhove {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t n_lags;                  /* K, 1 .. CTR_VANHOVE_MAX_LAGS */
+  int64_t half_bins;               /* H, 1 .. CTR_VANHOVE_MAX_HALF_BINS */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P <= 2^31 - 2 */
+  double bin_width;                /* finite, > 0 */
+  double mpp[CTR_MAX_NDIM];        /* per axis, finite */
+  int64_t lag[CTR_VANHOVE_MAX_LAGS];   /* the first K: ascending, >= 1, <= 2^31 - 3 */
+  const double* pos;               /* [N, ndim] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const int64_t* particle;         /* [N] */
+  const int64_t* order;            /* [N]: as in ctr_msd */
+  const double* edges;             /* [2 H + 1]: clause 5 */
+  const double* edge2;             /* [H + 1]: clause 6 */
+  int64_t* count;                  /* [K, ndim, 2 H] out */
+  int64_t* below;                  /* [K, ndim] out */
+  int64_t* above;                  /* [K, ndim] out */
+  double* density;                 /* [K, ndim, 2 H] out */
+  int64_t* count_r;                /* [K, H] out */
+  int64_t* above_r;                /* [K] out */
+  double* density_r;               /* [K, H] out */
+  int64_t* n;                      /* [K] out */
+  double* mean_d;                  /* [K, ndim] out */
+  double* mean_d2;                 /* [K, ndim] out */
+  double* mean_d4;                 /* [K, ndim] out */
+  double* alpha2;                  /* [K, ndim] out */
+  int32_t* status;                 /* [1] out */
+} ctr_vanhove;
+int ctr_vanhove_device(ctr_handle* h, const ctr_vanhove* d, void* hip_stream);
+
 /* ---- pair correlation function g(r) of a feature table (ABI 8, additions) ----
  * The structure of a frame, where the calls above describe dynamics: the bond length inside a
  * cluster is the first peak of g(r) over the pairs of one cluster, `separation` is the gap behind
