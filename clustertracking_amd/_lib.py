@@ -3,6 +3,7 @@
 There is no CPU fallback: if the library is missing, or no MI355X is visible,
 the calls raise.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -68,6 +69,7 @@ SIGNATURES = {
     'ctr_diffusion_ci_device': _stage(_abi.DiffusionCI),
     'ctr_diffusion_ci_plan': (C.c_int, [_P(_abi.DiffusionCI), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                         _P(C.c_int64)]),
+    'ctr_set_stage_max_grid': (C.c_int32, [_H, C.c_int32]),
     'ctr_query_done': (C.c_int, [_H]),
     'ctr_ipc_alloc': (C.c_int, [_H, C.c_int64, _P(C.c_void_p), C.c_void_p]),
     'ctr_ipc_open': (C.c_int, [_H, C.c_void_p, _P(C.c_void_p)]),
@@ -274,6 +276,26 @@ class Engine(object):
         if rc < 0:
             raise EngineError("ctr_query_done failed: %s" % (self._lib.ctr_last_error(self._h) or b'').decode())
         return rc == 1
+
+    def set_stage_max_grid(self, max_grid):
+        """``ctr_set_stage_max_grid``: the cap on the grids of the table stages' grid-stride kernels
+        for every later stage call of this engine (1 .. 65536; 0: the default, 65536).  Returns the
+        cap before, -1 for a value outside the range (nothing changes)."""
+        return int(self._lib.ctr_set_stage_max_grid(self._h, C.c_int32(int(max_grid))))
+
+    @contextlib.contextmanager
+    def stage_max_grid(self, max_grid):
+        """A test switch: inside the ``with`` block the table stages launch their grid-stride
+        kernels with at most ``max_grid`` workgroups, so that small tables take the trips past the
+        grid; results never depend on it.  The cap before is restored on the way out, also after
+        an exception: the default engine is shared by every call of the process."""
+        before = self.set_stage_max_grid(max_grid)
+        if before < 0:
+            raise ValueError("stage_max_grid: %r is outside [0, 65536]" % (max_grid,))
+        try:
+            yield self
+        finally:
+            self.set_stage_max_grid(before)
 
     def synchronize(self, stream=None):
         self._check(self._lib.ctr_synchronize(self._h, C.c_void_p(stream or 0)),

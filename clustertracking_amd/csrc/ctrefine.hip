@@ -123,6 +123,7 @@ struct ctr_handle {
   Scratch drift;   // ctr_drift_device: the step of every frame
   Scratch msd;     // ctr_msd_device, ctr_emsd_device, ctr_vanhove_device: the sorted rows, row ranges, partials of the chunks
   Scratch pcf;     // ctr_pair_correlation_device: the work items of the frames, their partial weights
+  unsigned stage_max_grid = STAGE_MAX_GRID;   // run_stage: StageRun::max_grid (ctr_set_stage_max_grid)
 };
 
 namespace {
@@ -245,7 +246,7 @@ int run_stage(const char* name, ctr_handle* h, Scratch ctr_handle::*scratch, con
               int (*launch)(const D*, StageRun*, const char**, Extra*...)) {
   const char* msg = "";
   auto failed = [&](int rc, const char* why) { return fail(h, rc, std::string(name) + ": " + why); };
-  StageRun run = {STAGE_CHECK, nullptr, nullptr, 0};
+  StageRun run = {STAGE_CHECK, nullptr, nullptr, 0, h ? h->stage_max_grid : STAGE_MAX_GRID};
   int rc = launch(d, &run, &msg, (Extra*)nullptr...);
   if (rc != CTR_OK) return failed(rc, msg);
   if (!h) return failed(CTR_ERR_INVALID, "null handle");
@@ -1069,7 +1070,7 @@ int ctr_cluster_tracks_plan(const ctr_cluster_tracks* c, int64_t* scratch_bytes,
                             int32_t* jumps_per_round) {
   const char* msg = "";
   ctr_tracks_plan plan = {};
-  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
   const int rc = ctr_cluster_tracks_launch(c, &run, &msg, &plan);
   if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_cluster_tracks_plan: ") + msg);
   if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
@@ -1119,7 +1120,7 @@ int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* 
 int ctr_refine_prepare_plan(const ctr_refine_prepare* r, int64_t* scratch_bytes) {
   const char* msg = "";
   long long bytes = 0;
-  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
   const int rc = ctr_refine_prepare_launch(r, &run, &msg, &bytes);
   if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_refine_prepare_plan: ") + msg);
   if (scratch_bytes) *scratch_bytes = bytes;
@@ -1134,7 +1135,7 @@ int ctr_find_link_refine_device(ctr_handle* h, const ctr_find_link* f, const ctr
 int ctr_relocate_plan(const ctr_relocate* r, int64_t* tile_pixels, int64_t* lds_bytes) {
   const char* msg = "";
   long long tile = 0, lds = 0;
-  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
   const int rc = ctr_relocate_launch(r, &run, &msg, &tile, &lds);
   if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_relocate_plan: ") + msg);
   if (tile_pixels) *tile_pixels = tile;
@@ -1159,7 +1160,7 @@ int ctr_diffusion_ci_plan(const ctr_diffusion_ci* d, int32_t* rows_in_lds, int64
                           int64_t* pairs_per_chunk) {
   const char* msg = "";
   ctr_ci_plan plan = {};
-  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
   const int rc = ctr_diffusion_ci_launch(d, &run, &msg, &plan);
   if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_diffusion_ci_plan: ") + msg);
   if (rows_in_lds) *rows_in_lds = plan.rows_in_lds;
@@ -1167,6 +1168,13 @@ int ctr_diffusion_ci_plan(const ctr_diffusion_ci* d, int32_t* rows_in_lds, int64
   if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
   if (pairs_per_chunk) *pairs_per_chunk = plan.pairs_per_chunk;
   return CTR_OK;
+}
+
+int32_t ctr_set_stage_max_grid(ctr_handle* h, int32_t max_grid) {
+  if (!h || max_grid < 0 || max_grid > (int32_t)STAGE_MAX_GRID) return -1;
+  const int32_t before = (int32_t)h->stage_max_grid;
+  h->stage_max_grid = max_grid ? (unsigned)max_grid : STAGE_MAX_GRID;
+  return before;
 }
 
 int ctr_synchronize(ctr_handle* h, void* hip_stream) {

@@ -502,6 +502,26 @@ __global__ __launch_bounds__(LNK_THREADS) void fl_solve_kernel(FlArgs a, int t) 
   }
 }
 
+// With the refinement, behind link_rank_kernel: that kernel ranks the births of a level by the
+// table's positions, which are the refined ones by then, but a level is linked before it is refined
+// and its births are numbered where they were located.  A birth is always a located row, and its
+// whole-pixel position is still in the descriptor's table: the rank among the births of its level by
+// those.  (Two births of one pixel row whose refined positions come in the other order did swap ids.)
+template <int ND>
+__global__ __launch_bounds__(LNK_THREADS) void fl_birth_rank_kernel(FlArgs a) {
+  const long long stride = (long long)gridDim.x * LNK_THREADS;
+  for (long long i = (long long)blockIdx.x * LNK_THREADS + threadIdx.x; i < a.ncap; i += stride) {
+    if (a.l.link[i] >= 0) continue;
+    const int t = lnk_level_of(a.start, a.n_levels, i);
+    const long long s0 = a.start[t], l0 = a.loc_off[t], n_loc = a.loc_off[t + 1] - l0, local = i - s0;
+    if (t == 0 || local >= n_loc) continue;      // level 0 counts its rows
+    int rank = 0;
+    for (long long j = 0; j < n_loc; ++j)
+      if (j != local && a.l.link[s0 + j] < 0) rank += lnk_row_before<ND>(a.loc_pos, l0 + j, l0 + local) ? 1 : 0;
+    a.l.rank[i] = rank;
+  }
+}
+
 // one workgroup: o_off[t] = live rows of the levels before t
 __global__ __launch_bounds__(LNK_THREADS) void fl_offsets_kernel(FlArgs a) {
   const long long n = workgroup_scan_n<LNK_THREADS, long long>(

@@ -140,6 +140,8 @@ struct StageRun {
   void* scratch;         // STAGE_LAUNCH: a block of scratch_bytes, for a stage that asked for any
   size_t scratch_bytes;  // out; the caller starts it at 0, a stage without scratch leaves it; 0 from a
                          // stage with scratch: nothing to launch
+  unsigned max_grid;     // most workgroups of a grid-stride launch (stage_common.h: stride_grid, frame_grid):
+                         // the handle's cap, STAGE_MAX_GRID where there is no handle; never 0
 };
 int ctr_characterize_launch(const ctr_characterize* c, StageRun* stage, const char** msg);   // characterize_kernels.h
 int ctr_preprocess_launch(const ctr_preprocess* p, StageRun* stage, const char** msg);       // preprocess_kernels.h

@@ -133,7 +133,8 @@ __device__ __forceinline__ void label_frame(const double* spos, int* label, int 
 
 // ---- host -----------------------------------------------------------------------------------
 constexpr size_t STAGE_ALIGN = 256;          // of every part of a stage's scratch
-constexpr unsigned STAGE_MAX_GRID = 1u << 16;   // grid-stride kernels
+constexpr unsigned STAGE_MAX_GRID = 1u << 16;   // grid-stride kernels: the cap of a handle unless lowered
+                                                // (ctr_set_stage_max_grid); it travels as StageRun::max_grid
 
 inline size_t align_up(size_t x) { return (x + STAGE_ALIGN - 1) / STAGE_ALIGN * STAGE_ALIGN; }
 
@@ -145,13 +146,13 @@ inline size_t carve(size_t& at, size_t bytes) {
 }
 
 // workgroups of `threads` for n elements of a grid-stride kernel: at least one, at most max_grid
-inline unsigned stride_grid(long long n, int threads, unsigned max_grid = STAGE_MAX_GRID) {
+inline unsigned stride_grid(long long n, int threads, unsigned max_grid) {
   const long long g = (n + threads - 1) / threads;
   return g < 1 ? 1u : g > (long long)max_grid ? max_grid : (unsigned)g;
 }
 
 // one workgroup per frame, striding past max_grid frames
-inline unsigned frame_grid(long long T, unsigned max_grid = STAGE_MAX_GRID) {
+inline unsigned frame_grid(long long T, unsigned max_grid) {
   return T < (long long)max_grid ? (unsigned)T : max_grid;
 }
 

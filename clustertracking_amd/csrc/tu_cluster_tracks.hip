@@ -67,9 +67,9 @@ int ctr_cluster_tracks_launch(const ctr_cluster_tracks* c, StageRun* stage, cons
     STAGE_TRY(hipMemsetAsync(c->status, 0, sizeof(int32_t), s));
     long long n = a.T + 1 > a.N ? a.T + 1 : a.N;
     n = M > n ? M : n;
-    hipLaunchKernelGGL(ctk_setup_kernel, dim3(stride_grid(n, CTK_THREADS)), block, 0, s, a, 1);
+    hipLaunchKernelGGL(ctk_setup_kernel, dim3(stride_grid(n, CTK_THREADS, stage->max_grid)), block, 0, s, a, 1);
     if (a.T > 0 && a.N > 0)
-      hipLaunchKernelGGL(ctk_groups_kernel, dim3(frame_grid(a.T)), block, 0, s, a);
+      hipLaunchKernelGGL(ctk_groups_kernel, dim3(frame_grid(a.T, stage->max_grid)), block, 0, s, a);
     STAGE_TRY(hipGetLastError());
     return CTR_OK;
   }
@@ -85,7 +85,7 @@ int ctr_cluster_tracks_launch(const ctr_cluster_tracks* c, StageRun* stage, cons
   a.n_members = c->n_members;
   a.n_rounds = c->n_rounds;
   STAGE_TRY(hipMemsetAsync(ws + o_flags, 0, o_A - o_flags, s));
-  const dim3 gP(stride_grid(P, CTK_THREADS)), gM(stride_grid(M, CTK_THREADS));
+  const dim3 gP(stride_grid(P, CTK_THREADS, stage->max_grid)), gM(stride_grid(M, CTK_THREADS, stage->max_grid));
   hipLaunchKernelGGL(ctk_init_kernel, gP, block, 0, s, a);
   bool synced = false;
   for (int r = 0; r < R && M > 0 && P > 1; ++r) {
@@ -99,7 +99,7 @@ int ctr_cluster_tracks_launch(const ctr_cluster_tracks* c, StageRun* stage, cons
       if (!hooked) break;
     }
   }
-  hipLaunchKernelGGL(ctk_verify_kernel, dim3(stride_grid(M > P ? M : P, CTK_THREADS)), block, 0, s, a);
+  hipLaunchKernelGGL(ctk_verify_kernel, dim3(stride_grid(M > P ? M : P, CTK_THREADS, stage->max_grid)), block, 0, s, a);
   hipLaunchKernelGGL(ctk_count_kernel, gP, block, 0, s, a);
   if (nb > 0) hipLaunchKernelGGL(ctk_blocksum_kernel, dim3((unsigned)nb), block, 0, s, a);
   hipLaunchKernelGGL(ctk_scan_kernel, dim3(1), block, 0, s, a, nb);
@@ -146,10 +146,10 @@ int ctr_track_positions_launch(const ctr_track_positions* p, StageRun* stage, co
   STAGE_TRY(hipMemsetAsync(p->status, 0, sizeof(int32_t), s));
   long long n = a.T + 1 > a.N ? a.T + 1 : a.N;
   n = a.P > n ? a.P : n;
-  hipLaunchKernelGGL(ctk_setup_kernel, dim3(stride_grid(n, CTK_THREADS)), block, 0, s, a, 0);
+  hipLaunchKernelGGL(ctk_setup_kernel, dim3(stride_grid(n, CTK_THREADS, stage->max_grid)), block, 0, s, a, 0);
   if (cells > 0) {
-    const dim3 gT(frame_grid(a.T));
-    hipLaunchKernelGGL(ctk_fill_kernel, dim3(stride_grid(cells * a.cs * a.ndim, CTK_THREADS)), block, 0, s, a);
+    const dim3 gT(frame_grid(a.T, stage->max_grid));
+    hipLaunchKernelGGL(ctk_fill_kernel, dim3(stride_grid(cells * a.cs * a.ndim, CTK_THREADS, stage->max_grid)), block, 0, s, a);
     if (a.N > 0) {
       hipLaunchKernelGGL(ctk_present_kernel, gT, block, 0, s, a);
       hipLaunchKernelGGL(ctk_scatter_kernel, gT, block, 0, s, a);

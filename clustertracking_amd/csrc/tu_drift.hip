@@ -43,9 +43,9 @@ int ctr_drift_launch(const ctr_drift* c, StageRun* stage, const char** msg) {
   a.status = c->status;
   const dim3 block(DR_THREADS);
   STAGE_TRY(hipMemsetAsync(c->status, 0, sizeof(int32_t), s));
-  hipLaunchKernelGGL(drift_check_kernel, dim3(stride_grid(a.T + 1 > a.N ? a.T + 1 : a.N, DR_THREADS)), block, 0, s, a);
+  hipLaunchKernelGGL(drift_check_kernel, dim3(stride_grid(a.T + 1 > a.N ? a.T + 1 : a.N, DR_THREADS, stage->max_grid)), block, 0, s, a);
   if (a.T > 0) {
-    hipLaunchKernelGGL(drift_pairs_kernel, dim3(frame_grid(a.T)), block, 0, s, a);
+    hipLaunchKernelGGL(drift_pairs_kernel, dim3(frame_grid(a.T, stage->max_grid)), block, 0, s, a);
     hipLaunchKernelGGL(drift_scan_kernel, dim3(1), block, 0, s, a);
   }
   STAGE_TRY(hipGetLastError());
@@ -75,8 +75,8 @@ int ctr_drift_subtract_launch(const ctr_drift_subtract* c, StageRun* stage, cons
   a.status = c->status;
   const dim3 block(DR_THREADS);
   STAGE_TRY(hipMemsetAsync(c->status, 0, sizeof(int32_t), s));
-  hipLaunchKernelGGL(drift_check_kernel, dim3(stride_grid(a.T + 1, DR_THREADS)), block, 0, s, a);
-  if (a.N > 0) hipLaunchKernelGGL(drift_subtract_kernel, dim3(stride_grid(a.N, DR_THREADS)), block, 0, s, a);
+  hipLaunchKernelGGL(drift_check_kernel, dim3(stride_grid(a.T + 1, DR_THREADS, stage->max_grid)), block, 0, s, a);
+  if (a.N > 0) hipLaunchKernelGGL(drift_subtract_kernel, dim3(stride_grid(a.N, DR_THREADS, stage->max_grid)), block, 0, s, a);
   STAGE_TRY(hipGetLastError());
   return CTR_OK;
 }
@@ -101,7 +101,7 @@ int ctr_filter_stubs_launch(const ctr_filter_stubs* c, StageRun* stage, const ch
   a.particle_out = (long long*)c->particle_out;
   a.count = c->count;
   a.status = c->status;
-  const dim3 block(DR_THREADS), grid(stride_grid(a.N, DR_THREADS));
+  const dim3 block(DR_THREADS), grid(stride_grid(a.N, DR_THREADS, stage->max_grid));
   STAGE_TRY(hipMemsetAsync(c->status, 0, sizeof(int32_t), s));
   if (a.P > 0) STAGE_TRY(hipMemsetAsync(c->count, 0, sizeof(int32_t) * (size_t)a.P, s));
   if (a.N > 0) {

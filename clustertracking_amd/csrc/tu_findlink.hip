@@ -55,13 +55,14 @@ int refine_level(const FlArgs& a, const ctr_refine_com* com, int t, StageRun* su
 }
 
 template <int ND>
-int run(const FlArgs& a, const ctr_relocate& rel, const ctr_refine_com* com, hipStream_t s, const char** msg) {
+int run(const FlArgs& a, const ctr_relocate& rel, const ctr_refine_com* com, const StageRun* stage, const char** msg) {
+  const hipStream_t s = stage->stream;
   const unsigned rows = (unsigned)((a.ncap + LNK_THREADS - 1) / LNK_THREADS);
   hipLaunchKernelGGL(fl_start_kernel, dim3(1), dim3(LNK_THREADS), 0, s, a);
   hipLaunchKernelGGL(fl_fill_kernel<ND>, dim3(rows), dim3(LNK_THREADS), 0, s, a);
   // the host does not read the levels' sizes: a fixed grid strides over a level's rows
   const unsigned per_level = rows < 16u ? rows : 16u;
-  StageRun sub = {STAGE_LAUNCH, s, nullptr, 0};
+  StageRun sub = {STAGE_LAUNCH, s, nullptr, 0, stage->max_grid};
   int rc = refine_level(a, com, 0, &sub, msg);
   if (rc != CTR_OK) return rc;
   for (int t = 1; t < a.n_levels; ++t) {
@@ -74,6 +75,7 @@ int run(const FlArgs& a, const ctr_relocate& rel, const ctr_refine_com* com, hip
     if (rc != CTR_OK) return rc;
   }
   hipLaunchKernelGGL(link_rank_kernel<ND>, dim3(rows), dim3(LNK_THREADS), 0, s, a.l);
+  if (com) hipLaunchKernelGGL(fl_birth_rank_kernel<ND>, dim3(rows), dim3(LNK_THREADS), 0, s, a);
   hipLaunchKernelGGL(link_scan_kernel, dim3(1), dim3(LNK_THREADS), 0, s, a.l);
   for (long long reach = 1; reach < a.n_levels - 1; reach *= 2)
     hipLaunchKernelGGL(link_jump_kernel, dim3(rows), dim3(LNK_THREADS), 0, s, a.l);
@@ -112,7 +114,7 @@ int find_link(const ctr_find_link* f, const ctr_refine_com* com, StageRun* stage
   rel.max_candidates = LNK_MAX_SRC;     // a shortage is at most the sources of a sub-network
   rel.minmass = f->minmass;
   rel.scale_factor = f->scale_factor;
-  StageRun scalars = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+  StageRun scalars = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, stage->max_grid};
   const int rc = ctr_relocate_launch(&rel, &scalars, msg, nullptr, nullptr);
   if (rc != CTR_OK) return rc;
   for (int d = 0; d < f->ndim; ++d) {   // FindLinker.__init__ (find_link.py:766-781), as tu_relocate.hip
@@ -120,7 +122,7 @@ int find_link(const ctr_find_link* f, const ctr_refine_com* com, StageRun* stage
     max_dist = std::max(max_dist, (double)(slr + f->radius[d] + 1) / f->search_range[d]);
   }
   if (com) {   // its own checks of max_iterations, shift_thresh and the window; then the shared fields
-    StageRun com_scalars = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0};
+    StageRun com_scalars = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, stage->max_grid};
     const int rcc = ctr_refine_com_launch(com, &com_scalars, msg, nullptr);
     if (rcc != CTR_OK) return rcc;
     if (com->ndim != f->ndim) { *msg = "the refinement's ndim differs from the find-link descriptor's"; return CTR_ERR_INVALID; }
@@ -194,7 +196,7 @@ int find_link(const ctr_find_link* f, const ctr_refine_com* com, StageRun* stage
   rel.signal = a.r_signal;
   rel.size = a.r_size;
   rel.status = a.r_status;
-  const int rr = f->ndim == 2 ? run<2>(a, rel, com, s, msg) : run<3>(a, rel, com, s, msg);
+  const int rr = f->ndim == 2 ? run<2>(a, rel, com, stage, msg) : run<3>(a, rel, com, stage, msg);
   if (rr != CTR_OK) return rr;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { *msg = hipGetErrorString(e); return CTR_ERR_DEVICE; }

@@ -39,7 +39,9 @@ MsdLayout msd_layout(size_t& total, int ndim, long long N, long long P) {
 }
 
 // status zeroed, the check, the row ranges zeroed, the sorted rows
-hipError_t msd_prepare(MsdArgs& a, const MsdLayout& o, char* scratch, hipStream_t s) {
+hipError_t msd_prepare(MsdArgs& a, const MsdLayout& o, const StageRun* stage) {
+  char* scratch = (char*)stage->scratch;
+  const hipStream_t s = stage->stream;
   a.code = (int*)(scratch + o.code);
   a.key = (int*)(scratch + o.key);
   a.spos = (double*)(scratch + o.spos);
@@ -50,8 +52,8 @@ hipError_t msd_prepare(MsdArgs& a, const MsdLayout& o, char* scratch, hipStream_
   e = hipMemsetAsync(a.first, 0, (size_t)((char*)a.last - (char*)a.first) + sizeof(int) * (size_t)(a.P > 0 ? a.P : 1), s);
   if (e != hipSuccess) return e;
   const dim3 block(MSD_THREADS);
-  hipLaunchKernelGGL(msd_check_kernel, dim3(stride_grid(a.T + 1 > a.N ? a.T + 1 : a.N, MSD_THREADS)), block, 0, s, a);
-  if (a.N > 0) hipLaunchKernelGGL(msd_rows_kernel, dim3(stride_grid(a.N, MSD_THREADS)), block, 0, s, a);
+  hipLaunchKernelGGL(msd_check_kernel, dim3(stride_grid(a.T + 1 > a.N ? a.T + 1 : a.N, MSD_THREADS, stage->max_grid)), block, 0, s, a);
+  if (a.N > 0) hipLaunchKernelGGL(msd_rows_kernel, dim3(stride_grid(a.N, MSD_THREADS, stage->max_grid)), block, 0, s, a);
   return hipSuccess;
 }
 
@@ -86,8 +88,8 @@ int ctr_msd_launch(const ctr_msd* c, StageRun* stage, const char** msg) {
   a.pos = c->pos;
   a.msd = c->msd; a.mean_d = c->mean_d; a.mean_d2 = c->mean_d2; a.n = c->n;
   a.status = c->status;
-  STAGE_TRY(msd_prepare(a, o, (char*)stage->scratch, s));
-  if (a.M > 0) hipLaunchKernelGGL(msd_particle_kernel, dim3(frame_grid(a.M)), dim3(MSD_THREADS), 0, s, a);
+  STAGE_TRY(msd_prepare(a, o, stage));
+  if (a.M > 0) hipLaunchKernelGGL(msd_particle_kernel, dim3(frame_grid(a.M, stage->max_grid)), dim3(MSD_THREADS), 0, s, a);
   STAGE_TRY(hipGetLastError());
   return CTR_OK;
 }
@@ -125,14 +127,14 @@ int ctr_emsd_launch(const ctr_emsd* c, StageRun* stage, const char** msg) {
   a.n_chunks = n_chunks;
   a.msd = c->msd; a.mean_d = c->mean_d; a.mean_d2 = c->mean_d2; a.n_pool = (long long*)c->n;
   a.status = c->status;
-  STAGE_TRY(msd_prepare(a, o, (char*)stage->scratch, s));
+  STAGE_TRY(msd_prepare(a, o, stage));
   const dim3 block(MSD_THREADS);
   // few chunks: their lags are shared among workgroups until about MSD_FILL of them are in flight
   long long groups = n_chunks > 0 ? MSD_FILL / n_chunks : 1;
   groups = groups < 1 ? 1 : groups > a.L ? a.L : groups;
   a.lag_groups = groups;
-  if (n_chunks > 0) hipLaunchKernelGGL(msd_chunk_kernel, dim3(frame_grid(n_chunks * groups)), block, 0, s, a);
-  hipLaunchKernelGGL(msd_pool_kernel, dim3(stride_grid(a.L, MSD_THREADS)), block, 0, s, a);
+  if (n_chunks > 0) hipLaunchKernelGGL(msd_chunk_kernel, dim3(frame_grid(n_chunks * groups, stage->max_grid)), block, 0, s, a);
+  hipLaunchKernelGGL(msd_pool_kernel, dim3(stride_grid(a.L, MSD_THREADS, stage->max_grid)), block, 0, s, a);
   STAGE_TRY(hipGetLastError());
   return CTR_OK;
 }
@@ -192,11 +194,11 @@ int ctr_vanhove_launch(const ctr_vanhove* c, StageRun* stage, const char** msg) 
   v.n = (long long*)c->n;
   v.density = c->density; v.density_r = c->density_r;
   v.mean_d = c->mean_d; v.mean_d2 = c->mean_d2; v.mean_d4 = c->mean_d4; v.alpha2 = c->alpha2;
-  STAGE_TRY(msd_prepare(a, o, (char*)stage->scratch, s));
+  STAGE_TRY(msd_prepare(a, o, stage));
   const dim3 block(MSD_THREADS);
-  hipLaunchKernelGGL(vanhove_clear_kernel, dim3(stride_grid((long long)v.K * a.ndim * 2 * v.H, MSD_THREADS)), block, 0, s, v);
-  if (n_chunks > 0) hipLaunchKernelGGL(vanhove_bin_kernel, dim3(frame_grid(n_chunks * v.K)), block, 0, s, v);
-  hipLaunchKernelGGL(vanhove_finish_kernel, dim3(v.K), block, 0, s, v);
+  hipLaunchKernelGGL(vanhove_clear_kernel, dim3(stride_grid((long long)v.K * a.ndim * 2 * v.H, MSD_THREADS, stage->max_grid)), block, 0, s, v);
+  if (n_chunks > 0) hipLaunchKernelGGL(vanhove_bin_kernel, dim3(frame_grid(n_chunks * v.K, stage->max_grid)), block, 0, s, v);
+  hipLaunchKernelGGL(vanhove_finish_kernel, dim3(frame_grid(v.K, stage->max_grid)), block, 0, s, v);
   STAGE_TRY(hipGetLastError());
   return CTR_OK;
 }

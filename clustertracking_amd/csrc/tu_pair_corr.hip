@@ -71,12 +71,12 @@ int ctr_pair_correlation_launch(const ctr_pair_correlation* c, StageRun* stage, 
   a.status = c->status;
   STAGE_TRY(hipMemsetAsync(a.status, 0, sizeof(int32_t), s));
   const dim3 block(PCF_THREADS);
-  hipLaunchKernelGGL(pcf_check_kernel, dim3(stride_grid(a.T + 1, PCF_THREADS)), block, 0, s, a);
-  if (a.T > 0) hipLaunchKernelGGL(pcf_frames_kernel, dim3(frame_grid(a.T)), block, 0, s, a);
+  hipLaunchKernelGGL(pcf_check_kernel, dim3(stride_grid(a.T + 1, PCF_THREADS, stage->max_grid)), block, 0, s, a);
+  if (a.T > 0) hipLaunchKernelGGL(pcf_frames_kernel, dim3(frame_grid(a.T, stage->max_grid)), block, 0, s, a);
   hipLaunchKernelGGL(pcf_items_kernel, dim3(1), block, 0, s, a);
-  if (max_items > 0) hipLaunchKernelGGL(pcf_pairs_kernel, dim3(frame_grid(max_items)), block, 0, s, a);
-  if (a.T > 0) hipLaunchKernelGGL(pcf_finish_kernel, dim3(stride_grid(a.T * a.B, PCF_THREADS)), block, 0, s, a);
-  hipLaunchKernelGGL(pcf_pool_kernel, dim3(stride_grid(a.B, PCF_THREADS)), block, 0, s, a);
+  if (max_items > 0) hipLaunchKernelGGL(pcf_pairs_kernel, dim3(frame_grid(max_items, stage->max_grid)), block, 0, s, a);
+  if (a.T > 0) hipLaunchKernelGGL(pcf_finish_kernel, dim3(stride_grid(a.T * a.B, PCF_THREADS, stage->max_grid)), block, 0, s, a);
+  hipLaunchKernelGGL(pcf_pool_kernel, dim3(stride_grid(a.B, PCF_THREADS, stage->max_grid)), block, 0, s, a);
   STAGE_TRY(hipGetLastError());
   return CTR_OK;
 }

@@ -20,23 +20,26 @@ namespace {
 // larger and 3D windows take the wavefront
 constexpr long long RFC_ROW_WINDOW = 17 * 17;
 // workgroups of a level of ctr_find_link_refine_device: its rows are counted on the device, so a
-// fixed grid strides over them
+// fixed grid strides over them (fewer where the handle's cap is lower: StageRun::max_grid)
 constexpr unsigned RFC_LEVEL_GRID = 32;
 
 template <int ND, typename T, int G>
-void launch_g(const RfcArgs& a, long long rows, hipStream_t s) {
+void launch_g(const RfcArgs& a, long long rows, const StageRun* stage) {
   const long long per = RFC_THREADS / G;
   unsigned grid = (unsigned)((rows + per - 1) / per);
-  if (a.level_cnt) grid = grid < RFC_LEVEL_GRID ? grid : RFC_LEVEL_GRID;
-  hipLaunchKernelGGL((refine_com_kernel<ND, T, G>), dim3(grid), dim3(RFC_THREADS), 0, s, a);
+  if (a.level_cnt) {
+    const unsigned cap = RFC_LEVEL_GRID < stage->max_grid ? RFC_LEVEL_GRID : stage->max_grid;
+    grid = grid < cap ? grid : cap;
+  }
+  hipLaunchKernelGGL((refine_com_kernel<ND, T, G>), dim3(grid), dim3(RFC_THREADS), 0, stage->stream, a);
 }
 
 // rows: the features, or a bound on the rows of a level
 template <typename T>
-void launch(int ndim, const RfcArgs& a, long long vol, long long rows, hipStream_t s) {
-  if (ndim == 3) launch_g<3, T, 64>(a, rows, s);
-  else if (vol <= RFC_ROW_WINDOW) launch_g<2, T, 16>(a, rows, s);
-  else launch_g<2, T, 64>(a, rows, s);
+void launch(int ndim, const RfcArgs& a, long long vol, long long rows, const StageRun* stage) {
+  if (ndim == 3) launch_g<3, T, 64>(a, rows, stage);
+  else if (vol <= RFC_ROW_WINDOW) launch_g<2, T, 16>(a, rows, stage);
+  else launch_g<2, T, 64>(a, rows, stage);
 }
 
 }  // namespace
@@ -91,19 +94,18 @@ int ctr_refine_com_launch(const ctr_refine_com* c, StageRun* stage, const char**
     a.n_iter = c->n_iter;
   }
   if (stage->mode != STAGE_LAUNCH || rows <= 0) return CTR_OK;
-  const hipStream_t s = stage->stream;
   a.frames = c->frames;
   a.frame_elems = E;
   a.n_frames = (int)c->n_frames;
   a.max_iterations = c->max_iterations;
   a.shift_thresh = c->shift_thresh;
   switch (c->frame_dtype) {
-    case CTR_DTYPE_U8: launch<uint8_t>(c->ndim, a, vol, rows, s); break;
-    case CTR_DTYPE_U16: launch<uint16_t>(c->ndim, a, vol, rows, s); break;
-    case CTR_DTYPE_I16: launch<int16_t>(c->ndim, a, vol, rows, s); break;
-    case CTR_DTYPE_I32: launch<int32_t>(c->ndim, a, vol, rows, s); break;
-    case CTR_DTYPE_F32: launch<float>(c->ndim, a, vol, rows, s); break;
-    default: launch<double>(c->ndim, a, vol, rows, s); break;
+    case CTR_DTYPE_U8: launch<uint8_t>(c->ndim, a, vol, rows, stage); break;
+    case CTR_DTYPE_U16: launch<uint16_t>(c->ndim, a, vol, rows, stage); break;
+    case CTR_DTYPE_I16: launch<int16_t>(c->ndim, a, vol, rows, stage); break;
+    case CTR_DTYPE_I32: launch<int32_t>(c->ndim, a, vol, rows, stage); break;
+    case CTR_DTYPE_F32: launch<float>(c->ndim, a, vol, rows, stage); break;
+    default: launch<double>(c->ndim, a, vol, rows, stage); break;
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { *msg = hipGetErrorString(e); return CTR_ERR_DEVICE; }

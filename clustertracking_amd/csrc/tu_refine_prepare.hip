@@ -69,7 +69,7 @@ int ctr_refine_prepare_launch(const ctr_refine_prepare* r, StageRun* stage, cons
     if (N == 0) return CTR_OK;
     a.fit_params = r->fit_params; a.fit_cost = r->fit_cost; a.fit_std = r->fit_std;
     a.params_out = r->params_out; a.cost_out = r->cost_out; a.std_out = r->std_out;
-    hipLaunchKernelGGL(rp_scatter_kernel, dim3(stride_grid(N * a.np, RP_THREADS)), block, 0, s, a);
+    hipLaunchKernelGGL(rp_scatter_kernel, dim3(stride_grid(N * a.np, RP_THREADS, stage->max_grid)), block, 0, s, a);
     STAGE_TRY(hipGetLastError());
     return CTR_OK;
   }
@@ -93,8 +93,8 @@ int ctr_refine_prepare_launch(const ctr_refine_prepare* r, StageRun* stage, cons
   a.params = r->params; a.low = r->low; a.high = r->high;
   a.status = r->status;
   STAGE_TRY(hipMemsetAsync(r->status, 0, 2 * sizeof(int32_t), s));
-  hipLaunchKernelGGL(rp_setup_kernel, dim3(stride_grid(T + 1 > N ? T + 1 : N, RP_THREADS)), block, 0, s, a);
-  const dim3 gT(frame_grid(T));
+  hipLaunchKernelGGL(rp_setup_kernel, dim3(stride_grid(T + 1 > N ? T + 1 : N, RP_THREADS, stage->max_grid)), block, 0, s, a);
+  const dim3 gT(frame_grid(T, stage->max_grid));
   if (T > 0 && N > 0) {
     if (r->ndim == 2) hipLaunchKernelGGL(rp_label_kernel<2>, gT, block, 0, s, a);
     else hipLaunchKernelGGL(rp_label_kernel<3>, gT, block, 0, s, a);
@@ -104,7 +104,7 @@ int ctr_refine_prepare_launch(const ctr_refine_prepare* r, StageRun* stage, cons
   hipLaunchKernelGGL(rp_scan_kernel, dim3(1), block, 0, s, a);
   if (T > 0 && N > 0) {
     hipLaunchKernelGGL(rp_tables_kernel, gT, block, 0, s, a, b);
-    hipLaunchKernelGGL(rp_feasible_kernel, dim3(stride_grid(N, RP_THREADS)), block, 0, s, a);
+    hipLaunchKernelGGL(rp_feasible_kernel, dim3(stride_grid(N, RP_THREADS, stage->max_grid)), block, 0, s, a);
   }
   STAGE_TRY(hipGetLastError());
   return CTR_OK;

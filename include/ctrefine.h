@@ -1518,6 +1518,16 @@ int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* 
 /* No device needed: the scratch of a call (0 for CTR_PREPARE_SCATTER). */
 int ctr_refine_prepare_plan(const ctr_refine_prepare* r, int64_t* scratch_bytes);
 
+/* A test switch: the most workgroups that a grid-stride kernel of the table stages is launched with
+ * by every later stage call of this handle (refine_prepare, drift, msd / emsd, vanhove,
+ * pair_correlation, cluster_tracks / track_positions, and the per-level refinement of
+ * ctr_find_link_refine_device, whose fixed grid is lowered to it).  max_grid within [1, 65536], or
+ * 0 for the default of 65536.  Returns the cap that held before; a null handle or a value outside
+ * the range returns -1 and changes nothing.  A stage's results never depend on it: every such
+ * kernel strides past its grid, and the suite lowers the cap to make small tables take those
+ * further trips.  Not synchronised with calls of other threads on the same handle. */
+int32_t ctr_set_stage_max_grid(ctr_handle* h, int32_t max_grid);
+
 /* Has the last ctr_refine_batch_device call of this handle finished on the device?  1 yes (also
  * when there was none), 0 still running, -1 error.  Never blocks: lets a pipeline that keeps
  * several batches in flight hand finished batches on (e.g. to the result gather) from the host
