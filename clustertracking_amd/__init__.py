@@ -26,7 +26,7 @@ from . import msd
 from .msd import msd_arrays, emsd_arrays, imsd, emsd
 from .vanhove import vanhove_arrays, vanhove     # the function shadows the submodule: importlib.import_module reaches it
 from . import static
-from .static import pair_correlation_arrays, pair_correlation
+from .static import pair_correlation_arrays, pair_correlation, neighbors_arrays, neighbors, proximity
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -39,7 +39,8 @@ __all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', '
            'cluster_tracks', 'cluster_tracks_arrays', 'track_positions', 'track_positions_arrays',
            'drift', 'compute_drift', 'subtract_drift', 'filter_stubs', 'compute_drift_arrays', 'subtract_drift_arrays',
            'filter_stubs_arrays', 'msd', 'msd_arrays', 'emsd_arrays', 'imsd', 'emsd',
-           'vanhove_arrays', 'vanhove', 'static', 'pair_correlation_arrays', 'pair_correlation']
+           'vanhove_arrays', 'vanhove', 'static', 'pair_correlation_arrays', 'pair_correlation',
+           'neighbors_arrays', 'neighbors', 'proximity']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

@@ -359,6 +359,23 @@ class PairCorrelation(C.Structure):
     ]
 
 
+NBR_OK, NBR_BAD_TABLE = 0, 1                                   # status[0] of ctr_neighbors_device
+NBR_MAX_K = 16                         # the largest list a thread keeps in registers
+
+
+class Neighbors(C.Structure):
+    """``ctr_neighbors`` (include/ctrefine.h): nearest neighbours and proximity of a feature table;
+    ``pairs`` takes the ``PCF_PAIRS_*`` codes."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('pairs', C.c_int32), ('k', C.c_int32), ('lag', C.c_int32),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64),
+        ('limit2', C.c_double), ('mpp', C.c_double * MAX_NDIM),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('group', C.c_void_p), ('particle', C.c_void_p),
+        ('dist', C.c_void_p), ('dist2', C.c_void_p), ('index', C.c_void_p), ('count', C.c_void_p),
+        ('particle_min', C.c_void_p), ('particle_min2', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
 PREPARE_BATCH, PREPARE_SCATTER = 0, 1                         # ctr_refine_prepare.mode
 PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
 

@@ -63,6 +63,7 @@ SIGNATURES = {
     'ctr_emsd_device': _stage(_abi.Emsd),
     'ctr_vanhove_device': _stage(_abi.Vanhove),
     'ctr_pair_correlation_device': _stage(_abi.PairCorrelation),
+    'ctr_neighbors_device': _stage(_abi.Neighbors),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
     'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
@@ -401,6 +402,7 @@ for _name, _symbol, _too_large in (
         ('emsd_device', 'ctr_emsd_device', False),
         ('vanhove_device', 'ctr_vanhove_device', False),
         ('pair_correlation_device', 'ctr_pair_correlation_device', False),
+        ('neighbors_device', 'ctr_neighbors_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 

@@ -123,6 +123,7 @@ struct ctr_handle {
   Scratch drift;   // ctr_drift_device: the step of every frame
   Scratch msd;     // ctr_msd_device, ctr_emsd_device, ctr_vanhove_device: the sorted rows, row ranges, partials of the chunks
   Scratch pcf;     // ctr_pair_correlation_device: the work items of the frames, their partial weights
+  Scratch nbr;     // ctr_neighbors_device: the work items of the frames, the keys of the particles
   unsigned stage_max_grid = STAGE_MAX_GRID;   // run_stage: StageRun::max_grid (ctr_set_stage_max_grid)
 };
 
@@ -482,7 +483,7 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1109,6 +1110,10 @@ int ctr_vanhove_device(ctr_handle* h, const ctr_vanhove* d, void* hip_stream) {
 
 int ctr_pair_correlation_device(ctr_handle* h, const ctr_pair_correlation* d, void* hip_stream) {
   return run_stage("ctr_pair_correlation_device", h, &ctr_handle::pcf, d, hip_stream, ctr_pair_correlation_launch);
+}
+
+int ctr_neighbors_device(ctr_handle* h, const ctr_neighbors* d, void* hip_stream) {
+  return run_stage("ctr_neighbors_device", h, &ctr_handle::nbr, d, hip_stream, ctr_neighbors_launch);
 }
 
 int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream) {

@@ -122,7 +122,8 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
-// tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd, tu_pair_corr)
+// tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd, tu_pair_corr,
+// tu_neighbors)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -209,5 +210,8 @@ int ctr_vanhove_launch(const ctr_vanhove* d, StageRun* stage, const char** msg);
 // pair correlation function of a feature table (pair_corr_kernels.h; scratch: the first work item of
 // every frame and, for the arc correction, a partial weight per work item)
 int ctr_pair_correlation_launch(const ctr_pair_correlation* d, StageRun* stage, const char** msg);
+// nearest neighbours and proximity of a feature table (neighbors_kernels.h; scratch: the first work item
+// of every frame and a key per particle)
+int ctr_neighbors_launch(const ctr_neighbors* d, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

@@ -48,6 +48,40 @@ there is one box for all frames; coincident rows are counted; there is a result 
 row is a reference (no ``fraction`` or ``p_indices`` sampling).  Parity with trackpy itself is not pinned by a
 test: it is not a dependency.  All pairs of a frame are visited; there is no cell list.
 
+Nearest neighbours and proximity (``neighbors_arrays``, ``neighbors``, ``proximity``;
+``ctr_neighbors_device``) are the structure per feature, where g(r) is pooled: how far every row is from
+its nearest rows, which rows those are, and how many lie within a distance.  Within a frame (``lag=0``)
+that is the upper bound of ``search_range``, the coordination number and, with ``pairs='same'``, the bond
+length per cluster and frame; from frame t into frame t + 1 (``lag=1``) it is the displacement that
+``search_range`` must exceed; with ``pairs='other'`` it is the filter that keeps ``cluster_tracks``,
+``motion`` and ``diffusion_tensor_ci`` to clusters that diffuse freely.  trackpy has ``static.proximity``
+for the first; parity with it is not pinned.  The rule (``include/ctrefine.h``, DESIGN.md 7b;
+``tests/_neighbors.py`` restates it in NumPy):
+
+1. Scaling.  ``q = pos * mpp`` per axis, one rounding: clause 2 above.
+2. A row exists when every coordinate of ``q`` is finite.  There is no box.
+3. Candidates.  The candidates of row ``i`` of frame ``t`` are the existing rows ``j`` of frame ``t + lag``;
+   with ``lag == 0``, ``j == i`` is excluded; a row of a frame with ``t + lag >= T`` has no candidate.
+   ``pairs='same'``: also ``group[i] == group[j] >= 0``; ``'other'``: the candidates that fail that.
+4. Distance.  ``d2`` is the sum over the axes, in axis order, of ``(q_j - q_i)_a`` squared, every product
+   and sum rounded on its own.  A candidate qualifies when ``d2 < limit2``, strictly: a row at exactly
+   ``max_dist`` does not.  ``limit2 = max_dist * max_dist``, computed once on the host; ``+inf`` without.
+5. ``count[i]`` is the number of qualifying candidates, exact: a coordination number with ``max_dist``.
+6. Neighbours.  The qualifying candidates sorted by ``(d2, j)`` ascending; the first ``k`` are the
+   neighbours: ``dist2[i, m]`` their ``d2``, ``index[i, m]`` their global row, ``dist[i, m] =
+   sqrt(dist2[i, m])``.  Coincident rows (``d2 == 0``) are neighbours like any other.  Where fewer than
+   ``k`` qualify, the remaining entries are NaN, NaN and -1.
+7. Rows with no result: a row that does not exist, a row of a frame without a candidate frame and a row
+   outside ``[frame_offset[0], frame_offset[T])`` get NaN, -1 and 0, and are nobody's neighbour.
+8. Per particle (with ``particle`` and ``n_particles = P``).  ``particle_min2[p]`` is the minimum of
+   ``dist2[i, 0]`` over the rows with ``particle[i] == p`` that have a neighbour, ``particle_min[p]`` its
+   square root, NaN where there is none; rows with an id outside ``[0, P)`` contribute nowhere.
+9. A refused table.  A ``frame_offset`` that does not rise within ``[0, N]``: ``status[0] =
+   _abi.NBR_BAD_TABLE``, every float output NaN, ``index`` -1, ``count`` 0; ``ValueError`` for ndarrays.
+
+All rows of the candidate frame are visited; every output element has one owner thread, so the same
+bytes come back on every call.
+
 There is no CPU fallback: without the library or a GPU the calls raise ``EngineError``; argument
 errors are raised before that.
 """
@@ -59,8 +93,10 @@ import numpy as np
 from . import _abi, _tables
 
 PairCorrelation = collections.namedtuple('PairCorrelation', ['r_edges', 'g', 'g_frame', 'count', 'weight', 'n_ref', 'n_rows', 'status'])
+Neighbors = collections.namedtuple('Neighbors', ['dist', 'dist2', 'index', 'count', 'particle_min', 'particle_min2', 'status'])
 
 _REFUSED = "pair_correlation_arrays: frame_offset must rise within [0, N]"
+_NBR_REFUSED = "neighbors_arrays: frame_offset must rise within [0, N]"
 
 
 def _positive(value, what):
@@ -241,3 +277,132 @@ def pair_correlation(f, cutoff, dr=0.5, mpp=1., boundary=None, edge='arc', group
         return res.r_edges, res.g
     frames = pd.RangeIndex(first, first + len(offset) - 1, name=t_column)
     return res.r_edges, pd.DataFrame(res.g_frame, index=frames, columns=pd.Index(res.r_edges[:-1], name='r'))
+
+
+def neighbors_arrays(pos, frame_offset, k=1, mpp=1., max_dist=None, group=None, pairs='all', lag=0, particle=None,
+                     n_particles=None, device=0):
+    """The ``k`` nearest rows of every row among the rows of the frame ``lag`` frames on, how many lie
+    within ``max_dist`` and, per particle, the smallest nearest-neighbour distance
+    (``ctr_neighbors_device``; the module's rule, where trackpy has ``static.proximity`` and a
+    ``cKDTree`` per frame).
+
+    pos float64 ``[N, ndim]``, ndim 2 or 3, rows sorted by frame; frame_offset int64 ``[T + 1]``: what
+    ``locate_arrays``, ``find_link_arrays``, ``refine_arrays`` and ``subtract_drift_arrays`` return, as
+    ndarrays or as tensors on ``cuda:device``.  k: 1 .. ``_abi.NBR_MAX_K``.  mpp: microns per pixel, a
+    number or one per axis.  max_dist: only rows nearer than this, in the units of ``pos * mpp``, are
+    neighbours and are counted; default no limit.  group: int64 ``[N]``, e.g. the cluster labels; pairs:
+    ``'all'``, ``'same'`` (both rows of one group ``>= 0``) or ``'other'``.  lag: 0 for the neighbours
+    within a frame, 1 for those of frame t in frame t + 1.  particle: int64 ``[N]`` with ids in
+    ``[0, n_particles)`` (default ``particle.max() + 1``, one host read for a tensor).
+
+    Returns ``Neighbors(dist [N, k], dist2 [N, k], index int64 [N, k], count int64 [N], particle_min [P]
+    or None, particle_min2 [P] or None, status)``: ndarrays and an int for ndarrays, tensors (status: int32
+    ``[1]``) for a tensor ``pos``, and then nothing is read back to the host.  NaN and -1 where a row has
+    fewer than ``k`` neighbours.  A frame_offset that does not rise within ``[0, N]`` raises ``ValueError``
+    for ndarrays; for tensors status is ``_abi.NBR_BAD_TABLE``, the distances NaN, index -1 and count 0.
+    The same bytes on every call."""
+    pos, n, ndim = _tables.positions(pos)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _abi.NBR_MAX_K:
+        raise ValueError("k must be an integer within 1 .. %d, not %r" % (_abi.NBR_MAX_K, k))
+    if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= lag <= 2 ** 31 - 1:
+        raise ValueError("lag must be an integer >= 0, not %r" % (lag,))
+    limit2 = math.inf
+    if max_dist is not None:
+        limit2 = _positive(max_dist, 'max_dist') ** 2
+        if not limit2 > 0:
+            raise ValueError("max_dist squared must be positive, not %r" % (limit2,))
+    scale = _scales(mpp, ndim)
+    if pairs not in _abi.PCF_PAIRS_CODES:
+        raise ValueError("pairs must be one of 'all', 'same', 'other', not %r" % (pairs,))
+    if pairs != 'all' and group is None:
+        raise ValueError("pairs=%r needs a group" % (pairs,))
+    frame_offset, n_frames = _tables.offsets(frame_offset)
+    if group is not None:
+        if _tables.is_tensor(group) and str(group.dtype) != 'torch.int64':
+            raise ValueError("a group tensor is int64, not %s" % (group.dtype,))
+        group = _tables.column(group, n, 'group')
+    if particle is None and n_particles is not None:
+        raise ValueError("n_particles needs a particle column")
+    if particle is not None:
+        if _tables.is_tensor(particle) and str(particle.dtype) != 'torch.int64':
+            raise ValueError("a particle tensor is int64, not %s" % (particle.dtype,))
+        particle, n_particles = _tables.particles(particle, n, n_particles)
+    if n_frames > 2 ** 31 - 3 or n > 2 ** 31 - 1:
+        raise ValueError("too many frames or features for one call")
+    as_tensor = _tables.is_tensor(pos)
+    k, lag = int(k), int(lag)
+    with _tables.stage(device) as (eng, dev):
+        import torch
+        pos_t = _tables.on_device(pos, dev, torch.float64, 'pos')
+        off_t = _tables.on_device(frame_offset, dev, torch.int64, 'frame_offset')
+        group_t = None if group is None else _tables.on_device(group, dev, torch.int64, 'group')
+        par_t = None if particle is None else _tables.on_device(particle, dev, torch.int64, 'particle')
+        if par_t is not None and n_particles is None:
+            n_particles = _tables.count_particles(par_t, n)
+        dist = torch.empty((n, k), dtype=torch.float64, device=dev)
+        dist2 = torch.empty((n, k), dtype=torch.float64, device=dev)
+        index = torch.empty((n, k), dtype=torch.int64, device=dev)
+        count = torch.empty(n, dtype=torch.int64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        per_particle = ()
+        if par_t is not None:
+            per_particle = (torch.empty(n_particles, dtype=torch.float64, device=dev),
+                            torch.empty(n_particles, dtype=torch.float64, device=dev))
+        d = _abi.Neighbors()
+        d.ndim, d.pairs, d.k, d.lag = ndim, _abi.PCF_PAIRS_CODES[pairs], k, lag
+        d.n_frames, d.n_features, d.n_particles, d.limit2 = n_frames, n, n_particles or 0, limit2
+        for a in range(ndim):
+            d.mpp[a] = float(scale[a])
+        d.pos, d.frame_offset = pos_t.data_ptr() or None, off_t.data_ptr()
+        d.group = None if group_t is None else (group_t.data_ptr() or None)
+        d.particle = None if par_t is None else (par_t.data_ptr() or None)
+        d.dist, d.dist2, d.index, d.count = (x.data_ptr() or None for x in (dist, dist2, index, count))
+        if per_particle:
+            d.particle_min, d.particle_min2 = (x.data_ptr() or None for x in per_particle)
+        d.status = status.data_ptr()
+        eng.on_current_stream(eng.neighbors_device, d, dev=dev)
+        out = _tables.results(as_tensor, status, _abi.NBR_OK, _NBR_REFUSED, dist, dist2, index, count, *per_particle)
+        return Neighbors(*(tuple(out) + (() if per_particle else (None, None))), status if as_tensor else _abi.NBR_OK)
+
+
+def neighbors(f, k=1, mpp=1., max_dist=None, group_column=None, pairs='all', lag=0, pos_columns=None,
+              t_column='frame', device=0):
+    """The nearest neighbours of every row of a table of features: ``(dist [len(f), k], neighbor
+    [len(f), k], count [len(f)])`` in the row order of ``f`` -- the distances, the positions in ``f`` of
+    the neighbours as for ``.iloc`` (-1 where there is none, the distance NaN) and the number of rows
+    within ``max_dist``.  What ``cKDTree.query`` per frame gives a user of trackpy, by the module's rule;
+    parity with trackpy is not pinned: it is not a dependency.
+
+    f: a DataFrame with the position columns (default ``['y', 'x']``, with ``'z'`` in front where the
+    table has one) and ``t_column``; no ``particle`` column is needed.  The frames are taken dense from
+    the first to the last, so ``lag`` counts frame numbers.  group_column: an integer column such as
+    ``'cluster'``, ``'particle'`` or ``'cluster_track'`` for ``pairs='same'`` / ``'other'``.  The other
+    arguments as for :func:`neighbors_arrays`."""
+    if pairs not in _abi.PCF_PAIRS_CODES:
+        raise ValueError("pairs must be one of 'all', 'same', 'other', not %r" % (pairs,))
+    if pairs != 'all' and group_column is None:
+        raise ValueError("pairs=%r needs a group_column" % (pairs,))
+    offset, _, pos, group = _frame_sorted(f, pos_columns, t_column, group_column)
+    order = np.argsort(f[t_column].values.astype(np.int64), kind='stable')      # the order of _frame_sorted
+    res = neighbors_arrays(pos, offset, k, mpp, max_dist, group, pairs, lag, device=device)
+    dist = np.empty_like(res.dist)
+    neighbor = np.empty_like(res.index)
+    count = np.empty_like(res.count)
+    dist[order] = res.dist
+    neighbor[order] = np.where(res.index >= 0, order[np.maximum(res.index, 0)], -1)
+    count[order] = res.count
+    return dist, neighbor, count
+
+
+def proximity(f, mpp=1., pos_columns=None, t_column='frame', device=0):
+    """The distance of every particle to its nearest neighbour, as trackpy's ``static.proximity`` gives
+    it: a DataFrame indexed by ``particle`` with one column ``'proximity'``, the smallest same-frame
+    nearest-neighbour distance over the particle's rows, in the units of ``pos * mpp``; NaN for a
+    particle that was always alone in its frame.  By the module's rule (clause 8 of the neighbours);
+    parity with trackpy is not pinned: it is not a dependency.
+
+    f: a linked DataFrame with the position columns, ``t_column`` and ``'particle'``."""
+    import pandas as pd
+    _, offset, _, ids, dense, _, pos = _tables.frame_sorted(f, pos_columns, t_column)
+    res = neighbors_arrays(pos, offset, 1, mpp, particle=dense, n_particles=len(ids), device=device)
+    return pd.DataFrame({'proximity': res.particle_min}, index=pd.Index(ids, name='particle'))

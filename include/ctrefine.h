@@ -1435,6 +1435,79 @@ typedef struct ctr_pair_correlation {
 } ctr_pair_correlation;
 int ctr_pair_correlation_device(ctr_handle* h, const ctr_pair_correlation* d, void* hip_stream);
 
+/* ---- nearest neighbours and proximity of a feature table (ABI 8, additions) ----
+ * The structure per feature, where g(r) above is pooled: how far every row is from its nearest
+ * rows, which rows those are, and how many rows lie within a distance.  Within a frame (lag 0) it
+ * is the upper bound of `search_range`, the coordination number and, over the rows of one group,
+ * the bond length; from frame t into frame t + 1 (lag 1) the displacement that `search_range` must
+ * exceed; to the rows of other groups the filter that keeps cluster_tracks and motion to free
+ * clusters.  The reference's users take it from trackpy (static.proximity) and a cKDTree per frame;
+ * this visits all rows of the candidate frame.  The rule is the project's own dense rule;
+ * tests/_neighbors.py restates it in NumPy.  Parity with trackpy is not pinned.
+ * Input: pos [N, ndim], ndim 2 or 3, rows sorted by frame; frame_offset [T + 1]; group [N] or null;
+ * particle [N] or null; k in 1 .. CTR_NBR_MAX_K; lag >= 0; mpp per axis, > 0; limit2 > 0 or +inf.
+ *   1. Scaling.  q = pos * mpp per axis, one rounding; everything below is in these units.
+ *   2. A row exists when every coordinate of q is finite.  There is no box.
+ *   3. Candidates.  The candidates of row i of frame t are the existing rows j of frame t + lag;
+ *      with lag == 0, j == i is excluded; a row of a frame with t + lag >= T has no candidate.
+ *      CTR_PCF_PAIRS_SAME: also group[i] == group[j] >= 0; _OTHER: the candidates that fail that.
+ *   4. Distance.  d2 = the sum over the axes, in axis order, of (q_j - q_i)_a squared, every
+ *      product and sum rounded on its own.  A candidate qualifies when d2 < limit2, strictly;
+ *      limit2 = max_dist * max_dist, which the host computes once, or +inf without a max_dist.
+ *   5. count[i] = the number of qualifying candidates: exact, int64.
+ *   6. Neighbours.  The qualifying candidates sorted by (d2, j) ascending; the first k are the
+ *      neighbours: dist2[i, m] their d2, index[i, m] their global row j, dist[i, m] =
+ *      sqrt(dist2[i, m]).  Coincident rows (d2 == 0) are neighbours like any other.  Where fewer
+ *      than k qualify the remaining entries are NaN, NaN and -1.
+ *   7. Rows with no result: a row that does not exist, a row of a frame without a candidate frame
+ *      and a row outside [frame_offset[0], frame_offset[T]) get NaN, -1 and count 0, and are
+ *      nobody's neighbour.
+ *   8. Per particle (n_particles = P > 0).  particle_min2[p] = the minimum of dist2[i, 0] over the
+ *      rows with particle[i] == p that have a neighbour; particle_min[p] its square root; NaN where
+ *      there is none.  Rows with an id outside [0, P) contribute nowhere.
+ *   9. A refused table.  A frame_offset that is not monotone within [0, N] is refused: status[0] =
+ *      CTR_NBR_BAD_TABLE, every float output NaN, index -1, count 0, and no kernel follows an
+ *      offset before nbr_check has passed it.
+ * Launches, 256 threads each.  nbr_check.  nbr_defaults: the outputs of a refused table and of the
+ * rows outside the frames, and the per-particle keys.  nbr_items, one workgroup: the exclusive scan
+ * of ceil(rows / 256) over the frames.  nbr_pairs: a work item is a frame and a tile of 256 of its
+ * rows, T + N / 256 workgroups of which the surplus leaves; a thread owns one row and every output
+ * element of it, keeps the row and its best (d2, j) in registers -- a sorted list of compile-time
+ * capacity 1, 4 or 16, the smallest that holds k, as an unrolled compare-and-shift chain -- and walks
+ * the candidate frame's rows, staged 256 at a time in LDS with their group ids.  Candidates arrive
+ * in ascending j and enter only on a strict d2 < kept, behind equal entries: the (d2, j) order
+ * without a comparison of indices.  nbr_particles: the per-particle minimum, taken by nbr_pairs with
+ * 64-bit integer atomics on the ordered key of the non-negative double, and its square root.  No
+ * float atomic and no sum of doubles whose order could matter: the same bytes on every call.
+ * Scratch of the handle: 8 (T + 1) bytes and 8 P for the keys.
+ * Descriptors are checked before the handle.  Device pointers; asynchronous on `hip_stream`. */
+#define CTR_NBR_OK 0
+#define CTR_NBR_BAD_TABLE 1
+#define CTR_NBR_MAX_K 16             /* the largest list a thread keeps in registers */
+typedef struct ctr_neighbors {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t pairs;                   /* CTR_PCF_PAIRS_* */
+  int32_t k;                       /* 1 .. CTR_NBR_MAX_K */
+  int32_t lag;                     /* >= 0: the candidates of frame t are in frame t + lag */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P, 0: no per-particle result */
+  double limit2;                   /* > 0 or +inf */
+  double mpp[CTR_MAX_NDIM];        /* per axis, > 0 */
+  const double* pos;               /* [N, ndim] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const int64_t* group;            /* [N], or null with CTR_PCF_PAIRS_ALL */
+  const int64_t* particle;         /* [N], with P > 0 */
+  double* dist;                    /* [N, k] out */
+  double* dist2;                   /* [N, k] out */
+  int64_t* index;                  /* [N, k] out */
+  int64_t* count;                  /* [N] out */
+  double* particle_min;            /* [P] out, with P > 0 */
+  double* particle_min2;           /* [P] out, with P > 0 */
+  int32_t* status;                 /* [1] out */
+} ctr_neighbors;
+int ctr_neighbors_device(ctr_handle* h, const ctr_neighbors* d, void* hip_stream);
+
 /* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
  * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
  * (find_clusters, the stable sort by (frame, cluster), FitFunctions.feature_bounds, the feasibility
@@ -1520,7 +1593,7 @@ int ctr_refine_prepare_plan(const ctr_refine_prepare* r, int64_t* scratch_bytes)
 
 /* A test switch: the most workgroups that a grid-stride kernel of the table stages is launched with
  * by every later stage call of this handle (refine_prepare, drift, msd / emsd, vanhove,
- * pair_correlation, cluster_tracks / track_positions, and the per-level refinement of
+ * pair_correlation, neighbors, cluster_tracks / track_positions, and the per-level refinement of
  * ctr_find_link_refine_device, whose fixed grid is lowered to it).  max_grid within [1, 65536], or
  * 0 for the default of 65536.  Returns the cap that held before; a null handle or a value outside
  * the range returns -1 and changes nothing.  A stage's results never depend on it: every such
