@@ -1,9 +1,10 @@
-"""The front-end of a table stage (``cluster_tracks``, ``drift``, ``msd``, ``vanhove``, ``motion``, ``motion_ci``):
+"""The front-end of a table stage (``cluster_tracks``, ``drift``, ``msd``, ``vanhove``, ``static``, ``motion``, ``motion_ci``):
 the argument checks of a linked table, its placement on the device, the prologue and the tail of a
 call.  A stage module keeps its rule, its descriptor and its outputs; what two of them would spell
 alike lives here, and no stage module is imported.  Argument errors are raised before the engine is
 looked up (:func:`stage`), so they need neither the library nor a GPU.
 """
+import math
 import sys
 
 import numpy as np
@@ -22,6 +23,13 @@ def integer(value, least, what):
     return int(value)
 
 
+def positive(value, what):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(value) or value <= 0:
+        raise ValueError("%s must be a finite positive number, not %r" % (what, value))
+    return float(value)
+
+
 def column(x, n, what, dtype=np.int64):
     """a 1-D table column: a tensor as it is (checked later against the device), else an ndarray"""
     if is_tensor(x):
@@ -36,6 +44,13 @@ def column(x, n, what, dtype=np.int64):
     if x.dtype.kind not in 'iu':
         raise ValueError("%s must hold integers, not %s" % (what, x.dtype))
     return np.ascontiguousarray(x, dtype=dtype)
+
+
+def int64_column(x, n, what):
+    """:func:`column` of an int64 column: a tensor is not converted, so it has to be int64 already"""
+    if is_tensor(x) and str(x.dtype) != 'torch.int64':
+        raise ValueError("a %s tensor is int64, not %s" % (what, x.dtype))
+    return column(x, n, what)
 
 
 def positions(pos, what='pos'):
@@ -123,13 +138,15 @@ def results(as_tensor, status, ok, refused, *tensors):
 _LINK_FIRST = {'particle': ': link it first (find_link, link_df)', 'cluster': ': label it first (find_clusters)'}
 
 
-def frame_sorted(f, pos_columns, t_column, extra=(), with_pos=True):
-    """the rows of the DataFrame ``f`` sorted by frame: (order, frame_offset, first_frame, ids, dense
-    particle, pos_columns, pos) and then the int64 values of every column of ``extra``"""
-    integers = ('particle',) + tuple(extra) + (t_column,)
+def frame_sorted(f, pos_columns, t_column, extra=(), with_pos=True, particle=True):
+    """the rows of the DataFrame ``f`` sorted by frame, the frames dense from the first to the last:
+    (order, frame_offset, first_frame, ids, dense particle, pos_columns, pos) and then the int64 values of
+    every column of ``extra``.  ``particle=False``: a table of features that need not be linked; ids and
+    dense are None, and a missing column is no hint to link or label the table."""
+    integers = (('particle',) if particle else ()) + tuple(extra) + (t_column,)
     for col in integers:
         if col not in f:
-            raise ValueError("the table has no %r column%s" % (col, _LINK_FIRST.get(col, '')))
+            raise ValueError("the table has no %r column%s" % (col, _LINK_FIRST.get(col, '') if particle else ''))
     if with_pos:
         if pos_columns is None:
             pos_columns = ['z', 'y', 'x'] if 'z' in f else ['y', 'x']
@@ -146,7 +163,10 @@ def frame_sorted(f, pos_columns, t_column, extra=(), with_pos=True):
     first = int(frames.min())
     length = int(frames.max()) - first + 1
     offset = np.searchsorted(frames[order] - first, np.arange(length + 1), side='left').astype(np.int64)
-    ids, dense = np.unique(f['particle'].values[order], return_inverse=True)
+    ids = dense = None
+    if particle:
+        ids, dense = np.unique(f['particle'].values[order], return_inverse=True)
+        dense = dense.astype(np.int64).reshape(-1)
     pos = np.ascontiguousarray(f[pos_columns].values[order], dtype=np.float64) if with_pos else None
-    return (order, offset, first, ids, dense.astype(np.int64).reshape(-1), pos_columns, pos) \
+    return (order, offset, first, ids, dense, pos_columns, pos) \
         + tuple(f[col].values[order].astype(np.int64) for col in extra)

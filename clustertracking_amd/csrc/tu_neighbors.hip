@@ -12,21 +12,18 @@
 namespace {
 
 #include "stage_common.h"
+#include "pair_walk.h"
 #include "neighbors_kernels.h"
 
 // a static message, or null
 const char* nbr_scalars(const ctr_neighbors* c) {
-  if (c->ndim != 2 && c->ndim != 3) return "ndim must be 2 or 3";
-  if (c->pairs != CTR_PCF_PAIRS_ALL && c->pairs != CTR_PCF_PAIRS_SAME && c->pairs != CTR_PCF_PAIRS_OTHER)
-    return "pairs must be CTR_PCF_PAIRS_ALL, _SAME or _OTHER";
+  const char* too_many = "too many frames, features or particles for one call";
+  if (const char* why = pair_scalars(c, too_many)) return why;
   if (c->k < 1 || c->k > CTR_NBR_MAX_K) return "k must be within 1 .. CTR_NBR_MAX_K";
   if (c->lag < 0) return "lag must be >= 0";
-  if (c->n_frames < 0 || c->n_features < 0 || c->n_particles < 0) return "negative counts";
-  if (c->n_frames > 0x7ffffffdLL || c->n_features > 0x7fffffffLL || c->n_particles > 0x7ffffffeLL)
-    return "too many frames, features or particles for one call";
+  if (c->n_particles < 0) return "negative counts";
+  if (c->n_particles > 0x7ffffffeLL) return too_many;
   if (!(c->limit2 > 0.)) return "limit2 must be positive or +inf";
-  for (int d = 0; d < c->ndim; ++d)
-    if (!std::isfinite(c->mpp[d]) || !(c->mpp[d] > 0.)) return "mpp must be finite and positive";
   return nullptr;
 }
 
@@ -43,38 +40,29 @@ int ctr_neighbors_launch(const ctr_neighbors* c, StageRun* stage, const char** m
   if (const char* why = nbr_scalars(c)) { *msg = why; return CTR_ERR_INVALID; }
   if (stage->mode == STAGE_CHECK_SCALARS) return CTR_OK;
   if (!c->status || !c->frame_offset) { *msg = "null status or frame_offset"; return CTR_ERR_INVALID; }
-  if (c->n_features > 0 && !c->pos) { *msg = "features without pos"; return CTR_ERR_INVALID; }
-  if (c->n_features > 0 && c->pairs != CTR_PCF_PAIRS_ALL && !c->group) { *msg = "pairs by group without group"; return CTR_ERR_INVALID; }
+  if (const char* why = pair_columns(c)) { *msg = why; return CTR_ERR_INVALID; }
   if (c->n_features > 0 && (!c->dist || !c->dist2 || !c->index || !c->count)) { *msg = "null output"; return CTR_ERR_INVALID; }
   if (c->n_particles > 0 && (!c->particle_min || !c->particle_min2)) { *msg = "a particle column without particle_min"; return CTR_ERR_INVALID; }
   if (c->n_particles > 0 && c->n_features > 0 && !c->particle) { *msg = "n_particles without particle"; return CTR_ERR_INVALID; }
-  // a frame of n rows has ceil(n / 256) work items: at most T + N / 256 in all, whatever the offsets
-  const long long max_items = c->n_frames + c->n_features / NBR_TILE;
-  size_t total = 0;
-  const size_t o_start = carve(total, sizeof(long long) * (size_t)(c->n_frames + 1));
+  size_t total = 0, o_start;
+  const long long max_items = pair_max_items(c, total, o_start);
   const size_t o_pkey = carve(total, sizeof(unsigned long long) * (size_t)c->n_particles);
   stage->scratch_bytes = total;
   if (stage->mode != STAGE_LAUNCH) return CTR_OK;
 
   const hipStream_t s = stage->stream;
   NbrArgs a = {};
-  a.ndim = c->ndim; a.pairs = c->pairs; a.k = c->k;
-  a.lag = c->lag; a.T = c->n_frames; a.N = c->n_features; a.P = c->n_particles;
+  a.tab = pair_table(c, stage->scratch, o_start);
+  a.k = c->k; a.lag = c->lag; a.P = c->n_particles;
   a.limit2 = c->limit2;
-  for (int d = 0; d < c->ndim; ++d) a.mpp[d] = c->mpp[d];
-  a.pos = c->pos;
-  a.frame_offset = (const long long*)c->frame_offset;
-  a.group = (const long long*)c->group;
   a.particle = (const long long*)c->particle;
-  a.item_start = (long long*)((char*)stage->scratch + o_start);
   a.pkey = (unsigned long long*)((char*)stage->scratch + o_pkey);
   a.dist = c->dist; a.dist2 = c->dist2; a.index = (long long*)c->index; a.count = (long long*)c->count;
   a.particle_min = c->particle_min; a.particle_min2 = c->particle_min2;
-  a.status = c->status;
-  STAGE_TRY(hipMemsetAsync(a.status, 0, sizeof(int32_t), s));
+  STAGE_TRY(hipMemsetAsync(c->status, 0, sizeof(int32_t), s));
   const dim3 block(NBR_THREADS);
-  const long long defaults = a.N > a.P ? a.N : a.P;
-  hipLaunchKernelGGL(nbr_check_kernel, dim3(stride_grid(a.T + 1, NBR_THREADS, stage->max_grid)), block, 0, s, a);
+  const long long defaults = c->n_features > a.P ? c->n_features : a.P;
+  hipLaunchKernelGGL(nbr_check_kernel, dim3(stride_grid(c->n_frames + 1, NBR_THREADS, stage->max_grid)), block, 0, s, a);
   if (defaults > 0) hipLaunchKernelGGL(nbr_defaults_kernel, dim3(stride_grid(defaults, NBR_THREADS, stage->max_grid)), block, 0, s, a);
   hipLaunchKernelGGL(nbr_items_kernel, dim3(1), block, 0, s, a);
   if (max_items > 0) {

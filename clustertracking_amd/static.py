@@ -99,16 +99,9 @@ _REFUSED = "pair_correlation_arrays: frame_offset must rise within [0, N]"
 _NBR_REFUSED = "neighbors_arrays: frame_offset must rise within [0, N]"
 
 
-def _positive(value, what):
-    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(value) or value <= 0:
-        raise ValueError("%s must be a finite positive number, not %r" % (what, value))
-    return float(value)
-
-
 def bins(cutoff, dr, ndim):
     """clause 1: ``(r_edges [B + 1], edge2 [B + 1], shell [B])`` as float64 ndarrays"""
-    cutoff, dr = _positive(cutoff, 'cutoff'), _positive(dr, 'dr')
+    cutoff, dr = _tables.positive(cutoff, 'cutoff'), _tables.positive(dr, 'dr')
     if cutoff / dr > _abi.PCF_MAX_BINS:
         raise ValueError("cutoff / dr gives more than %d bins" % _abi.PCF_MAX_BINS)
     n_bins = int(math.ceil(cutoff / dr))
@@ -143,15 +136,20 @@ def _boundary(boundary, ndim):
     return boundary
 
 
+def _pairs(pairs, group, word='group'):
+    """``word``: what the caller calls ``group``"""
+    if pairs not in _abi.PCF_PAIRS_CODES:
+        raise ValueError("pairs must be one of 'all', 'same', 'other', not %r" % (pairs,))
+    if pairs != 'all' and group is None:
+        raise ValueError("pairs=%r needs a %s" % (pairs, word))
+
+
 def _modes(edge, pairs, group, ndim):
     if edge not in _abi.PCF_EDGE_CODES:
         raise ValueError("edge must be one of 'none', 'interior', 'arc', not %r" % (edge,))
     if edge == 'arc' and ndim != 2:
         raise ValueError("edge='arc' is the correction of a rectangle: ndim 2 only; use 'interior' or 'none'")
-    if pairs not in _abi.PCF_PAIRS_CODES:
-        raise ValueError("pairs must be one of 'all', 'same', 'other', not %r" % (pairs,))
-    if pairs != 'all' and group is None:
-        raise ValueError("pairs=%r needs a group" % (pairs,))
+    _pairs(pairs, group)
 
 
 def pair_correlation_arrays(pos, frame_offset, cutoff, dr=0.5, mpp=1., boundary=None, edge='arc', group=None,
@@ -182,9 +180,7 @@ def pair_correlation_arrays(pos, frame_offset, cutoff, dr=0.5, mpp=1., boundary=
     boundary = _boundary(boundary, ndim)
     frame_offset, n_frames = _tables.offsets(frame_offset)
     if group is not None:
-        if _tables.is_tensor(group) and str(group.dtype) != 'torch.int64':
-            raise ValueError("a group tensor is int64, not %s" % (group.dtype,))
-        group = _tables.column(group, n, 'group')
+        group = _tables.int64_column(group, n, 'group')
     if n_frames > 2 ** 31 - 3 or n > 2 ** 31 - 1:
         raise ValueError("too many frames or features for one call")
     as_tensor = _tables.is_tensor(pos)
@@ -227,33 +223,6 @@ def pair_correlation_arrays(pos, frame_offset, cutoff, dr=0.5, mpp=1., boundary=
         return PairCorrelation(*out, status if as_tensor else _abi.PCF_OK)
 
 
-def _frame_sorted(f, pos_columns, t_column, group_column):
-    """the rows of the DataFrame ``f`` sorted by frame, the frames dense from the first to the last:
-    (frame_offset, first frame, pos, group or None).  No ``particle`` column is needed."""
-    if pos_columns is None:
-        pos_columns = ['z', 'y', 'x'] if 'z' in f else ['y', 'x']
-    pos_columns = list(pos_columns)
-    if [c for c in pos_columns if c not in f] or len(pos_columns) not in (2, 3):
-        raise ValueError("pos_columns must name 2 or 3 columns of the table, not %r" % (pos_columns,))
-    integers = (t_column,) if group_column is None else (t_column, group_column)
-    for col in integers:
-        if col not in f:
-            raise ValueError("the table has no %r column" % (col,))
-    if len(f) == 0:
-        raise ValueError("an empty table has no frames")
-    for col in integers:
-        if np.asarray(f[col].values).dtype.kind not in 'iu':
-            raise ValueError("the %r column must hold integers, not %s" % (col, f[col].values.dtype))
-    frames = f[t_column].values.astype(np.int64)
-    order = np.argsort(frames, kind='stable')
-    first = int(frames.min())
-    length = int(frames.max()) - first + 1
-    offset = np.searchsorted(frames[order] - first, np.arange(length + 1), side='left').astype(np.int64)
-    pos = np.ascontiguousarray(f[pos_columns].values[order], dtype=np.float64)
-    group = None if group_column is None else f[group_column].values[order].astype(np.int64)
-    return offset, first, pos, group
-
-
 def pair_correlation(f, cutoff, dr=0.5, mpp=1., boundary=None, edge='arc', group_column=None, pairs='all',
                      pos_columns=None, t_column='frame', per_frame=False, device=0):
     """The pair correlation function of a table of features: ``(r_edges, g)`` as trackpy's
@@ -267,12 +236,10 @@ def pair_correlation(f, cutoff, dr=0.5, mpp=1., boundary=None, edge='arc', group
     such as ``'cluster'``, ``'particle'`` or ``'cluster_track'`` for ``pairs='same'`` / ``'other'``.  The
     other arguments as for :func:`pair_correlation_arrays`."""
     import pandas as pd
-    if pairs not in _abi.PCF_PAIRS_CODES:
-        raise ValueError("pairs must be one of 'all', 'same', 'other', not %r" % (pairs,))
-    if pairs != 'all' and group_column is None:
-        raise ValueError("pairs=%r needs a group_column" % (pairs,))
-    offset, first, pos, group = _frame_sorted(f, pos_columns, t_column, group_column)
-    res = pair_correlation_arrays(pos, offset, cutoff, dr, mpp, boundary, edge, group, pairs, device)
+    _pairs(pairs, group_column, 'group_column')
+    _, offset, first, _, _, _, pos, *group = _tables.frame_sorted(
+        f, pos_columns, t_column, () if group_column is None else (group_column,), particle=False)
+    res = pair_correlation_arrays(pos, offset, cutoff, dr, mpp, boundary, edge, group[0] if group else None, pairs, device)
     if not per_frame:
         return res.r_edges, res.g
     frames = pd.RangeIndex(first, first + len(offset) - 1, name=t_column)
@@ -308,25 +275,18 @@ def neighbors_arrays(pos, frame_offset, k=1, mpp=1., max_dist=None, group=None, 
         raise ValueError("lag must be an integer >= 0, not %r" % (lag,))
     limit2 = math.inf
     if max_dist is not None:
-        limit2 = _positive(max_dist, 'max_dist') ** 2
+        limit2 = _tables.positive(max_dist, 'max_dist') ** 2
         if not limit2 > 0:
             raise ValueError("max_dist squared must be positive, not %r" % (limit2,))
     scale = _scales(mpp, ndim)
-    if pairs not in _abi.PCF_PAIRS_CODES:
-        raise ValueError("pairs must be one of 'all', 'same', 'other', not %r" % (pairs,))
-    if pairs != 'all' and group is None:
-        raise ValueError("pairs=%r needs a group" % (pairs,))
+    _pairs(pairs, group)
     frame_offset, n_frames = _tables.offsets(frame_offset)
     if group is not None:
-        if _tables.is_tensor(group) and str(group.dtype) != 'torch.int64':
-            raise ValueError("a group tensor is int64, not %s" % (group.dtype,))
-        group = _tables.column(group, n, 'group')
+        group = _tables.int64_column(group, n, 'group')
     if particle is None and n_particles is not None:
         raise ValueError("n_particles needs a particle column")
     if particle is not None:
-        if _tables.is_tensor(particle) and str(particle.dtype) != 'torch.int64':
-            raise ValueError("a particle tensor is int64, not %s" % (particle.dtype,))
-        particle, n_particles = _tables.particles(particle, n, n_particles)
+        particle, n_particles = _tables.particles(_tables.int64_column(particle, n, 'particle'), n, n_particles)
     if n_frames > 2 ** 31 - 3 or n > 2 ** 31 - 1:
         raise ValueError("too many frames or features for one call")
     as_tensor = _tables.is_tensor(pos)
@@ -378,13 +338,10 @@ def neighbors(f, k=1, mpp=1., max_dist=None, group_column=None, pairs='all', lag
     the first to the last, so ``lag`` counts frame numbers.  group_column: an integer column such as
     ``'cluster'``, ``'particle'`` or ``'cluster_track'`` for ``pairs='same'`` / ``'other'``.  The other
     arguments as for :func:`neighbors_arrays`."""
-    if pairs not in _abi.PCF_PAIRS_CODES:
-        raise ValueError("pairs must be one of 'all', 'same', 'other', not %r" % (pairs,))
-    if pairs != 'all' and group_column is None:
-        raise ValueError("pairs=%r needs a group_column" % (pairs,))
-    offset, _, pos, group = _frame_sorted(f, pos_columns, t_column, group_column)
-    order = np.argsort(f[t_column].values.astype(np.int64), kind='stable')      # the order of _frame_sorted
-    res = neighbors_arrays(pos, offset, k, mpp, max_dist, group, pairs, lag, device=device)
+    _pairs(pairs, group_column, 'group_column')
+    order, offset, _, _, _, _, pos, *group = _tables.frame_sorted(
+        f, pos_columns, t_column, () if group_column is None else (group_column,), particle=False)
+    res = neighbors_arrays(pos, offset, k, mpp, max_dist, group[0] if group else None, pairs, lag, device=device)
     dist = np.empty_like(res.dist)
     neighbor = np.empty_like(res.index)
     count = np.empty_like(res.count)

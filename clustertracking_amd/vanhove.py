@@ -76,16 +76,9 @@ def _lags(lagtime):
     return lags
 
 
-def _positive(value, what):
-    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(value) or value <= 0:
-        raise ValueError("%s must be a finite positive number, not %r" % (what, value))
-    return float(value)
-
-
 def bins(bin_width, max_disp):
     """clauses 5 and 6: ``(H, edges [2 H + 1], r_edges [H + 1], edge2 [H + 1])`` as float64 ndarrays"""
-    bin_width, max_disp = _positive(bin_width, 'bin_width'), _positive(max_disp, 'max_disp')
+    bin_width, max_disp = _tables.positive(bin_width, 'bin_width'), _tables.positive(max_disp, 'max_disp')
     if max_disp / bin_width > _abi.VANHOVE_MAX_HALF_BINS:
         raise ValueError("max_disp / bin_width gives more than %d bins on a side" % _abi.VANHOVE_MAX_HALF_BINS)
     half = max(int(math.ceil(max_disp / bin_width)), 1)      # 1 where the quotient underflows to 0

@@ -92,3 +92,24 @@ def tile_edges(ndim=2, seed=3):
     """frames of 0, 1, 2, 255, 256, 257 and 513 rows: the tile's edge on the owner side and on the
     candidate side, an empty frame, a one-row frame, 9 work items"""
     return uniform_frames(seed, (0, 1, 2, TILE - 1, TILE, TILE + 1, 2 * TILE + 1), (60., 45., 30.)[:ndim], ndim)
+
+
+SHARED_CUTOFF, SHARED_DR = 8., 0.5      # 16 bins: r_edges[16] = 8 exactly, the box is a few cutoffs wide
+
+
+def shared_rule(ndim):
+    """(pos, frame_offset, group) for the rule that g(r) and the neighbours share -- the same d2, the same
+    existence, the same group filter: the table of the tile edges with a row that does not exist inside
+    a tile and groups -3 .. 11.  With ``edge='none'`` and the default box every finite row is a
+    reference row, so ``count[t, :].sum()`` of g(r) at (SHARED_CUTOFF, SHARED_DR) is the sum over the rows
+    of frame t of the neighbours' ``count`` at ``max_dist = SHARED_CUTOFF``, ``lag = 0``."""
+    pos, off = tile_edges(ndim)
+    pos = pos.copy()
+    pos[off[5] + 100] = np.nan
+    group = np.random.RandomState(6).randint(-3, 12, len(pos)).astype(np.int64)
+    return pos, off, group
+
+
+def counts_per_frame(count, frame_offset):
+    """the neighbours' count[i] summed over the rows of every frame"""
+    return np.array([count[a:b].sum() for a, b in zip(frame_offset[:-1], frame_offset[1:])], dtype=np.int64)

@@ -166,6 +166,32 @@ def test_groups_same_and_other(engine):
     assert (ahead['all'].count == ahead['same'].count + ahead['other'].count).all()
 
 
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_count_matches_pair_correlation(engine, ndim):
+    """g(r) and the neighbours walk the same pairs (csrc/pair_walk.h): the pairs that g(r) bins in a frame
+    are the candidates that the neighbours count in it, exactly, for every `pairs`, at the default grid cap
+    and under a cap of two workgroups.  tests/test_neighbors_rule.py holds the two restatements to the same."""
+    pos, off, group = yard.shared_rule(ndim)
+    mpp = (0.5, 1., 2.)[:ndim]
+    totals = {}
+    for pairs in ('all', 'same', 'other'):
+        def both():
+            g = ct.pair_correlation_arrays(pos, off, yard.SHARED_CUTOFF, yard.SHARED_DR, mpp=mpp, edge='none', group=group, pairs=pairs)
+            assert g.status == _abi.PCF_OK and g.count.shape == (len(off) - 1, 16) and g.r_edges[16] == yard.SHARED_CUTOFF
+            n = ct.neighbors_arrays(pos, off, k=1, mpp=mpp, max_dist=float(g.r_edges[16]), group=group, pairs=pairs, lag=0)
+            assert n.status == _abi.NBR_OK
+            return g.count.sum(1), yard.counts_per_frame(n.count, off)
+        binned, counted = both()
+        print(ndim, pairs, 'pairs per frame', binned.tolist())
+        assert binned.dtype == counted.dtype == np.int64 and (binned == counted).all(), (ndim, pairs, binned, counted)
+        with engine.stage_max_grid(2):
+            low_binned, low_counted = both()
+        assert (low_binned == binned).all() and (low_counted == binned).all(), (ndim, pairs, low_binned, low_counted)
+        totals[pairs] = binned
+    assert (totals['all'] == totals['same'] + totals['other']).all()
+    assert totals['all'][:2].tolist() == [0, 0] and (totals['same'][3:] > 0).all() and (totals['other'][3:] > 0).all()
+
+
 def test_mpp_per_axis(engine):
     pos, off = TABLES[3]
     got, ref = check('mpp 3D', pos, off, k=4, mpp=(2., 1., 0.5), max_dist=11.)

@@ -6,16 +6,9 @@ unconstrained, no lowpass) run at 3 wavefronts per SIMD (block_kernel.h: block_o
 cells of that table at one.  They must do so without scratch memory: a later edit that brings
 spills back, or that needs more registers than their wavefronts per SIMD leave, fails here instead
 of silently costing throughput."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM_BIN = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'llvm', 'bin')
-TARGET = 'hipv4-amdgcn-amd-amdhsa--gfx950'
+import _resources
 
 # refine_block_kernel<ND, ISO, NT, W, CONS, LP, FIT> -> mangled name (anonymous namespace)
 def _mangled(nd, iso, nt, w, cons=False, lp=False, fit=0):
@@ -35,43 +28,12 @@ VGPRS_PER_SIMD = 512                 # per lane, CDNA3/4: VGPRs and AGPRs from o
 GRANULE = 8
 
 
-def _tool(name):
-    p = os.path.join(LLVM_BIN, name)
-    return p if os.path.exists(p) else shutil.which(name)
-
-
 @pytest.fixture(scope='module')
 def kernels(tmp_path_factory):
-    from clustertracking_amd import _lib
-    lib = _lib.LIB_PATH
-    if not os.path.exists(lib):
-        pytest.skip('libctrefine.so is not built')
-    objcopy, bundler, readelf = _tool('llvm-objcopy'), _tool('clang-offload-bundler'), _tool('llvm-readelf')
-    if not (objcopy and bundler and readelf):
-        pytest.skip('llvm-objcopy / clang-offload-bundler / llvm-readelf not found')
-    d = tmp_path_factory.mktemp('co')
-    fatbin = str(d / 'fatbin')
-    subprocess.check_call([objcopy, '--dump-section', '.hip_fatbin=' + fatbin, lib, str(d / 'lib.so')])
-    # one offload bundle per translation unit, back to back in the section
-    data = open(fatbin, 'rb').read()
-    magic = b'__CLANG_OFFLOAD_BUNDLE__'
-    starts = [m.start() for m in re.finditer(re.escape(magic), data)]
-    if not starts:
-        pytest.skip('the fat binary holds no uncompressed offload bundles')
-    out = {}
-    for j, (s, e) in enumerate(zip(starts, starts[1:] + [len(data)])):
-        bundle, co = str(d / ('bundle%d' % j)), str(d / ('gfx950_%d.co' % j))
-        with open(bundle, 'wb') as f:
-            f.write(data[s:e])
-        subprocess.check_call([bundler, '--type=o', '--unbundle', '--targets=' + TARGET,
-                               '--input=' + bundle, '--output=' + co])
-        notes = subprocess.check_output([readelf, '--notes', co], text=True)
-        # the amdhsa.kernels list of the metadata note: one "- .agpr_count: ..." block per kernel
-        for block in re.split(r'\n\s+- \.agpr_count:', notes)[1:]:
-            block = '.agpr_count:' + block
-            fields = dict(re.findall(r'^\s*(\.[a-z_]+):\s+(\S+)\s*$', block, re.M))
-            if '.name' in fields:
-                out[fields['.name']] = fields
+    try:
+        out = _resources.metadata('', tmp_path_factory.mktemp('co'))
+    except _resources.Unavailable as e:
+        pytest.skip(str(e))
     assert out, 'no kernel metadata found in the gfx950 code object'
     return out
 

@@ -92,6 +92,25 @@ def test_the_yardstick_of_a_refused_table():
     assert np.isnan(r.particle_min).all() and r.particle_min.shape == (4,)
 
 
+@pytest.mark.parametrize('ndim', [2, 3])
+def test_the_yardsticks_agree_on_the_shared_rule(ndim):
+    """the table and the identity of test_gpu_neighbors.py::test_count_matches_pair_correlation, on the two
+    restatements: the pairs that g(r) bins in a frame are the candidates that the neighbours count in it"""
+    import _pair_correlation as pcf
+    pos, off, group = yard.shared_rule(ndim)
+    assert np.diff(off).tolist() == [0, 1, 2, 255, 256, 257, 513] and np.isnan(pos).any(1).sum() == 1 and (group < 0).any()
+    mpp = (0.5, 1., 2.)[:ndim]
+    totals = {}
+    for pairs in ('all', 'same', 'other'):
+        g = pcf.pair_correlation(pos, off, yard.SHARED_CUTOFF, yard.SHARED_DR, mpp=mpp, edge='none', group=group, pairs=pairs)
+        assert g.count.shape == (7, 16) and g.r_edges[16] == yard.SHARED_CUTOFF
+        n = yard.neighbors(pos, off, k=1, mpp=mpp, max_dist=g.r_edges[16], group=group, pairs=pairs)
+        totals[pairs] = g.count.sum(1)
+        assert (totals[pairs] == yard.counts_per_frame(n.count, off)).all(), (ndim, pairs)
+    assert (totals['all'] == totals['same'] + totals['other']).all()
+    assert totals['all'][:2].tolist() == [0, 0] and (totals['same'][3:] > 0).all() and (totals['other'][3:] > 0).all()
+
+
 # ---- argument errors: raised before the engine is looked up ----
 POS2, POS3, OFF = np.zeros((4, 2)), np.zeros((4, 3)), np.array([0, 2, 4])
 GROUP = np.zeros(4, dtype=np.int64)
