@@ -27,6 +27,7 @@ from .msd import msd_arrays, emsd_arrays, imsd, emsd
 from .vanhove import vanhove_arrays, vanhove     # the function shadows the submodule: importlib.import_module reaches it
 from . import static
 from .static import pair_correlation_arrays, pair_correlation, neighbors_arrays, neighbors, proximity
+from .twopoint import twopoint_arrays, twopoint   # the function shadows the submodule, as vanhove does
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -40,7 +41,7 @@ __all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', '
            'drift', 'compute_drift', 'subtract_drift', 'filter_stubs', 'compute_drift_arrays', 'subtract_drift_arrays',
            'filter_stubs_arrays', 'msd', 'msd_arrays', 'emsd_arrays', 'imsd', 'emsd',
            'vanhove_arrays', 'vanhove', 'static', 'pair_correlation_arrays', 'pair_correlation',
-           'neighbors_arrays', 'neighbors', 'proximity']
+           'neighbors_arrays', 'neighbors', 'proximity', 'twopoint_arrays', 'twopoint']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

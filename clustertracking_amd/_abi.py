@@ -376,6 +376,26 @@ class Neighbors(C.Structure):
     ]
 
 
+TP_OK, TP_BAD_TABLE = 0, 1                                     # status[0] of ctr_twopoint_device
+TP_MAX_BINS, TP_MAX_LAGS = 512, 16     # bins (edge2, counts and sums of a workgroup are in LDS); lags of a call
+TP_MAX2_RANGE = (2. ** -500, 2. ** 500)                        # ctr_twopoint.max2: its square is finite, the unit 2^(e - 40) normal
+TP_MAX_REACH2_MAX2 = 2. ** 1000                                # (n_bins dr)^2 max2 at most: no product of a pair overflows
+
+
+class TwoPoint(C.Structure):
+    """``ctr_twopoint`` (include/ctrefine.h): two-point displacement correlations of linked particles;
+    ``pairs`` takes the ``PCF_PAIRS_*`` codes."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('pairs', C.c_int32), ('n_lags', C.c_int32), ('reserved0', C.c_int32),
+        ('n_bins', C.c_int64), ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64),
+        ('dr', C.c_double), ('max2', C.c_double), ('mpp', C.c_double * MAX_NDIM), ('lag', C.c_int64 * TP_MAX_LAGS),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('particle', C.c_void_p), ('group', C.c_void_p),
+        ('edge2', C.c_void_p),
+        ('n', C.c_void_p), ('dot', C.c_void_p), ('longitudinal', C.c_void_p), ('transverse', C.c_void_p), ('cos', C.c_void_p),
+        ('sums', C.c_void_p), ('n_moved', C.c_void_p), ('beyond', C.c_void_p), ('status', C.c_void_p),
+    ]
+
+
 PREPARE_BATCH, PREPARE_SCATTER = 0, 1                         # ctr_refine_prepare.mode
 PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
 

@@ -64,6 +64,7 @@ SIGNATURES = {
     'ctr_vanhove_device': _stage(_abi.Vanhove),
     'ctr_pair_correlation_device': _stage(_abi.PairCorrelation),
     'ctr_neighbors_device': _stage(_abi.Neighbors),
+    'ctr_twopoint_device': _stage(_abi.TwoPoint),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
     'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
@@ -403,6 +404,7 @@ for _name, _symbol, _too_large in (
         ('vanhove_device', 'ctr_vanhove_device', False),
         ('pair_correlation_device', 'ctr_pair_correlation_device', False),
         ('neighbors_device', 'ctr_neighbors_device', False),
+        ('twopoint_device', 'ctr_twopoint_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 

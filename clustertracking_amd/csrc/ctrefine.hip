@@ -124,6 +124,7 @@ struct ctr_handle {
   Scratch msd;     // ctr_msd_device, ctr_emsd_device, ctr_vanhove_device: the sorted rows, row ranges, partials of the chunks
   Scratch pcf;     // ctr_pair_correlation_device: the work items of the frames, their partial weights
   Scratch nbr;     // ctr_neighbors_device: the work items of the frames, the keys of the particles
+  Scratch twopt;   // ctr_twopoint_device: the work items of the frames, the partner's row of every row and lag
   unsigned stage_max_grid = STAGE_MAX_GRID;   // run_stage: StageRun::max_grid (ctr_set_stage_max_grid)
 };
 
@@ -483,7 +484,7 @@ void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1114,6 +1115,10 @@ int ctr_pair_correlation_device(ctr_handle* h, const ctr_pair_correlation* d, vo
 
 int ctr_neighbors_device(ctr_handle* h, const ctr_neighbors* d, void* hip_stream) {
   return run_stage("ctr_neighbors_device", h, &ctr_handle::nbr, d, hip_stream, ctr_neighbors_launch);
+}
+
+int ctr_twopoint_device(ctr_handle* h, const ctr_twopoint* d, void* hip_stream) {
+  return run_stage("ctr_twopoint_device", h, &ctr_handle::twopt, d, hip_stream, ctr_twopoint_launch);
 }
 
 int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream) {

@@ -1,7 +1,8 @@
 // drift_kernels.h -- drift of a linked video: the step of every frame, its smoothing and running
 // sum, the subtraction, and the stub filter (ctr_drift_device, ctr_drift_subtract_device,
 // ctr_filter_stubs_device; include/ctrefine.h has the rule).  Included by
-// tu_drift.hip inside its anonymous namespace, after stage_common.h.  The kernel boundary is the
+// tu_drift.hip inside its anonymous namespace, after stage_common.h and particle_match.h (the LDS
+// table particle -> row, which the two-point stage shares).  The kernel boundary is the
 // only synchronisation between workgroups; every loop is bounded by the launch's arguments or, for
 // the rows of a frame, by offsets that drift_check_kernel has checked against them; integer atomics
 // only: every float sum is taken in an order that the input alone decides.
@@ -9,10 +10,8 @@
 #define CTREFINE_DRIFT_KERNELS_H
 
 constexpr int DR_THREADS = 256;         // a workgroup of every kernel here: 4 wavefronts
-constexpr int DR_TILE = 2048;           // rows of frame t - 1 in one LDS table
-constexpr int DR_SLOTS = 4096;          // its slots, 8 bytes each: never more than half full
 constexpr int DR_ROWS = 8;              // rows of frame t per thread and chunk (a chunk: DR_THREADS * DR_ROWS rows)
-constexpr unsigned long long DR_EMPTY = ~0ull;
+// DR_TILE rows of frame t - 1 in one LDS table of DR_SLOTS slots: particle_match.h, with drift_insert and drift_lookup
 
 struct DriftArgs {
   int ndim, smoothing;
@@ -42,30 +41,6 @@ __global__ void __launch_bounds__(DR_THREADS) drift_check_kernel(const DriftArgs
     if (i < n_par) bad |= a.particle[i] >= a.P;
   }
   if (bad) st_agent(a.status, CTR_DRIFT_BAD_TABLE);
-}
-
-__device__ __forceinline__ unsigned drift_slot(int p) { return ((unsigned)p * 2654435761u) >> 20; }   // 12 bits: DR_SLOTS
-
-// (particle << 32 | row) into the table; a particle that is there already keeps the lower row
-__device__ __forceinline__ void drift_insert(unsigned long long* tab, int p, unsigned row) {
-  const unsigned long long mine = ((unsigned long long)(unsigned)p << 32) | row;
-  unsigned s = drift_slot(p);
-  for (int probe = 0; probe < DR_SLOTS; ++probe, s = (s + 1) & (DR_SLOTS - 1)) {
-    const unsigned long long old = atomicCAS(tab + s, DR_EMPTY, mine);
-    if (old == DR_EMPTY) return;
-    if ((unsigned)(old >> 32) == (unsigned)p) { atomicMin(tab + s, mine); return; }
-  }
-}
-
-// the row of particle p in the table, or -1
-__device__ __forceinline__ int drift_lookup(const unsigned long long* tab, int p) {
-  unsigned s = drift_slot(p);
-  for (int probe = 0; probe < DR_SLOTS; ++probe, s = (s + 1) & (DR_SLOTS - 1)) {
-    const unsigned long long v = tab[s];
-    if (v == DR_EMPTY) return -1;
-    if ((unsigned)(v >> 32) == (unsigned)p) return (int)(unsigned)v;
-  }
-  return -1;
 }
 
 // One workgroup per frame t: n_pairs[t] and dx[t], the mean of pos[i] - pos[j] over its pairs.

@@ -123,7 +123,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
 // tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd, tu_pair_corr,
-// tu_neighbors)
+// tu_neighbors, tu_twopoint)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -213,5 +213,8 @@ int ctr_pair_correlation_launch(const ctr_pair_correlation* d, StageRun* stage, 
 // nearest neighbours and proximity of a feature table (neighbors_kernels.h; scratch: the first work item
 // of every frame and a key per particle)
 int ctr_neighbors_launch(const ctr_neighbors* d, StageRun* stage, const char** msg);
+// two-point displacement correlations of linked particles (twopoint_kernels.h; scratch: the first work
+// item of every frame and the partner's row of every row and lag)
+int ctr_twopoint_launch(const ctr_twopoint* d, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

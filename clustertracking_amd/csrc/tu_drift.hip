@@ -8,6 +8,7 @@
 namespace {
 
 #include "stage_common.h"
+#include "particle_match.h"
 #include "drift_kernels.h"
 
 }  // namespace

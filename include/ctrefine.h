@@ -1508,6 +1508,103 @@ typedef struct ctr_neighbors {
 } ctr_neighbors;
 int ctr_neighbors_device(ctr_handle* h, const ctr_neighbors* d, void* hip_stream);
 
+/* ---- two-point displacement correlations of linked particles (ABI 8, additions) ----
+ * Whether particles move together, as a function of their separation: the mean over the pairs of a
+ * frame, binned by distance, of the product of their displacements over a lag -- its trace (dot), its
+ * part along the line between the two (longitudinal, D_rr of two-point microrheology), its part across
+ * that line (transverse) and the cosine of the angle between the two displacements.  Where the
+ * reference's users take trackpy's motion.velocity_corr / direction_corr; g(r) and the neighbours above
+ * say how close rows come, this says whether their motion is coupled.  A residual drift shows as a
+ * constant |v|^2 lag^2 at every r, wrong links in the first bins.  The rule is the project's own
+ * dense rule; tests/_twopoint.py restates it in NumPy.  Parity with trackpy is not pinned; it differs
+ * in: bins and a pool over all frames, ordered pairs, any lag, and max_disp.
+ * Input: pos [N, ndim], ndim 2 or 3, rows sorted by frame; frame_offset [T + 1]; particle [N], ids
+ * below P, negative = unlinked; group [N] or null; K lags; B bins of width dr; mpp per axis, > 0;
+ * edge2 [B + 1] and max2, which the host computes once.
+ *   1. Bins.  Clause 1 of g(r): B = ceil(cutoff / dr), at most CTR_TP_MAX_BINS; r_edges[b] = b * dr;
+ *      edge2 = r_edges * r_edges, computed on the host.
+ *   2. Scaling and existence.  q = pos * mpp per axis, one rounding.  A row exists when every
+ *      coordinate of q is finite.  There is no box.
+ *   3. Lags.  An ascending list of distinct integers >= 1, at most CTR_TP_MAX_LAGS of them.
+ *   4. Partner.  The partner of row i of frame t at lag k is the lowest row j of frame t + k with
+ *      particle[j] == particle[i] >= 0; there is none when t + k >= T or particle[i] < 0: drift's rule
+ *      for a repeated particle.
+ *   5. Displacement.  u_a = q_partner,a - q_i,a; u2 = the sum over the axes, in axis order, of u_a *
+ *      u_a, every product and sum rounded on its own.  Row i has moved at lag k when it exists, its
+ *      partner exists and u2 <= max2; max2 = max_disp * max_disp, computed once on the host.
+ *      n_moved[k] counts the moved rows, beyond[k] the rows with a finite u and u2 > max2.  Rows
+ *      outside [frame_offset[0], frame_offset[T]) take no part.
+ *   6. Pairs.  A pair is an ordered pair (i, j), j != i, of rows of one frame that have both moved at
+ *      lag k, with 0 < d2 < edge2[B]; d2 and the bin as in clause 7 of g(r): edge2[b] <= d2 <
+ *      edge2[b + 1].  Coincident rows are not pairs, because L below divides by d2.
+ *      CTR_PCF_PAIRS_SAME / _OTHER with group as in clause 6 of g(r).
+ *   7. Per pair, every product and sum rounded on its own: R_a = q_j,a - q_i,a, the differences that
+ *      d2 squares; dot = the sum over the axes, in axis order, of u_i,a * u_j,a; a_i = that sum of
+ *      u_i,a * R_a and a_j = of u_j,a * R_a; L = (a_i * a_j) / d2; c = dot / sqrt(u2_i * u2_j) where
+ *      that product is > 0, else 0.
+ *   8. Fixed point.  e = the smallest integer with 2^e >= max2; unit = 2^(e - 40) and unit_cos =
+ *      2^-40.  A value x enters as the integer rint(x / unit), ties to even; the scaling is exact.
+ *   9. Sums.  n[k, b] counts the pairs, exact int64.  sums[k, b, s], s = dot, L, c, are the exact
+ *      integer sums, each a 128-bit two's-complement number in two int64 words (hi, lo).  Integer
+ *      addition commutes: the order of the pairs cannot matter, and there is no float sum at all.
+ *  10. Means.  A sum that fits int64 (hi is the sign extension of lo) is converted from that int64
+ *      with one rounding; a larger one is (double)hi * 2^64 + (double)(uint64)lo.  Then dot[k, b] =
+ *      (x * unit) / (double)n, and likewise longitudinal (from the L sum) and cos (with unit_cos).
+ *      transverse comes from the exact integer difference S_dot - S_L the same way, divided also by
+ *      ndim - 1: ((x * unit) / (double)n) / (double)(ndim - 1), the mean per transverse axis.  NaN
+ *      where n == 0.
+ *  11. A refused table.  A frame_offset that does not rise within [0, N] or a particle[i] >= P is
+ *      refused: status[0] = CTR_TP_BAD_TABLE, float outputs NaN, integers 0, and no kernel follows an
+ *      index of a refused table.
+ * Consequences: (i, j) and (j, i) give the same three integers (a_i and a_j swap and change sign
+ * exactly), so n and every sum are even; S_all == S_same + S_other as integers.
+ * Launches, 256 threads each.  twopt_check.  twopt_defaults zeroes the integer outputs.
+ * twopt_partner, one workgroup per (lag, frame), striding: the partner's row of every moved row, or
+ * -1, into scratch, 4 bytes per row and lag; the rows of frame t + k go through an LDS open-addressing
+ * table in tiles of 2048, lowest row kept (drift's); n_moved and beyond by integer atomics.
+ * twopt_items: the exclusive scan of ceil(rows / 256) over the frames.  twopt_pairs, one workgroup
+ * per (lag, frame, tile of 256 rows), striding: a thread keeps q, u and u2 of its row in registers
+ * and walks the frame's rows, staged 256 at a time in LDS with their u and u2 (the walk of g(r));
+ * 32-bit counts and 64-bit sums per bin in LDS, added to the global (hi, lo) words at the end of a
+ * work item and every 32 tiles (|integer| <= 2^41 per pair, 2^16 pairs per tile: below 2^62); the
+ * carry into hi is the old low word against the new one, plus the sign extension.  twopt_finish, one
+ * thread per (k, b): clause 10.  Integer atomics only: the same bytes on every call.
+ * Scratch of the handle: 8 (T + 1) + 4 K N bytes.
+ * Descriptors are checked before the handle.  Device pointers; asynchronous on `hip_stream`. */
+#define CTR_TP_OK 0
+#define CTR_TP_BAD_TABLE 1
+#define CTR_TP_MAX_BINS 512          /* edge2, the counts and the sums of a workgroup are in LDS */
+#define CTR_TP_MAX_LAGS 16
+typedef struct ctr_twopoint {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t pairs;                   /* CTR_PCF_PAIRS_* */
+  int32_t n_lags;                  /* K, 1 .. CTR_TP_MAX_LAGS */
+  int32_t reserved0;
+  int64_t n_bins;                  /* B, 1 .. CTR_TP_MAX_BINS */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P */
+  double dr;                       /* > 0 */
+  double max2;                     /* max_disp squared, within [2^-500, 2^500]; (n_bins dr)^2 max2 <= 2^1000 */
+  double mpp[CTR_MAX_NDIM];        /* per axis, > 0 */
+  int64_t lag[CTR_TP_MAX_LAGS];    /* ascending, distinct, >= 1 */
+  const double* pos;               /* [N, ndim] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const int64_t* particle;         /* [N] */
+  const int64_t* group;            /* [N], or null with CTR_PCF_PAIRS_ALL */
+  const double* edge2;             /* [B + 1] */
+  int64_t* n;                      /* [K, B] out */
+  double* dot;                     /* [K, B] out */
+  double* longitudinal;            /* [K, B] out */
+  double* transverse;              /* [K, B] out */
+  double* cos;                     /* [K, B] out */
+  int64_t* sums;                   /* [K, B, 3, 2] out: dot, L, c; each (hi, lo) */
+  int64_t* n_moved;                /* [K] out */
+  int64_t* beyond;                 /* [K] out */
+  int32_t* status;                 /* [1] out */
+} ctr_twopoint;
+int ctr_twopoint_device(ctr_handle* h, const ctr_twopoint* d, void* hip_stream);
+
 /* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
  * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
  * (find_clusters, the stable sort by (frame, cluster), FitFunctions.feature_bounds, the feasibility
@@ -1593,7 +1690,7 @@ int ctr_refine_prepare_plan(const ctr_refine_prepare* r, int64_t* scratch_bytes)
 
 /* A test switch: the most workgroups that a grid-stride kernel of the table stages is launched with
  * by every later stage call of this handle (refine_prepare, drift, msd / emsd, vanhove,
- * pair_correlation, neighbors, cluster_tracks / track_positions, and the per-level refinement of
+ * pair_correlation, neighbors, twopoint, cluster_tracks / track_positions, and the per-level refinement of
  * ctr_find_link_refine_device, whose fixed grid is lowered to it).  max_grid within [1, 65536], or
  * 0 for the default of 65536.  Returns the cap that held before; a null handle or a value outside
  * the range returns -1 and changes nothing.  A stage's results never depend on it: every such
