@@ -61,7 +61,7 @@ KFAM_NONE, KFAM_SMALL, KFAM_GAUSS, KFAM_GAUSS_TP, KFAM_LOWPASS, KFAM_RING, KFAM_
 
 
 FLAG_THROUGHPUT = 1   # ctr_problem.flags (include/ctrefine.h): scheduling hint, results unchanged
-FLAG_ISOLATE_TAIL = 2  # only the kernel of the likely slow fits beside the main stream
+FLAG_ISOLATE_TAIL = 2  # accepted, without effect: the lanes place a long kernel by its measured duration
 FLAG_WINDOW_FILTER = 4  # noise_size was given: the window is thresholded even with every sigma 0
 
 

@@ -72,6 +72,7 @@ SIGNATURES = {
     'ctr_diffusion_ci_plan': (C.c_int, [_P(_abi.DiffusionCI), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                         _P(C.c_int64)]),
     'ctr_set_stage_max_grid': (C.c_int32, [_H, C.c_int32]),
+    'ctr_set_lane_limit': (C.c_int32, [C.c_int32, C.c_int32]),
     'ctr_query_done': (C.c_int, [_H]),
     'ctr_ipc_alloc': (C.c_int, [_H, C.c_int64, _P(C.c_void_p), C.c_void_p]),
     'ctr_ipc_open': (C.c_int, [_H, C.c_void_p, _P(C.c_void_p)]),
@@ -298,6 +299,12 @@ class Engine(object):
             yield self
         finally:
             self.set_stage_max_grid(before)
+
+    def set_lane_limit(self, n):
+        """``ctr_set_lane_limit`` on this engine's device: later ``refine_batch_device`` calls use
+        only the first ``n`` lanes (0: all).  Returns the number in use before, -1 for a value
+        outside the range (nothing changes).  Results never depend on it."""
+        return int(self._lib.ctr_set_lane_limit(C.c_int32(self.device), C.c_int32(int(n))))
 
     def synchronize(self, stream=None):
         self._check(self._lib.ctr_synchronize(self._h, C.c_void_p(stream or 0)),

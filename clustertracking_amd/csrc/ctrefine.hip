@@ -16,18 +16,24 @@
 //                         Cholesky + range-space KKT step (constraints)
 //   find_clusters_kernel  cluster labelling of a frame (find.py:72-93)
 // Clusters are binned by problem size on the host (ctr_plan_create); the bins run
-// concurrently on forked streams.  gfx950 only; no CUDA paths, no CPU fallback.
+// concurrently on the lanes of the device (lane_sched.h).  gfx950 only; no CUDA paths, no CPU
+// fallback.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <chrono>
+#include <functional>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "kargs.h"
+#include "lane_sched.h"
 
 namespace {
 
@@ -58,13 +64,22 @@ constexpr int SLOT_SINGLES8 = 0, SLOT_SINGLES64 = 1, SLOT_PAIRS64 = 2, SLOT_PAIR
 // pixels of a single-feature window up to which singles take 8 lanes (else 64) and a bin of pairs
 // may run in two tiers (ctr_plan_create)
 constexpr int64_t NARROW_WINDOW = 600;
-// side streams for concurrent bin launches.  Three, not more: HIP deals streams to the hardware
-// queues round robin, and with 1 + 3 streams per handle and a queue count that is a multiple of 4
-// the streams that share a queue have the same role in different handles; eight handles in flight
-// reach the same rate as with four side streams (48 M cluster-fits/s on cfg 2) over a wider range
-// of GPU_MAX_HW_QUEUES (16..22 instead of 20..22)
-constexpr int NSIDE = 3;
 constexpr int GATE_US = 20;  // head start of the block kernels over the small kernels (delay_kernel)
+// launches of a call that are chains of their own on the lanes: one per bin, and the bulk tier of
+// the pairs
+constexpr int LAUNCH_PAIRS16 = NBINS, NLAUNCH = NBINS + 1;
+
+// The duration of one launch of a plan, for the placement of its next call (lane_sched.h): a pair
+// of timing events around the kernel, read back without blocking once both have completed.  While
+// a pair is pending, later calls of the plan are not timed; nor is every call after the first
+// reading (TIMING_EVERY).
+constexpr int TIMING_EVERY = 8;
+struct LaunchTiming {
+  lane_sched::Estimate est;
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  bool pending = false;
+  int untimed = 0;   // calls since the launch was last timed
+};
 
 struct ctr_plan {
   ctr_problem prob;
@@ -77,6 +92,7 @@ struct ctr_plan {
   double* d_ws = nullptr;
   long long* d_ws_off = nullptr;   // [n_clusters] offset in doubles (0 for the other clusters)
   mutable int large_epoch = 0;     // launches of the large kernel on this plan (tags its leader / helper words)
+  mutable LaunchTiming timing[NLAUNCH];   // guarded by the mutex of the device's lane pool
   int64_t bin_begin[NBINS + 1] = {0};
   int64_t bin_count[NBINS] = {0};
   // choose_kernel's family and table slot of each bin (the same for every cluster of a bin)
@@ -100,9 +116,32 @@ struct Scratch {
   hipEvent_t event = nullptr;
 };
 
+// The lanes of a device: one non-blocking stream per hardware queue (pool_acquire finds them),
+// shared by every handle of the device and counted by them.  How many at most: lane_sched.h,
+// lanes_from_env(GPU_MAX_HW_QUEUES), read once when the pool is made; it decides where a kernel is
+// queued, never what it computes.  mu guards the books and the enqueues of a call: the chains of
+// two calls never interleave on a lane otherwise than call by call.
+struct LanePool {
+  int device = 0, refs = 0;
+  std::mutex mu;
+  std::vector<hipStream_t> lanes;
+  lane_sched::Pool books;
+  std::vector<hipEvent_t> spare;   // ticket events (no timing) that have completed, to be recorded again
+  explicit LanePool(int n) : books(n) {}
+};
+
 struct ctr_handle {
   int device = 0;
+  // The handle's own stream: what hip_stream = NULL means to every entry point.  A refine call
+  // on it is queued on the lanes alone and leaves `pending` set; whoever names the stream next
+  // goes through own_stream(), which makes it wait for that call first (a lazy join: no stream
+  // sits in a device-side wait for a call's slowest kernel while nobody asks for its results).
   hipStream_t stream = nullptr;
+  LanePool* pool = nullptr;
+  bool pending = false;      // ev_done of a call on the own stream has not been joined to `stream`
+  // work, or a wait (ctr_engine_wait_stream), was queued on `stream` since the last refine call:
+  // the head of the next one waits for an event recorded on the stream, which covers all of it
+  bool own_dirty = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool ev_valid = false;
   std::string err;
@@ -112,8 +151,10 @@ struct ctr_handle {
   // unreachable cell is null.  attr_set: its dynamic LDS limit is set (table_kernel)
   struct { KernelInfo k; bool attr_set; } kernels[NFAM][2][2][NSLOT] = {};
   hipEvent_t ev_done = nullptr;   // end of the last ctr_refine_batch_device call of this handle
-  hipStream_t side[NSIDE] = {};
-  hipEvent_t ev_fork = nullptr, ev_gate = nullptr, ev_order = nullptr, ev_join[NSIDE] = {};
+  // ev_fork / ev_gate: the head chain of a call has prepared it / its small kernels may start;
+  // ev_order: ctr_stream_wait_engine / ctr_engine_wait_stream; ev_own: what was queued
+  // on the own stream before a call
+  hipEvent_t ev_fork = nullptr, ev_gate = nullptr, ev_order = nullptr, ev_own = nullptr;
   int* d_counter = nullptr;       // work counters of the small-kernel launches
   // ctr_link_device, ctr_find_link_device and ctr_find_link_refine_device; ctr_diffusion_device and ctr_diffusion_ci_device (partial sums, rows, statistics)
   Scratch link, motion;
@@ -142,6 +183,114 @@ int fail(ctr_handle* h, int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                                  \
       return fail(h, CTR_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_));   \
   } while (0)
+
+// ---- the lanes (LanePool) ------------------------------------------------------------------
+// by device.  A mutex of their own: the first handle of a device holds it through the trial of
+// pool_acquire (device synchronises, 10-20 ms), which must not block ctr_last_error and the like
+std::map<int, LanePool*> g_pools;
+std::mutex g_pool_mutex;
+
+// Is `cand` served by a hardware queue that none of `lanes` (on distinct queues themselves) is on?
+// A queue is served in order: with a delay kernel on every lane, one more on cand, queued last,
+// ends one delay after it was queued when cand has a queue to itself, and nearly two when it
+// stands behind a lane's (nearly: the lanes' kernels were queued a few us each earlier -- with a
+// delay of 400 us and nine lanes that difference already hid a queue of its own).  Measured on the
+// host, the best of three (whatever else the machine does can only lengthen a run: a wrong answer
+// costs a lane, never a result).
+constexpr unsigned PROBE_US = 1000;
+bool on_new_queue(const std::vector<hipStream_t>& lanes, hipStream_t cand) {
+  for (int rep = 0; rep < 3; ++rep) {
+    for (hipStream_t st : lanes) (void)hipStreamSynchronize(st);
+    (void)hipStreamSynchronize(cand);
+    for (hipStream_t st : lanes) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, st, (unsigned long long)PROBE_US * 100ull);
+    const auto t0 = std::chrono::steady_clock::now();
+    hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, cand, (unsigned long long)PROBE_US * 100ull);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = hipStreamSynchronize(cand) == hipSuccess && ok;
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    for (hipStream_t st : lanes) ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    if (!ok) return true;   // (no answer: keep the stream)
+    if (us < 1.5 * PROBE_US) return true;
+  }
+  return false;
+}
+
+// the pool of the device, made by its first handle; null: its streams could not be created.
+// How the runtime deals streams to the hardware queues is its own business (measured here: the
+// first GPU_MAX_HW_QUEUES streams of a process open a queue each, a later one joins the queue with
+// the fewest streams -- four streams made back to back by the first handle landed on three
+// queues), so the lanes are found by trial: streams are made until as many as there are queues
+// have proved to be on queues of their own, or three times that many have been tried; the
+// others are destroyed again.  (The device is current.)
+LanePool* pool_acquire(int device) {
+  std::lock_guard<std::mutex> g(g_pool_mutex);
+  LanePool*& slot = g_pools[device];
+  if (!slot) {
+    const int want = lane_sched::lanes_from_env(std::getenv("GPU_MAX_HW_QUEUES"));
+    std::vector<hipStream_t> lanes, rejected;
+    {
+      hipStream_t warm = nullptr;   // (the first launch of a kernel loads its code: not part of a trial)
+      if (hipStreamCreateWithFlags(&warm, hipStreamNonBlocking) != hipSuccess) { g_pools.erase(device); return nullptr; }
+      hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, warm, 100ull);
+      (void)hipStreamSynchronize(warm);
+      (void)hipGetLastError();
+      rejected.push_back(warm);
+    }
+    for (int tried = 0; (int)lanes.size() < want && tried < 3 * want; ++tried) {
+      hipStream_t st = nullptr;
+      if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) break;
+      (lanes.empty() || on_new_queue(lanes, st) ? lanes : rejected).push_back(st);
+    }
+    // (the rejected streams lived until here: each kept its queue less attractive for the next)
+    for (hipStream_t st : rejected) (void)hipStreamDestroy(st);
+    if (lanes.empty()) { g_pools.erase(device); return nullptr; }
+    LanePool* p = new LanePool((int)lanes.size());
+    p->device = device;
+    p->lanes = lanes;
+    slot = p;
+  }
+  slot->refs++;
+  return slot;
+}
+
+bool ticket_done(void*, lane_sched::EventId ev) { return hipEventQuery((hipEvent_t)ev) != hipErrorNotReady; }
+
+// the last handle of a device takes the pool with it, once its lanes have run dry
+void pool_release(LanePool* p) {
+  if (!p) return;
+  std::lock_guard<std::mutex> g(g_pool_mutex);
+  if (--p->refs > 0) return;
+  g_pools.erase(p->device);
+  for (hipStream_t st : p->lanes) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+  std::vector<lane_sched::EventId> retired;
+  p->books.retire([](void*, lane_sched::EventId) { return true; }, nullptr, &retired);
+  for (lane_sched::EventId ev : retired) (void)hipEventDestroy((hipEvent_t)ev);
+  for (hipEvent_t ev : p->spare) (void)hipEventDestroy(ev);
+  delete p;
+}
+
+// a ticket event of the pool, recorded on the lane at the end of a chain; booked with the chain's
+// estimate.  (p->mu is held.)
+hipError_t lane_ticket(LanePool* p, int lane, double ms, hipEvent_t* out) {
+  hipEvent_t ev = nullptr;
+  if (!p->spare.empty()) { ev = p->spare.back(); p->spare.pop_back(); }
+  else if (hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) return e;
+  if (hipError_t e = hipEventRecord(ev, p->lanes[(size_t)lane])) { p->spare.push_back(ev); return e; }
+  p->books.push(lane, (lane_sched::EventId)ev, ms);
+  *out = ev;
+  return hipSuccess;
+}
+
+// The handle's own stream for whoever queues work on it or waits for it: joined with the handle's
+// pending refine call first (ctr_handle::stream).
+hipStream_t own_stream(ctr_handle* h) {
+  if (h->pending) {
+    (void)hipStreamWaitEvent(h->stream, h->ev_done, 0);
+    h->pending = false;
+  }
+  h->own_dirty = true;
+  return h->stream;
+}
 
 int validate(const ctr_problem* p, std::string& msg) {
   if (!p) { msg = "null problem"; return CTR_ERR_INVALID; }
@@ -255,7 +404,7 @@ int run_stage(const char* name, ctr_handle* h, Scratch ctr_handle::*scratch, con
   if (scratch && run.scratch_bytes == 0) return CTR_OK;   // nothing to launch: the device is not touched
   HIP_TRY(h, hipSetDevice(h->device));
   run.mode = STAGE_LAUNCH;
-  run.stream = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  run.stream = hip_stream ? (hipStream_t)hip_stream : own_stream(h);
   Scratch* sc = scratch ? &(h->*scratch) : nullptr;
   if (sc) {
     if (!sc->event) HIP_TRY(h, hipEventCreateWithFlags(&sc->event, hipEventDisableTiming));
@@ -464,14 +613,12 @@ int ctr_create(ctr_handle** out, int device) {
   }
   for (auto& ev : h->ev)
     if (hipEventCreate(&ev) != hipSuccess) { delete h; return fail(nullptr, CTR_ERR_DEVICE, "hipEventCreate failed"); }
-  for (auto& st : h->side)
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { delete h; return fail(nullptr, CTR_ERR_DEVICE, "cannot create side streams"); }
-  bool evok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_gate, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming) == hipSuccess;
-  for (auto& ev : h->ev_join) evok = evok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-  evok = evok && hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) == hipSuccess;
-  if (!evok || hipMalloc((void**)&h->d_counter, sizeof(int) * 8) != hipSuccess) { delete h; return fail(nullptr, CTR_ERR_DEVICE, "cannot create events / counters"); }
+  bool evok = true;
+  for (hipEvent_t* ev : {&h->ev_fork, &h->ev_gate, &h->ev_order, &h->ev_own, &h->ev_done})
+    evok = evok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
+  if (!evok || hipMalloc((void**)&h->d_counter, sizeof(int) * 8) != hipSuccess) { ctr_destroy(h); return fail(nullptr, CTR_ERR_DEVICE, "cannot create events / counters"); }
+  h->pool = pool_acquire(device);
+  if (!h->pool) { ctr_destroy(h); return fail(nullptr, CTR_ERR_DEVICE, "cannot create the lanes of the device"); }
   for (int fam = 0; fam < NFAM; ++fam)
     for (int di = 0; di < 2; ++di)
       for (int ii = 0; ii < 2; ++ii)
@@ -483,20 +630,19 @@ int ctr_create(ctr_handle** out, int device) {
 void ctr_destroy(ctr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
+  // the last refine call, wherever its chains run, uses the handle's scratch until ev_done
+  if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
   for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
-  for (auto& st : h->side) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_gate) (void)hipEventDestroy(h->ev_gate);
-  if (h->ev_order) (void)hipEventDestroy(h->ev_order);
-  if (h->ev_done) (void)hipEventDestroy(h->ev_done);
-  for (auto& ev : h->ev_join) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {h->ev_fork, h->ev_gate, h->ev_order, h->ev_own, h->ev_done})
+    if (ev) (void)hipEventDestroy(ev);
   if (h->d_counter) (void)hipFree(h->d_counter);
   if (h->stream) (void)hipStreamDestroy(h->stream);
+  pool_release(h->pool);
   delete h;
 }
 
@@ -620,6 +766,10 @@ void ctr_plan_destroy(ctr_plan* plan) {
   if (plan->d_ws) (void)hipFree(plan->d_ws);
   if (plan->d_ws_off) (void)hipFree(plan->d_ws_off);
   if (plan->d_lp_w) (void)hipFree(plan->d_lp_w);
+  for (LaunchTiming& t : plan->timing) {
+    if (t.t0) (void)hipEventDestroy(t.t0);
+    if (t.t1) (void)hipEventDestroy(t.t1);
+  }
   delete plan;
 }
 
@@ -627,7 +777,7 @@ int ctr_frame_max_device(ctr_handle* h, const void* frames, int32_t frame_dtype,
                          int64_t frame_elems, double* out_max, void* hip_stream) {
   if (!h) return CTR_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : own_stream(h);
   return launch_frame_max(h, frames, frame_dtype, n_frames, frame_elems, out_max, s);
 }
 
@@ -639,19 +789,28 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
   for (int a = 0; a < p.ndim; ++a)
     if (b->shape[a] < 1) return fail(h, CTR_ERR_INVALID, "frame shape must be positive");
   HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  // A call is a set of chains, each a run of work for one stream:
+  //   head    waits for the handle's previous call and for what the caller ordered before this one,
+  //           then frame maxima, counters and this call's order of the clusters; records ev_fork
+  //           (and, after the delay of the gate, ev_gate)
+  //   bins    one chain per kernel launch: waits for ev_fork (the small kernels for ev_gate),
+  //           runs the kernel
+  //   finish  waits for every bin chain, then result rows, done flag, ev_done
+  // The bin chains go to the lanes of the device.  On a caller's stream the contract is stream
+  // order: head and finish stay on that stream.  On the handle's own stream (hip_stream = NULL)
+  // they go to lanes as well, nothing is queued on the stream itself and the call is left pending
+  // (own_stream).
+  // INVARIANT: a chain only waits for events that were recorded earlier in host order -- a call is
+  // enqueued head, bins, finish, under the pool's mutex, and its head waits for events of earlier
+  // calls alone.  Host order is therefore a valid order of execution for every placement, one lane
+  // for everything included: no chain can wait for something behind it in its own lane.
+  const bool own = hip_stream == nullptr;
+  LanePool* const pool = h->pool;
   int64_t frame_elems = 1;
   for (int a = 0; a < p.ndim; ++a) frame_elems *= b->shape[a];
   h->ev_valid = false;
-  // The handle owns scratch that a call uses from start to end (frame maxima, work counters,
-  // side streams): a call on another stream waits for the previous call of this handle.
-  HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));
-  HIP_TRY(h, hipEventRecord(h->ev[0], s));
   int rc = ensure_fmax(h, b->n_frames > 0 ? b->n_frames : 1);
   if (rc) return rc;
-  rc = launch_frame_max(h, b->frames, b->frame_dtype, b->n_frames, frame_elems, (double*)h->fmax.ptr, s);
-  if (rc) return rc;
-  HIP_TRY(h, hipEventRecord(h->ev[1], s));
 
   // squared relative residual tolerances of the large kernel's conjugate-gradient solve, far from /
   // near the solution (with the aggregated preconditioner 1e-8 far saves 12 % and costs parity:
@@ -681,46 +840,30 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
   k.cg_tol2_near = LARGE_CG_TOL2_NEAR;
   for (int a = 0; a < 3; ++a) k.lp_half[a] = plan->lp_half[a];
   const int ii = p.isotropic ? 1 : 0;
-  // The bins are independent: the big bin of singles runs on the caller's
-  // stream, the others on side streams forked from / joined to it by events, so
-  // that a few slow many-feature clusters overlap with the bulk.
+  // From here on the pool's mutex is held: the plan's timing entries (their guesses included) and
+  // the lanes' books belong to it.  An error return in the middle of the enqueue (HIP_TRY) leaves
+  // what was queued so far queued, its tickets booked -- they retire when their events complete --
+  // and ev_done of this call unrecorded: the handle's next call then waits for the call before
+  // this one, as after any failed call, and the caller is told that this one failed.
+  std::lock_guard<std::mutex> lock(pool->mu);
   // this call's order inside the bins: likely stragglers first (front_load_kernel)
   int32_t* ord = plan->d_order + plan->n_clusters;
-  {
-    FrontArgs fa;
-    fa.nbins = NBINS;
-    fa.keep_bin = BIN_SMALL1;
-    for (int bin = 0; bin < NBINS; ++bin) { fa.begin[bin] = (int)plan->bin_begin[bin]; fa.count[bin] = (int)plan->bin_count[bin]; }
-    HIP_TRY(h, hipMemsetAsync(plan->d_front, 0, sizeof(int) * 2 * NBINS, s));
-    // the work counters of the small-kernel launches, here rather than in their streams: a
-    // fill kernel queued behind the gate would wait for a slot on a machine already flooded
-    HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int) * 8, s));
-    hipLaunchKernelGGL(front_load_kernel, dim3((unsigned)((plan->n_clusters + 255) / 256)), dim3(256), 0, s, k, fa,
-                       plan->d_order, ord, plan->d_front, (int)plan->n_clusters);
-  }
-  HIP_TRY(h, hipEventRecord(h->ev_fork, s));
-  bool used[NSIDE] = {};
-  int next_side = 0;
-  // Which stream a kernel takes: the caller's (MAIN) or a side stream.  Default: round robin over
-  // the side streams in launch order.  With CTR_FLAG_ISOLATE_TAIL the tier of the likely slow fits
-  // (SLOW_SIDE: the 64-lane pairs kernel, the large-cluster kernel) has side stream 1 to itself and
-  // the others alternate between 0 and 2: with 4 streams per handle on 2 hardware queues per
-  // handle, stream k of a handle shares its queue with stream 3 - k of another handle (0 = main),
-  // so a long kernel on side 1 holds up that handle's side-0 kernels -- not its main stream, on
-  // which its next batch begins (a slow kernel in front of another handle's main stream delays
-  // that handle's whole next batch, slow kernel included: the delays chain).
-  enum StreamRole { MAIN, SIDE, SLOW_SIDE };
-  const bool isolate = (p.flags & CTR_FLAG_ISOLATE_TAIL) != 0;
-  auto pick_stream = [&](StreamRole role) -> hipStream_t {
-    if (role == MAIN) return s;
-    int j;
-    if (isolate) j = role == SLOW_SIDE ? 1 : (next_side++ % 2 == 0 ? 0 : 2);
-    else j = next_side++ % NSIDE;
-    if (!used[j]) { used[j] = true; (void)hipStreamWaitEvent(h->side[j], h->ev_fork, 0); }
-    return h->side[j];
+  // The bins are independent: every launch is a chain of its own, so that a few slow many-feature
+  // clusters overlap with the bulk.  The chains are made first -- a missing kernel is reported
+  // before anything is queued -- and enqueued in the order of their placement.  launch: the entry
+  // of plan->timing; gated: starts with the small kernels; run: queues the chain's kernels.
+  // (CTR_FLAG_ISOLATE_TAIL changes nothing here: the placement below keeps a long kernel out of
+  // the way of the others by its measured duration, whichever bin it belongs to.)
+  struct Chain {
+    int launch;
+    bool gated;
+    std::function<hipError_t(hipStream_t)> run;
   };
-  // block bins first, largest problems first (NT 8 -> 1, then the constrained NT 2 -> 1) so that
-  // their tails start early
+  std::vector<Chain> chains;
+  auto guess = [&](int launch, lane_sched::ChainClass cls, int64_t count, int nt) {
+    plan->timing[launch].est.guess = lane_sched::static_guess(cls, count, nt);
+  };
+  // block bins: NT 8 -> 1, then the constrained NT 2 -> 1
   for (int i = 0; i < MAXNT + 2; ++i) {
     const int bin = i < MAXNT ? MAXNT - 1 - i : (i == MAXNT ? BIN_CONS2 : BIN_CONS1);
     const int64_t cnt = plan->bin_count[bin];
@@ -730,8 +873,11 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     if (rc) return rc;
     k.order = ord + plan->bin_begin[bin];
     k.n_bin = (int32_t)cnt;
-    void* kargs[] = {(void*)&k};
-    HIP_TRY(h, hipLaunchKernel(ki->fn, dim3((unsigned)cnt), dim3((unsigned)ki->threads), kargs, ki->smem, pick_stream(SIDE)));
+    guess(bin, lane_sched::CHAIN_BLOCK, cnt, bin < MAXNT ? bin + 1 : (bin == BIN_CONS2 ? 2 : 1));
+    chains.push_back({bin, false, [k, ki, cnt](hipStream_t st) {
+      void* kargs[] = {(void*)&k};
+      return hipLaunchKernel(ki->fn, dim3((unsigned)cnt), dim3((unsigned)ki->threads), kargs, ki->smem, st);
+    }});
   }
   if (plan->bin_count[BIN_LARGE] > 0) {
     const int64_t cnt = plan->bin_count[BIN_LARGE];
@@ -743,28 +889,29 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     double* wsp = plan->d_ws;
     const long long* wso = plan->d_ws_off;
     int epoch = ++plan->large_epoch;
-    void* kargs[] = {(void*)&k, (void*)&wsp, (void*)&wso, (void*)&epoch};
-    HIP_TRY(h, hipLaunchKernel(ki->fn, dim3((unsigned)(cnt * plan->large_workgroups)), dim3((unsigned)ki->threads), kargs,
-                               ki->smem, pick_stream(SLOW_SIDE)));
+    const unsigned grid = (unsigned)(cnt * plan->large_workgroups);
+    guess(BIN_LARGE, lane_sched::CHAIN_LARGE, cnt, 1);
+    chains.push_back({BIN_LARGE, false, [k, ki, grid, wsp, wso, epoch](hipStream_t st) {
+      void* kargs[] = {(void*)&k, (void*)&wsp, (void*)&wso, (void*)&epoch};
+      return hipLaunchKernel(ki->fn, dim3(grid), dim3((unsigned)ki->threads), kargs, ki->smem, st);
+    }});
   }
   if (plan->bin_count[BIN_TOO_LARGE] > 0) {
     const int64_t cnt = plan->bin_count[BIN_TOO_LARGE];
     k.order = ord + plan->bin_begin[BIN_TOO_LARGE];
     k.n_bin = (int32_t)cnt;
-    hipLaunchKernelGGL(mark_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, pick_stream(SIDE), k,
-                       (int)CTR_STATUS_TOO_LARGE);
+    guess(BIN_TOO_LARGE, lane_sched::CHAIN_MARK, cnt, 1);
+    chains.push_back({BIN_TOO_LARGE, false, [k, cnt](hipStream_t st) {
+      hipLaunchKernelGGL(mark_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, k, (int)CTR_STATUS_TOO_LARGE);
+      return hipGetLastError();
+    }});
   }
-  if (plan->gate) {
-    hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, s, (unsigned long long)GATE_US * 100ull);
-    HIP_TRY(h, hipEventRecord(h->ev_gate, s));
-  }
+  // the small kernels start GATE_US after the others, where there are others (plan->gate)
   if (plan->bin_count[BIN_SMALL2] > 0) {
     const int64_t cnt = plan->bin_count[BIN_SMALL2];
     const KernelInfo* ki;
     rc = table_kernel(h, plan->bin_family[BIN_SMALL2], p.ndim, ii, plan->bin_slot[BIN_SMALL2], &ki);
     if (rc) return rc;
-    hipStream_t st = pick_stream(SLOW_SIDE);
-    if (plan->gate) (void)hipStreamWaitEvent(st, h->ev_gate, 0);
     int* counter = h->d_counter + 2;
     k.order = ord + plan->bin_begin[BIN_SMALL2];
     k.n_bin = (int32_t)cnt;
@@ -772,31 +919,33 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     if (plan->pairs_split) {
       // front_load_kernel has put the pairs closer than a quarter of the mask radius first and
       // counted them (on the device): the 64-lane kernel takes exactly those, the 16-lane kernel,
-      // on a stream of its own, the others -- which kernel fits a pair depends on the pair alone,
+      // a chain of its own, the others -- which kernel fits a pair depends on the pair alone,
       // not on the order of the batch.
       const KernelInfo* kb;
       rc = table_kernel(h, plan->bin_family[BIN_SMALL2], p.ndim, ii, SLOT_PAIRS16, &kb);
       if (rc) return rc;
       k.split = plan->d_front + 2 * BIN_SMALL2;
-      hipStream_t sb = pick_stream(SIDE);
-      if (plan->gate) (void)hipStreamWaitEvent(sb, h->ev_gate, 0);
-      // (a little later still than the first tier, whose few wavefronts must not queue up
-      // behind the thousands of this one)
-      hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, sb, (unsigned long long)GATE_US * 100ull);
       int* cbulk = h->d_counter + 3;
       k.split_part = 2;
       int64_t wb = (cnt + 3) / 4;
       if (wb > 8192) wb = 8192;
-      {
+      guess(LAUNCH_PAIRS16, lane_sched::CHAIN_PAIRS16, cnt, 1);
+      chains.push_back({LAUNCH_PAIRS16, plan->gate, [k, kb, wb, cbulk](hipStream_t st) {
+        // (a little later still than the first tier, whose few wavefronts must not queue up
+        // behind the thousands of this one)
+        hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, st, (unsigned long long)GATE_US * 100ull);
         void* kargs[] = {(void*)&k, (void*)&cbulk};
-        HIP_TRY(h, hipLaunchKernel(kb->fn, dim3((unsigned)wb), dim3(WAVE), kargs, 0, sb));
-      }
+        return hipLaunchKernel(kb->fn, dim3((unsigned)wb), dim3(WAVE), kargs, 0, st);
+      }});
       k.split_part = 1;
       if (waves > 2048) waves = 2048;   // persistent: a wavefront takes pair after pair
     }
     if (waves > 8192) waves = 8192;
-    void* kargs[] = {(void*)&k, (void*)&counter};
-    HIP_TRY(h, hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st));
+    guess(BIN_SMALL2, lane_sched::CHAIN_PAIRS64, cnt, 1);
+    chains.push_back({BIN_SMALL2, plan->gate, [k, ki, waves, counter](hipStream_t st) {
+      void* kargs[] = {(void*)&k, (void*)&counter};
+      return hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st);
+    }});
     k.split = nullptr;
     k.split_part = 0;
   }
@@ -810,23 +959,120 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     k.n_bin = (int32_t)cnt;
     int64_t waves = plan->bin_slot[BIN_SMALL1] == SLOT_SINGLES64 ? cnt : (cnt + 7) / 8;
     if (waves > 8192) waves = 8192;
-    void* kargs[] = {(void*)&k, (void*)&counter};
-    HIP_TRY(h, hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, pick_stream(MAIN)));
+    guess(BIN_SMALL1, lane_sched::CHAIN_SINGLES, cnt, 1);
+    chains.push_back({BIN_SMALL1, plan->gate, [k, ki, waves, counter](hipStream_t st) {
+      void* kargs[] = {(void*)&k, (void*)&counter};
+      return hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st);
+    }});
   }
-  for (int j = 0; j < NSIDE; ++j)
-    if (used[j]) {
-      HIP_TRY(h, hipEventRecord(h->ev_join[j], h->side[j]));
-      HIP_TRY(h, hipStreamWaitEvent(s, h->ev_join[j], 0));
+
+  lane_sched::Pool& books = pool->books;
+  // the books: what has completed leaves the lanes, and the launches of this plan that were timed
+  // and have completed give their durations
+  {
+    std::vector<lane_sched::EventId> retired;
+    books.retire(ticket_done, nullptr, &retired);
+    for (lane_sched::EventId ev : retired) pool->spare.push_back((hipEvent_t)ev);
+  }
+  std::vector<double> est(chains.size());
+  for (size_t i = 0; i < chains.size(); ++i) {
+    LaunchTiming& t = plan->timing[chains[i].launch];
+    if (t.pending && hipEventQuery(t.t1) != hipErrorNotReady) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, t.t0, t.t1) == hipSuccess) t.est.update((double)ms);
+      t.pending = false;
     }
+    est[i] = t.est.value();
+  }
+  (void)hipGetLastError();   // (a query that says "not ready" is no error of this call)
+  const double head_ms = lane_sched::static_guess(lane_sched::CHAIN_HEAD, 0);
+  const lane_sched::Pool::Placement place = books.place(own ? head_ms : -1., est);
+
+  // ---- head ----
+  hipStream_t s = own ? pool->lanes[(size_t)place.head] : (hipStream_t)hip_stream;
+  // The handle owns scratch that a call uses from start to end (frame maxima, work counters): a
+  // call waits for the previous call of this handle, whichever streams the two run on.
+  HIP_TRY(h, hipStreamWaitEvent(s, h->ev_done, 0));
+  if (own) {
+    if (h->own_dirty) {
+      HIP_TRY(h, hipEventRecord(h->ev_own, h->stream));
+      HIP_TRY(h, hipStreamWaitEvent(s, h->ev_own, 0));
+    }
+    h->own_dirty = false;
+  }
+  HIP_TRY(h, hipEventRecord(h->ev[0], s));
+  rc = launch_frame_max(h, b->frames, b->frame_dtype, b->n_frames, frame_elems, (double*)h->fmax.ptr, s);
+  if (rc) return rc;
+  HIP_TRY(h, hipEventRecord(h->ev[1], s));
+  {
+    FrontArgs fa;
+    fa.nbins = NBINS;
+    fa.keep_bin = BIN_SMALL1;
+    for (int bin = 0; bin < NBINS; ++bin) { fa.begin[bin] = (int)plan->bin_begin[bin]; fa.count[bin] = (int)plan->bin_count[bin]; }
+    HIP_TRY(h, hipMemsetAsync(plan->d_front, 0, sizeof(int) * 2 * NBINS, s));
+    // the work counters of the small-kernel launches, here rather than in their chains: a
+    // fill kernel queued behind the gate would wait for a slot on a machine already flooded
+    HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int) * 8, s));
+    k.order = nullptr;   // (the arguments of a bin's launch have no meaning here)
+    k.n_bin = 0;
+    hipLaunchKernelGGL(front_load_kernel, dim3((unsigned)((plan->n_clusters + 255) / 256)), dim3(256), 0, s, k, fa,
+                       plan->d_order, ord, plan->d_front, (int)plan->n_clusters);
+  }
+  HIP_TRY(h, hipEventRecord(h->ev_fork, s));
+  if (plan->gate) {
+    hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, s, (unsigned long long)GATE_US * 100ull);
+    HIP_TRY(h, hipEventRecord(h->ev_gate, s));
+  }
+  hipEvent_t ticket = nullptr;
+  if (own) HIP_TRY(h, lane_ticket(pool, place.head, head_ms, &ticket));
+
+  // ---- bins, the longest first ----
+  // last: the ticket of this call's latest chain on every lane; gate_seen: the lane has waited
+  // for ev_gate (a lane is in order: once is enough, and the head's own lane needs neither wait)
+  std::vector<hipEvent_t> last((size_t)books.size(), nullptr);
+  std::vector<char> gate_seen((size_t)books.size(), 0);
+  for (int i : place.order) {
+    const Chain& c = chains[(size_t)i];
+    const int lane = place.lane[(size_t)i];
+    hipStream_t st = pool->lanes[(size_t)lane];
+    if (st != s && !last[(size_t)lane]) HIP_TRY(h, hipStreamWaitEvent(st, h->ev_fork, 0));
+    if (c.gated && st != s && !gate_seen[(size_t)lane]) {
+      HIP_TRY(h, hipStreamWaitEvent(st, h->ev_gate, 0));
+      gate_seen[(size_t)lane] = 1;
+    }
+    LaunchTiming& t = plan->timing[c.launch];
+    // (two more markers in front of and behind the kernel: 15-20 us of a call that runs alone, so
+    // a launch that has a reading is timed again every TIMING_EVERY calls only)
+    bool timed = !t.pending && (!t.est.has_reading || ++t.untimed >= TIMING_EVERY);
+    if (timed) t.untimed = 0;
+    if (timed && !t.t0) timed = hipEventCreate(&t.t0) == hipSuccess;
+    if (timed && !t.t1) timed = hipEventCreate(&t.t1) == hipSuccess;
+    if (timed) HIP_TRY(h, hipEventRecord(t.t0, st));   // (after the chain's waits)
+    HIP_TRY(h, c.run(st));
+    if (timed) {
+      HIP_TRY(h, hipEventRecord(t.t1, st));
+      t.pending = true;
+    }
+    HIP_TRY(h, lane_ticket(pool, lane, est[(size_t)i], &last[(size_t)lane]));
+  }
+
+  // ---- finish: on the lane of the longest bin chain ----
+  hipStream_t fs = own ? pool->lanes[(size_t)place.finish] : s;
+  for (size_t l = 0; l < last.size(); ++l)
+    if (last[l] && pool->lanes[l] != fs) HIP_TRY(h, hipStreamWaitEvent(fs, last[l], 0));
   if (b->result_rows != nullptr && b->n_features > 0)
-    hipLaunchKernelGGL(result_rows_kernel, dim3((unsigned)((b->n_features + 255) / 256)), dim3(256), 0, s,
+    hipLaunchKernelGGL(result_rows_kernel, dim3((unsigned)((b->n_features + 255) / 256)), dim3(256), 0, fs,
                        b->params_out, b->cost, b->feat_offset, (int)b->n_clusters, (int)b->n_features,
                        (int)p.n_params, b->result_rows);
   if (b->done_flag != nullptr)
-    hipLaunchKernelGGL(done_flag_kernel, dim3(1), dim3(WAVE), 0, s, b->done_flag, b->done_value);
+    hipLaunchKernelGGL(done_flag_kernel, dim3(1), dim3(WAVE), 0, fs, b->done_flag, b->done_value);
   HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipEventRecord(h->ev[2], s));
-  HIP_TRY(h, hipEventRecord(h->ev_done, s));
+  HIP_TRY(h, hipEventRecord(h->ev[2], fs));
+  HIP_TRY(h, hipEventRecord(h->ev_done, fs));
+  if (own) {
+    HIP_TRY(h, lane_ticket(pool, place.finish, lane_sched::static_guess(lane_sched::CHAIN_FINISH, 0), &ticket));
+    h->pending = true;   // joined to the handle's stream by whoever names it next (own_stream)
+  }
   h->ev_valid = true;
   return CTR_OK;
 }
@@ -907,9 +1153,10 @@ int ctr_ipc_open(ctr_handle* h, const unsigned char* handle, void** dev_ptr) {
 int ctr_ipc_probe(ctr_handle* h, void* dst, int64_t value) {
   if (!h || !dst) return CTR_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(done_flag_kernel, dim3(1), dim3(WAVE), 0, h->stream, (int64_t*)dst, value);
+  hipStream_t s = own_stream(h);
+  hipLaunchKernelGGL(done_flag_kernel, dim3(1), dim3(WAVE), 0, s, (int64_t*)dst, value);
   HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipStreamSynchronize(s));
   return CTR_OK;
 }
 
@@ -961,8 +1208,8 @@ int ctr_find_clusters(ctr_handle* h, int32_t ndim, const double* pos, const int3
   int32_t* d_label = (int32_t*)(q + o_label);
   int32_t* d_count = (int32_t*)(q + o_count);
   int32_t* d_size = (int32_t*)(q + o_size);
-  hipStream_t s = h->stream;
-  HIP_TRY(h, hipMemcpyAsync(d_pos, pos, sizeof(double) * (size_t)N * ndim, hipMemcpyHostToDevice, s));
+  hipStream_t s = own_stream(h);
+  HIP_TRY(h, hipMemcpyAsync(d_pos, pos,sizeof(double) * (size_t)N * ndim, hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemcpyAsync(d_fo, frame_offset, sizeof(int32_t) * (size_t)(n_frames + 1), hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemsetAsync(d_count, 0, sizeof(int32_t) * (size_t)N, s));
   const double s2 = ndim == 3 ? separation[2] : 1.;
@@ -997,7 +1244,7 @@ int ctr_draw_frames_device(ctr_handle* h, const ctr_synth* sy, void* frames_out,
     return fail(h, CTR_ERR_INVALID, "null feature table");
   if (sy->n_features > 0x7fffffffLL) return fail(h, CTR_ERR_INVALID, "too many features for one launch");
   HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : own_stream(h);
   int* acc = nullptr;
   HIP_TRY(h, hipMallocAsync((void**)&acc, sizeof(int) * (size_t)total, s));
   HIP_TRY(h, hipMemsetAsync(acc, 0, sizeof(int) * (size_t)total, s));
@@ -1031,7 +1278,7 @@ int ctr_locate_maxima_device(ctr_handle* h, const ctr_locate* l, void* hip_strea
   if (!h) return CTR_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
   const char* msg = "";
-  const int rc = ctr_locate_launch(l, hip_stream ? (hipStream_t)hip_stream : h->stream, &msg);
+  const int rc = ctr_locate_launch(l, hip_stream ? (hipStream_t)hip_stream : own_stream(h), &msg);
   if (rc != CTR_OK) return fail(h, rc, std::string("ctr_locate_maxima_device: ") + msg);
   return CTR_OK;
 }
@@ -1190,8 +1437,23 @@ int32_t ctr_set_stage_max_grid(ctr_handle* h, int32_t max_grid) {
 int ctr_synchronize(ctr_handle* h, void* hip_stream) {
   if (!h) return CTR_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipStreamSynchronize(hip_stream ? (hipStream_t)hip_stream : h->stream));
+  if (hip_stream) {
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)hip_stream));
+    return CTR_OK;
+  }
+  // the handle's own stream, and the refine call that is pending beside it
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipEventSynchronize(h->ev_done));
+  h->pending = false;   // (done: there is nothing left to join)
   return CTR_OK;
+}
+
+int32_t ctr_set_lane_limit(int32_t device, int32_t n) {
+  std::lock_guard<std::mutex> g(g_pool_mutex);
+  const auto it = g_pools.find(device);
+  if (it == g_pools.end() || !it->second) return -1;
+  std::lock_guard<std::mutex> lock(it->second->mu);
+  return it->second->books.set_limit(n);
 }
 
 int ctr_query_done(ctr_handle* h) {
@@ -1209,13 +1471,19 @@ int ctr_engine_wait_stream(ctr_handle* h, void* hip_stream) {
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipEventRecord(h->ev_order, (hipStream_t)hip_stream));
   HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_order, 0));
+  // The head of the next refine call on the own stream is not queued there: it waits for an event
+  // recorded on the stream behind this wait and every earlier one (several calls, for several
+  // streams, are all honoured).
+  h->own_dirty = true;
   return CTR_OK;
 }
 
 int ctr_stream_wait_engine(ctr_handle* h, void* hip_stream) {
   if (!h) return CTR_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipEventRecord(h->ev_order, h->stream));
+  // a pending refine call directly: its end is an event of a lane, not of the handle's stream
+  if (h->pending) HIP_TRY(h, hipStreamWaitEvent((hipStream_t)hip_stream, h->ev_done, 0));
+  HIP_TRY(h, hipEventRecord(h->ev_order, own_stream(h)));
   HIP_TRY(h, hipStreamWaitEvent((hipStream_t)hip_stream, h->ev_order, 0));
   return CTR_OK;
 }
@@ -1281,7 +1549,7 @@ int ctr_refine_batch(ctr_handle* h, const ctr_problem* p, const ctr_batch* b) {
   int32_t* d_rounds = (int32_t*)take(sz_ci);
   int32_t* d_iter = (int32_t*)take(sz_ci);
   double* d_std = b->params_std ? (double*)take(sz_par) : nullptr;
-  hipStream_t s = h->stream;
+  hipStream_t s = own_stream(h);
   HIP_TRY(h, hipMemcpyAsync(d_frames, b->frames, (size_t)b->n_frames * (size_t)frame_elems * isz, hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemcpyAsync(d_fi, b->frame_index, sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemcpyAsync(d_fo, b->feat_offset, sizeof(int32_t) * (size_t)(C + 1), hipMemcpyHostToDevice, s));

@@ -75,13 +75,24 @@ enum { CTR_CONS_NONE = 0, CTR_CONS_DIMER = 1, CTR_CONS_TRIMER = 2, CTR_CONS_TETR
  * each); favour machine time per cluster over the latency of one batch -- pairs that are not
  * likely to be slow fits share a wavefront four at a time, larger 2D clusters run on the
  * fewest wavefronts.
- * CTR_FLAG_ISOLATE_TAIL: for batches that hold a fit far slower than the rest (e.g. two start
- * positions on one real feature: hundreds of iterations) while several batches are in flight:
- * the kernel that takes the likely slow fits gets a stream to itself whose hardware queue it
- * does not share with the main stream of another handle (a queue is served in order: a long
- * kernel in front of a main stream delays that handle's whole next batch).  Costs 10-15 % on
- * batches without such a fit, gains 30 % on batches with one; a caller can time
- * both.  Assumes 2 hardware queues per handle (GPU_MAX_HW_QUEUES = 2 x handles in flight).
+ * CTR_FLAG_ISOLATE_TAIL: accepted, without effect.  It used to give the kernel of the likely slow
+ * fits a stream of its own; the lanes (below) keep a long kernel out of the way of the others by
+ * its measured duration, whichever bin holds it.
+ *
+ * Lanes.  The kernels of ctr_refine_batch_device calls are queued on streams of the library, the
+ * lanes: one per hardware queue of the process, shared by every handle of a device (made with its
+ * first handle, released with its last).  Their number is at most the integer in the environment
+ * variable GPU_MAX_HW_QUEUES (the HIP runtime's own: hardware queues per process) within 1..32, or
+ * 4, HIP's default, where it is not set: the first ctr_create on a device keeps the streams
+ * that prove, in a trial with an empty kernel that waits (about 40 ms at 4 queues, 260 ms at 20),
+ * to be on queues of their own.  How many it found is what ctr_set_lane_limit with n = 0 returns:
+ * fewer than the queue count means a missed queue and a lower rate, never other results.  The library
+ * reads the variable once, when it makes the lanes of a device, and never sets it; it decides
+ * where a kernel is queued, never what it computes.  Every
+ * launch of a call goes, longest first by the duration measured in an earlier call of its plan, to
+ * the lane with the least work pending.  A call on the handle's own stream
+ * (hip_stream = NULL) is queued on the lanes alone; the stream itself is joined with the call when
+ * it is next named: by a *_device call on it, ctr_synchronize, ctr_stream_wait_engine.
  * CTR_FLAG_WINDOW_FILTER (NOT a scheduling flag): `noise_size` was given (refine.py:37 `if
  *   noise_size is not None`): the window goes through the reference's lowpass even where every
  *   sigma is 0 -- then that is its threshold alone, values <= threshold become 0
@@ -1704,8 +1715,16 @@ int32_t ctr_set_stage_max_grid(ctr_handle* h, int32_t max_grid);
  * without parking a stream in a device-side wait. */
 int ctr_query_done(ctr_handle* h);
 
-/* Block until the work queued by the *_device calls on `hip_stream` is done. */
+/* Block until the work queued by the *_device calls on `hip_stream` is done; NULL: the handle's
+ * own stream and the refine call that was last queued for it. */
 int ctr_synchronize(ctr_handle* h, void* hip_stream);
+
+/* Later ctr_refine_batch_device calls on `device` use only the first n lanes (see "Lanes" above);
+ * n within 1 .. the number of lanes, or 0 for all of them.  Returns the number in use before; -1,
+ * and nothing changes, for a value outside the range or a device on which no handle lives.  Work
+ * already queued stays where it is.  Results never depend on it: the suite runs the same calls on
+ * one lane, on two and on all. */
+int32_t ctr_set_lane_limit(int32_t device, int32_t n);
 
 /* The inbox of a multi-GPU pipeline (one process per GPU): the rank that collects the result rows
  * allocates a block on its device and exports it; every other rank maps it and passes addresses
@@ -1735,15 +1754,17 @@ int ctr_ipc_free(ctr_handle* h, void* dev_ptr);
  * (hip_stream = NULL above), without blocking the host.  `hip_stream` here is a hipStream_t
  * passed as void*; NULL means the legacy default stream (what PyTorch uses unless told
  * otherwise).
- *   ctr_engine_wait_stream: work queued later on the handle's stream starts only when
- *     everything queued so far on `hip_stream` has finished (inputs produced there).
+ *   ctr_engine_wait_stream: work queued later on the handle's stream -- the next refine call
+ *     for it included, whose kernels run on the lanes -- starts only when everything queued so
+ *     far on `hip_stream` has finished (inputs produced there).
  *   ctr_stream_wait_engine: work queued later on `hip_stream` starts only when everything
- *     queued so far on the handle's stream has finished (results consumed there). */
+ *     queued so far on the handle's stream, and the refine call last queued for it, has finished
+ *     (results consumed there). */
 int ctr_engine_wait_stream(ctr_handle* h, void* hip_stream);
 int ctr_stream_wait_engine(ctr_handle* h, void* hip_stream);
 
-/* Timing of the kernels of the last ctr_refine_batch_device call, measured
- * with HIP events on the launch stream (milliseconds); synchronises. */
+/* Timing of the kernels of the last ctr_refine_batch_device call, measured with HIP events at
+ * the start of the call, after its frame maxima and at its end (milliseconds); synchronises. */
 int ctr_last_kernel_ms(ctr_handle* h, double* frame_max_ms, double* refine_ms);
 
 #ifdef __cplusplus
