@@ -28,6 +28,8 @@ from .vanhove import vanhove_arrays, vanhove     # the function shadows the subm
 from . import static
 from .static import pair_correlation_arrays, pair_correlation, neighbors_arrays, neighbors, proximity
 from .twopoint import twopoint_arrays, twopoint   # the function shadows the submodule, as vanhove does
+from . import shape
+from .shape import (shape_arrays, shape_dynamics_arrays, shape_histogram_arrays, shape_names, shape_df, flexibility)
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -41,7 +43,9 @@ __all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', '
            'drift', 'compute_drift', 'subtract_drift', 'filter_stubs', 'compute_drift_arrays', 'subtract_drift_arrays',
            'filter_stubs_arrays', 'msd', 'msd_arrays', 'emsd_arrays', 'imsd', 'emsd',
            'vanhove_arrays', 'vanhove', 'static', 'pair_correlation_arrays', 'pair_correlation',
-           'neighbors_arrays', 'neighbors', 'proximity', 'twopoint_arrays', 'twopoint']
+           'neighbors_arrays', 'neighbors', 'proximity', 'twopoint_arrays', 'twopoint',
+           'shape', 'shape_arrays', 'shape_dynamics_arrays', 'shape_histogram_arrays', 'shape_names', 'shape_df',
+           'flexibility']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

@@ -396,6 +396,45 @@ class TwoPoint(C.Structure):
     ]
 
 
+SHAPE_MAX_COORDS, SHAPE_TILE, SHAPE_HALO_CAP = 19, 256, 768    # coordinates of a tetramer; the tiling of the dynamics
+SHAPE_MAX_BOND_BINS, SHAPE_MAX_ANGLE_BINS = 4096, 1024         # counters of a workgroup in LDS
+
+
+class Shape(C.Structure):
+    """``ctr_shape`` (include/ctrefine.h): the shape coordinates of tracked clusters."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('cluster_size', C.c_int32), ('n_tracks', C.c_int64), ('n_frames', C.c_int64),
+        ('mpp', C.c_double * MAX_NDIM),
+        ('pos', C.c_void_p), ('coords', C.c_void_p),
+    ]
+
+
+class ShapeDynamics(C.Structure):
+    """``ctr_shape_dynamics`` (include/ctrefine.h): displacement statistics and static moments of the
+    shape coordinates."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('cluster_size', C.c_int32), ('n_tracks', C.c_int64), ('n_frames', C.c_int64),
+        ('n_lags', C.c_int64), ('fps', C.c_double), ('mpp', C.c_double * MAX_NDIM),
+        ('lags', C.c_void_p), ('pos', C.c_void_p),
+        ('n', C.c_void_p), ('mean_d', C.c_void_p), ('mean_d2', C.c_void_p), ('mean_d4', C.c_void_p), ('flex', C.c_void_p),
+        ('pooled_n', C.c_void_p), ('pooled_mean_d', C.c_void_p), ('pooled_mean_d2', C.c_void_p),
+        ('pooled_mean_d4', C.c_void_p), ('pooled_flex', C.c_void_p),
+        ('count', C.c_void_p), ('mean', C.c_void_p), ('var', C.c_void_p), ('min', C.c_void_p), ('max', C.c_void_p),
+    ]
+
+
+class ShapeHistogram(C.Structure):
+    """``ctr_shape_histogram`` (include/ctrefine.h): the distributions of the shape coordinates."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('cluster_size', C.c_int32), ('per_track', C.c_int32), ('reserved0', C.c_int32),
+        ('n_tracks', C.c_int64), ('n_frames', C.c_int64), ('bond_bins', C.c_int64), ('angle_bins', C.c_int64),
+        ('bond_dr', C.c_double), ('angle_width', C.c_double), ('mpp', C.c_double * MAX_NDIM),
+        ('pos', C.c_void_p), ('bond_edges', C.c_void_p), ('angle_edges', C.c_void_p),
+        ('count_bond', C.c_void_p), ('above', C.c_void_p), ('count_angle', C.c_void_p), ('n', C.c_void_p),
+        ('density_bond', C.c_void_p), ('density_angle', C.c_void_p),
+    ]
+
+
 PREPARE_BATCH, PREPARE_SCATTER = 0, 1                         # ctr_refine_prepare.mode
 PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
 

@@ -65,6 +65,11 @@ SIGNATURES = {
     'ctr_pair_correlation_device': _stage(_abi.PairCorrelation),
     'ctr_neighbors_device': _stage(_abi.Neighbors),
     'ctr_twopoint_device': _stage(_abi.TwoPoint),
+    'ctr_shape_device': _stage(_abi.Shape),
+    'ctr_shape_dynamics_device': _stage(_abi.ShapeDynamics),
+    'ctr_shape_plan': (C.c_int, [_P(_abi.ShapeDynamics), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
+                                 _P(C.c_int64)]),
+    'ctr_shape_histogram_device': _stage(_abi.ShapeHistogram),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
     'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
@@ -180,6 +185,12 @@ def cluster_tracks_plan(desc):
     """``(scratch_bytes, max_rounds, jumps_per_round)`` of a ``ctr_cluster_tracks_device`` call
     (``ctr_cluster_tracks_plan``, no device needed); ``ValueError`` / ``NotImplementedError`` as the call itself."""
     return _plan('ctr_cluster_tracks_plan', desc, C.c_int64(), C.c_int32(), C.c_int32())
+
+
+def shape_plan(desc):
+    """The launch decision of ``ctr_shape_dynamics_device`` (``ctr_shape_plan``, no device needed):
+    ``(tile, halo, lds_bytes, n_tiles, scratch_bytes)``; ``ValueError`` as the call itself."""
+    return _plan('ctr_shape_plan', desc, C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64())
 
 
 def refine_prepare_plan(desc):
@@ -412,6 +423,9 @@ for _name, _symbol, _too_large in (
         ('pair_correlation_device', 'ctr_pair_correlation_device', False),
         ('neighbors_device', 'ctr_neighbors_device', False),
         ('twopoint_device', 'ctr_twopoint_device', False),
+        ('shape_device', 'ctr_shape_device', False),
+        ('shape_dynamics_device', 'ctr_shape_dynamics_device', False),
+        ('shape_histogram_device', 'ctr_shape_histogram_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 

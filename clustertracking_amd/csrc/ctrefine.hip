@@ -166,6 +166,7 @@ struct ctr_handle {
   Scratch pcf;     // ctr_pair_correlation_device: the work items of the frames, their partial weights
   Scratch nbr;     // ctr_neighbors_device: the work items of the frames, the keys of the particles
   Scratch twopt;   // ctr_twopoint_device: the work items of the frames, the partner's row of every row and lag
+  Scratch shape;   // ctr_shape_dynamics_device, ctr_shape_histogram_device: the coordinates of every frame, the partials of the tiles
   unsigned stage_max_grid = STAGE_MAX_GRID;   // run_stage: StageRun::max_grid (ctr_set_stage_max_grid)
 };
 
@@ -633,7 +634,7 @@ void ctr_destroy(ctr_handle* h) {
   // the last refine call, wherever its chains run, uses the handle's scratch until ev_done
   if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1366,6 +1367,33 @@ int ctr_neighbors_device(ctr_handle* h, const ctr_neighbors* d, void* hip_stream
 
 int ctr_twopoint_device(ctr_handle* h, const ctr_twopoint* d, void* hip_stream) {
   return run_stage("ctr_twopoint_device", h, &ctr_handle::twopt, d, hip_stream, ctr_twopoint_launch);
+}
+
+int ctr_shape_device(ctr_handle* h, const ctr_shape* s, void* hip_stream) {
+  return run_stage("ctr_shape_device", h, nullptr, s, hip_stream, ctr_shape_launch);
+}
+
+int ctr_shape_dynamics_device(ctr_handle* h, const ctr_shape_dynamics* d, void* hip_stream) {
+  return run_stage("ctr_shape_dynamics_device", h, &ctr_handle::shape, d, hip_stream, ctr_shape_dynamics_launch);
+}
+
+int ctr_shape_plan(const ctr_shape_dynamics* d, int32_t* tile, int32_t* halo, int64_t* lds_bytes, int64_t* n_tiles,
+                   int64_t* scratch_bytes) {
+  const char* msg = "";
+  ctr_shape_launch_plan plan = {};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
+  const int rc = ctr_shape_dynamics_launch(d, &run, &msg, &plan);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_shape_plan: ") + msg);
+  if (tile) *tile = plan.tile;
+  if (halo) *halo = plan.halo;
+  if (lds_bytes) *lds_bytes = plan.lds_bytes;
+  if (n_tiles) *n_tiles = plan.n_tiles;
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  return CTR_OK;
+}
+
+int ctr_shape_histogram_device(ctr_handle* h, const ctr_shape_histogram* d, void* hip_stream) {
+  return run_stage("ctr_shape_histogram_device", h, &ctr_handle::shape, d, hip_stream, ctr_shape_histogram_launch);
 }
 
 int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream) {

@@ -123,7 +123,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
 // tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd, tu_pair_corr,
-// tu_neighbors, tu_twopoint)
+// tu_neighbors, tu_twopoint, tu_shape)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -216,5 +216,15 @@ int ctr_neighbors_launch(const ctr_neighbors* d, StageRun* stage, const char** m
 // two-point displacement correlations of linked particles (twopoint_kernels.h; scratch: the first work
 // item of every frame and the partner's row of every row and lag)
 int ctr_twopoint_launch(const ctr_twopoint* d, StageRun* stage, const char** msg);
+// shape coordinates of tracked clusters (shape_kernels.h; scratch of the last two: the coordinates of
+// every frame, coordinate-major, and for the dynamics the sums per (track, tile, lag, coordinate) and per track):
+// the launch decision of the dynamics goes to *plan (may be null)
+struct ctr_shape_launch_plan {
+  int tile, halo;
+  long long lds_bytes, n_tiles, scratch_bytes;
+};
+int ctr_shape_launch(const ctr_shape* o, StageRun* stage, const char** msg);
+int ctr_shape_dynamics_launch(const ctr_shape_dynamics* d, StageRun* stage, const char** msg, ctr_shape_launch_plan* plan);
+int ctr_shape_histogram_launch(const ctr_shape_histogram* d, StageRun* stage, const char** msg);
 
 #endif  // CTREFINE_KARGS_H

@@ -1616,6 +1616,142 @@ typedef struct ctr_twopoint {
 } ctr_twopoint;
 int ctr_twopoint_device(ctr_handle* h, const ctr_twopoint* d, void* hip_stream);
 
+/* ---- shape coordinates of tracked clusters: bonds, angles, flexibility (ABI 8, additions) ----
+ * Everything ctr_orientation_device and ctr_diffusion_device report assumes that a tracked cluster is
+ * a rigid body: a basis is built from the features' positions, and every change of it is read as
+ * rotation.  These calls are the check of that assumption, and the plain measurement that comes with
+ * it (the bond length that constraints.dimer / trimer / tetramer need): the internal coordinates of
+ * every cluster in every frame, their distributions, and their displacement statistics over a sweep
+ * of lags.  The rule is this project's own; tests/_shape.py restates it with plain loops.  Input: the
+ * block `pos` [T, F, n, ndim] of ctr_track_positions_device, (z,) y, x, NaN where the cluster is not
+ * complete; n = cluster_size in {2, 3, 4}, ndim in {2, 3}; the 2D tetramer is accepted (no basis is
+ * needed).  No operation below is contracted to a fused multiply-add.
+ *   Rule 1, the coordinates of one (track, frame): C = NB + NA + 1 of them, in this order (C = 2, 7,
+ *     19 for n = 2, 3, 4).  x[i, a] = pos[i, a] * mpp[a], the product rounded on its own.
+ *     Bonds: NB = n (n - 1) / 2, the pairs a < b in lexicographic order (bond_ab): d = x[b] - x[a],
+ *       bond2 = sum over the axes, in axis order, of d * d, every product and sum rounded on its own;
+ *       bond = sqrt(bond2), correctly rounded.
+ *     Angles: NA = n (n - 1) (n - 2) / 2 (0, 3, 12): for the vertex a ascending, the pairs b < c of the
+ *       other features in lexicographic order (angle_a_bc): u = x[b] - x[a], v = x[c] - x[a], dot = sum
+ *       u_k v_k in axis order; in 2D cr = |u_0 v_1 - u_1 v_0|; in 3D cr = sqrt(c_0 c_0 + c_1 c_1 + c_2
+ *       c_2) with c = (u_1 v_2 - u_2 v_1, u_2 v_0 - u_0 v_2, u_0 v_1 - u_1 v_0), each component and each
+ *       square rounded on its own; angle = atan2(cr, dot) in [0, pi].  Coincident features give what
+ *       IEEE atan2 gives (0): no error.
+ *     Radius of gyration (rg, last): c_k = (sum_i x[i, k]) / n, features in order; rg = sqrt((sum_i
+ *       sum_k (x[i, k] - c_k)^2) / n), features outer, axes inner, correctly rounded.
+ *     Missing data: a frame with a non-finite x among its n ndim gives NaN in all C coordinates.
+ *   Rule 2, dynamics, per track t, coordinate c (value q) and lag k of lags[0 .. L - 1] (any integers;
+ *     k < 1 or k >= F has no row): the rows are the frames b with q[b] and q[b + k] both finite, d =
+ *     q[b + k] - q[b]; n[t, c, l] counts them (exact); mean_d, mean_d2, mean_d4 are the means of d, of
+ *     rn(d d) and of rn(rn(d d) rn(d d)); flex = ((mean_d2 * 0.5) * fps) / k, the scaling of
+ *     ctr_diffusion_device: the joint flexibility of an angle, the breathing diffusivity of a bond.
+ *     Where n == 0 the four are NaN.  Pooled over the tracks: pooled_n [C, L] and pooled_mean_d,
+ *     pooled_mean_d2, pooled_mean_d4, pooled_flex from the sums of the tracks added in track order.
+ *     (Slots follow the order of `particle`, so between tracks they are arbitrary: the counts and the
+ *     means are returned so that a caller can pool slots.)  Static moments per (t, c) over the frames
+ *     with a finite q: count, mean, var = mean((q - mean)^2) in two passes, min, max; NaN where count is 0.
+ *     Order of the sums: a workgroup per (track, tile of CTR_SHAPE_TILE = 256 frames) stages its tile
+ *     and a halo of frames behind it in LDS; the halo depends on F and C alone, never on the lags:
+ *     halo = min(max(F - 256, 0), min(CTR_SHAPE_HALO_CAP = 768, (8192 - 320) / C - 256)) (ctr_shape_plan);
+ *     a later frame beyond it is read from global memory: the same double.  Lane = frame of the tile; per
+ *     (coordinate, lag) the four sums go through one fixed wavefront tree, the four wavefronts are added
+ *     in their order, one partial per (track, tile, lag, coordinate); a second kernel adds the tiles in
+ *     tile order, a third the sums of the tracks in track order.  No float atomics: a (track, coordinate, lag) is
+ *     the same bytes alone, inside a batch of tracks, inside a sweep of lags, and on any stream.
+ *   Rule 3, distributions: bond bins B = bond_bins = ceil(bond_max / bond_dr), 1 <= B <=
+ *     CTR_SHAPE_MAX_BOND_BINS; bond_edges[b] = b * bond_dr, b = 0 .. B; angle bins A = angle_bins, 1 <=
+ *     A <= CTR_SHAPE_MAX_ANGLE_BINS, angle_edges = A + 1 equal steps from 0 to pi, angle_edges[A] the
+ *     double nearest pi; both computed by the caller and handed over.  A value v is in bin b iff
+ *     edges[b] <= v < edges[b + 1], decided by comparison with the edges (the device guesses with a
+ *     product); the last angle bin is closed at pi; bonds and rg at or above the last edge count in
+ *     `above`; a NaN is nowhere.  count_bond [NB + 1, B] (rg last), above [NB + 1], count_angle [NA, A],
+ *     n [1] = frames that entered (bond_01 is not NaN); with per_track a leading T on all four.  Counts
+ *     are int64 and exact; on every row count.sum() + above == n for finite coordinates.  density_bond =
+ *     count_bond / (n * bond_dr), density_angle = count_angle / (n * angle_width), angle_width = pi / A
+ *     as the caller rounds it; NaN where n == 0.
+ * Launches, 256 threads each.  shape_coords_kernel<ndim, n>: one lane per (track, frame), lanes along
+ * the frames; for ctr_shape_device it writes coords [T, F, C]; for the other two it writes the handle's
+ * scratch coordinate-major, [C][T F], so that every later read of a coordinate is contiguous along the
+ * frames, and trigonometry is done once per frame however many tiles stage it.  Dynamics:
+ * shape_partial_kernel, shape_final_kernel, shape_pool_kernel as above and shape_moments_kernel, a
+ * workgroup per (track, coordinate).  Histogram: shape_hist_kernel, a workgroup per (track or all,
+ * coordinate, chunk of 4096 frames) with uint32 counters in LDS and integer atomics on the int64
+ * tables, then shape_density_kernel.  Scratch of the handle: 8 C T F bytes, and for the dynamics 32 C L
+ * T (ceil(F / 256) + 1) bytes behind it: the partials, and the sums of every track that the pooling reads.  Calls of one handle that use it are ordered on the device.
+ * Descriptors are checked before the handle.  Device pointers, lags included; asynchronous. */
+#define CTR_SHAPE_MAX_COORDS 19
+#define CTR_SHAPE_TILE 256
+#define CTR_SHAPE_HALO_CAP 768
+#define CTR_SHAPE_MAX_BOND_BINS 4096
+#define CTR_SHAPE_MAX_ANGLE_BINS 1024
+typedef struct ctr_shape {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t cluster_size;            /* n: 2, 3 or 4 */
+  int64_t n_tracks;                /* T */
+  int64_t n_frames;                /* F */
+  double mpp[CTR_MAX_NDIM];        /* per axis, finite */
+  const double* pos;               /* [T, F, n, ndim] */
+  double* coords;                  /* [T, F, C] out */
+} ctr_shape;
+int ctr_shape_device(ctr_handle* h, const ctr_shape* s, void* hip_stream);
+
+typedef struct ctr_shape_dynamics {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t cluster_size;            /* n: 2, 3 or 4 */
+  int64_t n_tracks;                /* T */
+  int64_t n_frames;                /* F */
+  int64_t n_lags;                  /* L */
+  double fps;                      /* finite, > 0 */
+  double mpp[CTR_MAX_NDIM];        /* per axis, finite */
+  const int64_t* lags;             /* [L], device memory */
+  const double* pos;               /* [T, F, n, ndim] */
+  int64_t* n;                      /* [T, C, L] out */
+  double* mean_d;                  /* [T, C, L] out */
+  double* mean_d2;                 /* [T, C, L] out */
+  double* mean_d4;                 /* [T, C, L] out */
+  double* flex;                    /* [T, C, L] out */
+  int64_t* pooled_n;               /* [C, L] out */
+  double* pooled_mean_d;           /* [C, L] out */
+  double* pooled_mean_d2;          /* [C, L] out */
+  double* pooled_mean_d4;          /* [C, L] out */
+  double* pooled_flex;             /* [C, L] out */
+  int64_t* count;                  /* [T, C] out: frames with a finite coordinate */
+  double* mean;                    /* [T, C] out */
+  double* var;                     /* [T, C] out */
+  double* min;                     /* [T, C] out */
+  double* max;                     /* [T, C] out */
+} ctr_shape_dynamics;
+int ctr_shape_dynamics_device(ctr_handle* h, const ctr_shape_dynamics* d, void* hip_stream);
+/* No device needed: the launch decision of ctr_shape_dynamics_device from the scalars of d (its
+ * pointers are not looked at): the frames of a tile, the halo staged behind it, the dynamic LDS of a
+ * workgroup, the tiles of a track and the scratch of the call. */
+int ctr_shape_plan(const ctr_shape_dynamics* d, int32_t* tile, int32_t* halo, int64_t* lds_bytes, int64_t* n_tiles,
+                   int64_t* scratch_bytes);
+
+typedef struct ctr_shape_histogram {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t cluster_size;            /* n: 2, 3 or 4 */
+  int32_t per_track;               /* 0: all tracks in one table; 1: a leading T on the outputs */
+  int32_t reserved0;
+  int64_t n_tracks;                /* T */
+  int64_t n_frames;                /* F */
+  int64_t bond_bins;               /* B, 1 .. CTR_SHAPE_MAX_BOND_BINS */
+  int64_t angle_bins;              /* A, 1 .. CTR_SHAPE_MAX_ANGLE_BINS */
+  double bond_dr;                  /* finite, > 0 */
+  double angle_width;              /* pi / A as the caller rounds it */
+  double mpp[CTR_MAX_NDIM];        /* per axis, finite */
+  const double* pos;               /* [T, F, n, ndim] */
+  const double* bond_edges;        /* [B + 1] */
+  const double* angle_edges;       /* [A + 1] */
+  int64_t* count_bond;             /* [(T,) NB + 1, B] out */
+  int64_t* above;                  /* [(T,) NB + 1] out */
+  int64_t* count_angle;            /* [(T,) NA, A] out */
+  int64_t* n;                      /* [1] or [T] out */
+  double* density_bond;            /* [(T,) NB + 1, B] out */
+  double* density_angle;           /* [(T,) NA, A] out */
+} ctr_shape_histogram;
+int ctr_shape_histogram_device(ctr_handle* h, const ctr_shape_histogram* d, void* hip_stream);
+
 /* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
  * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
  * (find_clusters, the stable sort by (frame, cluster), FitFunctions.feature_bounds, the feasibility
