@@ -30,6 +30,7 @@ from .static import pair_correlation_arrays, pair_correlation, neighbors_arrays,
 from .twopoint import twopoint_arrays, twopoint   # the function shadows the submodule, as vanhove does
 from . import shape
 from .shape import (shape_arrays, shape_dynamics_arrays, shape_histogram_arrays, shape_names, shape_df, flexibility)
+from .residual import residual_arrays, residual   # the function shadows the submodule, as vanhove does
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -45,7 +46,7 @@ __all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', '
            'vanhove_arrays', 'vanhove', 'static', 'pair_correlation_arrays', 'pair_correlation',
            'neighbors_arrays', 'neighbors', 'proximity', 'twopoint_arrays', 'twopoint',
            'shape', 'shape_arrays', 'shape_dynamics_arrays', 'shape_histogram_arrays', 'shape_names', 'shape_df',
-           'flexibility']
+           'flexibility', 'residual_arrays', 'residual']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

@@ -435,6 +435,30 @@ class ShapeHistogram(C.Structure):
     ]
 
 
+RESID_CHUNK = 256                                              # rows of a chunk of the frame pass
+RESID_ZERO, RESID_NAN, RESID_IMAGE = 0, 1, 2                   # ctr_residual.outside
+RESID_OK, RESID_BAD_TABLE, RESID_BAD_CLUSTER = 0, 1, 2         # ctr_residual.status[0]
+INV_SERIES_MAX_PROFILE = 7                                     # profile parameters of inv_series_<N>: N + 1
+
+
+class Residual(C.Structure):
+    """``ctr_residual`` (include/ctrefine.h): model and residual frames of a fitted table."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('frame_dtype', C.c_int32), ('fit_function', C.c_int32), ('isotropic', C.c_int32),
+        ('n_profile', C.c_int32), ('outside', C.c_int32), ('want_frames', C.c_int32), ('want_model', C.c_int32),
+        ('has_cluster', C.c_int32), ('max_grid', C.c_int32),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64),
+        ('shape', C.c_int64 * MAX_NDIM), ('radius', C.c_int64 * MAX_NDIM),
+        ('frames', C.c_void_p), ('frame_offset', C.c_void_p), ('params', C.c_void_p), ('mask_pos', C.c_void_p),
+        ('cluster', C.c_void_p),
+        ('residual', C.c_void_p), ('model', C.c_void_p), ('coverage', C.c_void_p), ('owner', C.c_void_p),
+        ('n_pix', C.c_void_p), ('n_own', C.c_void_p), ('n_nan', C.c_void_p), ('sum', C.c_void_p), ('sum_sq', C.c_void_p),
+        ('own_sum_sq', C.c_void_p), ('max_abs', C.c_void_p), ('rms', C.c_void_p),
+        ('cluster_n_pix', C.c_void_p), ('cluster_sum_sq', C.c_void_p), ('cost', C.c_void_p),
+        ('status', C.c_void_p),
+    ]
+
+
 PREPARE_BATCH, PREPARE_SCATTER = 0, 1                         # ctr_refine_prepare.mode
 PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
 

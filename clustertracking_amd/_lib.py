@@ -3,6 +3,7 @@
 There is no CPU fallback: if the library is missing, or no MI355X is visible,
 the calls raise.
 """
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -70,6 +71,9 @@ SIGNATURES = {
     'ctr_shape_plan': (C.c_int, [_P(_abi.ShapeDynamics), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                  _P(C.c_int64)]),
     'ctr_shape_histogram_device': _stage(_abi.ShapeHistogram),
+    'ctr_residual_device': _stage(_abi.Residual),
+    'ctr_residual_plan': (C.c_int, [_P(_abi.Residual), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
+                                    _P(C.c_int64), _P(C.c_int64)]),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
     'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
@@ -191,6 +195,23 @@ def shape_plan(desc):
     """The launch decision of ``ctr_shape_dynamics_device`` (``ctr_shape_plan``, no device needed):
     ``(tile, halo, lds_bytes, n_tiles, scratch_bytes)``; ``ValueError`` as the call itself."""
     return _plan('ctr_shape_plan', desc, C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64())
+
+
+ResidualPlan = collections.namedtuple('ResidualPlan', 'tile chunk n_tiles grids lds_bytes scratch_bytes')
+
+
+def residual_plan(desc):
+    """The launch decision of ``ctr_residual_device`` (``ctr_residual_plan``, no device needed):
+    ``ResidualPlan(tile (3 ints), chunk, n_tiles, grids (check, frame, feature, cluster), lds_bytes,
+    scratch_bytes)``; ``ValueError`` / ``NotImplementedError`` as the call itself."""
+    lib = load()
+    tile, grids = (C.c_int32 * 3)(), (C.c_int64 * 4)()
+    chunk, n_tiles, lds, scratch = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+    rc = lib.ctr_residual_plan(C.byref(desc), tile, C.byref(chunk), C.byref(n_tiles), grids, C.byref(lds), C.byref(scratch))
+    if rc != _abi.OK:
+        msg = (lib.ctr_last_error(None) or b'').decode()
+        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
+    return ResidualPlan(tuple(tile), chunk.value, n_tiles.value, tuple(grids), lds.value, scratch.value)
 
 
 def refine_prepare_plan(desc):
@@ -426,6 +447,7 @@ for _name, _symbol, _too_large in (
         ('shape_device', 'ctr_shape_device', False),
         ('shape_dynamics_device', 'ctr_shape_dynamics_device', False),
         ('shape_histogram_device', 'ctr_shape_histogram_device', False),
+        ('residual_device', 'ctr_residual_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 

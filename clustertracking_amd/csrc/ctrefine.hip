@@ -167,6 +167,7 @@ struct ctr_handle {
   Scratch nbr;     // ctr_neighbors_device: the work items of the frames, the keys of the particles
   Scratch twopt;   // ctr_twopoint_device: the work items of the frames, the partner's row of every row and lag
   Scratch shape;   // ctr_shape_dynamics_device, ctr_shape_histogram_device: the coordinates of every frame, the partials of the tiles
+  Scratch resid;   // ctr_residual_device: the residual and owner of every pixel where the caller takes no frames, the frame maxima
   unsigned stage_max_grid = STAGE_MAX_GRID;   // run_stage: StageRun::max_grid (ctr_set_stage_max_grid)
 };
 
@@ -634,7 +635,7 @@ void ctr_destroy(ctr_handle* h) {
   // the last refine call, wherever its chains run, uses the handle's scratch until ev_done
   if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape, &h->resid}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1394,6 +1395,26 @@ int ctr_shape_plan(const ctr_shape_dynamics* d, int32_t* tile, int32_t* halo, in
 
 int ctr_shape_histogram_device(ctr_handle* h, const ctr_shape_histogram* d, void* hip_stream) {
   return run_stage("ctr_shape_histogram_device", h, &ctr_handle::shape, d, hip_stream, ctr_shape_histogram_launch);
+}
+
+int ctr_residual_device(ctr_handle* h, const ctr_residual* r, void* hip_stream) {
+  return run_stage("ctr_residual_device", h, &ctr_handle::resid, r, hip_stream, ctr_residual_launch);
+}
+
+int ctr_residual_plan(const ctr_residual* r, int32_t* tile, int32_t* chunk, int64_t* n_tiles, int64_t* grids,
+                      int64_t* lds_bytes, int64_t* scratch_bytes) {
+  const char* msg = "";
+  ctr_residual_launch_plan plan = {};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
+  const int rc = ctr_residual_launch(r, &run, &msg, &plan);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_residual_plan: ") + msg);
+  for (int d = 0; tile && d < 3; ++d) tile[d] = plan.tile[d];
+  if (chunk) *chunk = plan.chunk;
+  if (n_tiles) *n_tiles = plan.n_tiles;
+  for (int k = 0; grids && k < 4; ++k) grids[k] = plan.grids[k];
+  if (lds_bytes) *lds_bytes = plan.lds_bytes;
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  return CTR_OK;
 }
 
 int ctr_refine_prepare_device(ctr_handle* h, const ctr_refine_prepare* r, void* hip_stream) {

@@ -123,7 +123,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
 // tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd, tu_pair_corr,
-// tu_neighbors, tu_twopoint, tu_shape)
+// tu_neighbors, tu_twopoint, tu_shape, tu_residual)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -226,5 +226,13 @@ struct ctr_shape_launch_plan {
 int ctr_shape_launch(const ctr_shape* o, StageRun* stage, const char** msg);
 int ctr_shape_dynamics_launch(const ctr_shape_dynamics* d, StageRun* stage, const char** msg, ctr_shape_launch_plan* plan);
 int ctr_shape_histogram_launch(const ctr_shape_histogram* d, StageRun* stage, const char** msg);
+// model and residual frames of a fitted table (residual_kernels.h; scratch: the residual and owner of
+// every pixel where the caller does not take them, the frame maxima for the per-cluster cost): the
+// launch decision goes to *plan (may be null)
+struct ctr_residual_launch_plan {
+  int tile[3], chunk;
+  long long n_tiles, grids[4], lds_bytes, scratch_bytes;
+};
+int ctr_residual_launch(const ctr_residual* r, StageRun* stage, const char** msg, ctr_residual_launch_plan* plan);
 
 #endif  // CTREFINE_KARGS_H

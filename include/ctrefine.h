@@ -1752,6 +1752,121 @@ typedef struct ctr_shape_histogram {
 } ctr_shape_histogram;
 int ctr_shape_histogram_device(ctr_handle* h, const ctr_shape_histogram* d, void* hip_stream);
 
+/* ---- model and residual frames of a fitted table (ABI 8, additions) ----
+ * The step after ctr_refine_batch_device: the fitted model drawn back into the frames, the frames
+ * minus the model, and the goodness-of-fit sums per feature and per cluster by the rule of the
+ * reference's FitFunctions.get_residual (fitfunc.py:421-450).  Input: the frames [T, (z,) y, x] in
+ * any CTR_DTYPE_*, params [N, n_params] in the column order of a ctr_problem -- background, signal,
+ * <pos>, <size...>, <profile parameters> -- with the rows sorted by frame, frame_offset [T + 1], mask_pos
+ * [N, ndim] (the centres of the elliptical masks; NULL: the positions in params), cluster [N] (the
+ * smallest row of the row's cluster; NULL: no per-cluster output).  The residual is against the
+ * raw frame; constraints do not enter the model.  The rule is the project's own
+ * (tests/_residual.py restates it in NumPy with plain loops over the rows); no operation is
+ * contracted to a fused multiply-add.
+ *
+ * For pixel x of frame t and the rows i of that frame in ascending row order:
+ *   Covering.  Row i covers x when sum(((x - mask_pos_i) / radius)**2) <= 1, evaluated as NumPy
+ *     does: per axis a division, a product and a sum, in axis order, each rounded once; the edge is
+ *     included.  The box of a mask is clipped to the frame: a centre outside the frame covers
+ *     whatever part of its ellipse lies inside, a non-finite centre covers nothing.
+ *   Per-pixel maps.  coverage(x) is the number of covering rows (int32), owner(x) the lowest
+ *     covering row, or -1.
+ *   Term of a row.  term_i(x) = signal_i * g(r2_i(x)), with r2 and g as the refine kernels evaluate
+ *     them: d_a = x_a - pos_a, r2 = the sum over the axes, in axis order, of (d_a * d_a) * (1 / (size_a
+ *     * size_a)), every operation rounded on its own.  gauss: g = exp(-0.5 ndim r2).  ring (e =
+ *     thickness): r = sqrt(r2), num = r - 1 + e, g = exp(-0.5 ndim ((num / e) * (num / e))).  disc (e =
+ *     disc_size): e <= 0 the Gaussian; else ds = e, or 0.999 where e >= 1; g = 1 unless r2 > ds ds,
+ *     where u = (sqrt(r2) - ds) / (1 - ds), g = exp(u u ndim / -2).  inv_series_<N> (e[0 .. N]): g = e[0] / y,
+ *     y = polyval([1, e[1], ..., e[N]], r2) in Horner's order.  For ring and disc these are the
+ *     reference's r2_*_safe forms: where q = the sum of d_a d_a over the axes, last axis first, is
+ *     below 1, g is NaN (the disc with disc_size > 0 has the value 1 there, as the reference's
+ *     disc_func leaves it).
+ *   Residual.  residual(x) = ((image(x) - background_owner) - term_i1) - term_i2 ... over the covering
+ *     rows in ascending row order (fitfunc.py:443-448).
+ *   Model.  model(x) = background_owner + s, where s starts from 0 and takes the terms of the
+ *     covering rows in the same order.
+ *   Outside every mask.  outside decides the residual: 0.0 (CTR_RESID_ZERO), NaN (CTR_RESID_NAN) or
+ *     float64(image(x)) (CTR_RESID_IMAGE); model is 0.0, NaN or 0.0 respectively.
+ *   Per feature [N].  n_pix: covered pixels; n_own: pixels with owner == i; n_nan: covered pixels
+ *     whose residual is NaN; sum, sum_sq, max_abs: over its covered pixels whose residual is not NaN
+ *     (the reference's nansum; 0 where there is none); own_sum_sq: the same over its owned pixels;
+ *     rms = sqrt(sum_sq / n_pix), the divisor counting the NaN pixels as len(image) does there, NaN
+ *     for n_pix == 0.  Order of the sums: the pixels of the clipped box of the mask (every axis from
+ *     floor(max(c - radius - 1, 0)) to ceil(min(c + radius + 1, shape - 1))) are numbered in
+ *     row-major order; lane l of the feature's wavefront adds the pixels l, l + 64, ... in that order,
+ *     and the 64 lane sums are added by the butterfly x += x[lane ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.
+ *   Per cluster, only when cluster is given; per row [N], every row carrying its cluster's value.
+ *     cluster_n_pix = the sum of n_own over the rows of the cluster, cluster_sum_sq = the sum of
+ *     own_sum_sq, in ascending row order; cost = sqrt(cluster_sum_sq / cluster_n_pix) / max(frame_t),
+ *     the frame maximum of ctr_frame_max_device.  Where the masks of different clusters do not
+ *     overlap (always for separation >= diameter), cluster_sum_sq / cluster_n_pix is what
+ *     get_residual(..., norm=1.) returns for that cluster, and with mask_pos the last round's
+ *     centres cost is ctr_batch.cost.
+ * No float atomics; every output is the same bytes on every call, on every stream, and a frame's
+ * outputs do not depend on which other frames are in the call.
+ *
+ * status[0]: CTR_RESID_OK; CTR_RESID_BAD_TABLE for a frame_offset that does not rise from 0 to N
+ * (found by the first kernel; no other output is then written); CTR_RESID_BAD_CLUSTER for a cluster
+ * entry that is not a row c <= i of the row's frame with cluster[c] == c (those rows get 0, 0 and NaN).
+ *
+ * Launch (ctr_residual_plan).  Frame pass: a workgroup of 256 owns a tile of 8 x 32
+ * (2D) or 2 x 8 x 16 (3D) pixels of one frame, walks the rows of the frame in chunks of
+ * CTR_RESID_CHUNK through LDS in ascending row order, compacted to those whose clipped box meets
+ * the tile, and every pixel accumulates its terms in row order; a frame of any number of rows takes
+ * as many chunks as it needs.  Feature pass: one wavefront per row walks its clipped box and reads
+ * the residual and owner just written.  Cluster pass: a thread per row adds the rows of its cluster
+ * in its frame.  Every grid is capped (the handle's cap, ctr_set_stage_max_grid; max_grid > 0 lowers
+ * it further) and strides.  Scratch: the residual (8 B a pixel) and owner (4 B a pixel) where
+ * want_frames is 0, and 16 B a frame for the frame maxima where has_cluster is set. */
+#define CTR_RESID_CHUNK 256
+enum { CTR_RESID_ZERO = 0, CTR_RESID_NAN = 1, CTR_RESID_IMAGE = 2 };
+enum { CTR_RESID_OK = 0, CTR_RESID_BAD_TABLE = 1, CTR_RESID_BAD_CLUSTER = 2 };
+typedef struct ctr_residual {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t frame_dtype;             /* CTR_DTYPE_* */
+  int32_t fit_function;            /* CTR_FIT_* */
+  int32_t isotropic;               /* 1: one size column; 0: one per axis */
+  int32_t n_profile;               /* profile parameters: gauss 0, ring and disc 1, inv_series_<N> N + 1 */
+  int32_t outside;                 /* CTR_RESID_ZERO, _NAN or _IMAGE */
+  int32_t want_frames;             /* 1: residual, coverage and owner are outputs; 0: all three NULL */
+  int32_t want_model;              /* 1: model is an output; 0: NULL */
+  int32_t has_cluster;             /* 1: cluster and the three per-cluster outputs are given; 0: all NULL */
+  int32_t max_grid;                /* > 0: a cap on every grid below the handle's; 0: the handle's */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N < 2^31 - 1 */
+  int64_t shape[CTR_MAX_NDIM];     /* (z,) y, x of a frame */
+  int64_t radius[CTR_MAX_NDIM];    /* of the masks, 1 .. 1024 */
+  const void* frames;              /* [T, (z,) y, x] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const double* params;            /* [N, 2 + ndim + (isotropic ? 1 : ndim) + n_profile] */
+  const double* mask_pos;          /* [N, ndim] or NULL */
+  const int64_t* cluster;          /* [N] or NULL */
+  double* residual;                /* [T, (z,) y, x] out or NULL */
+  double* model;                   /* [T, (z,) y, x] out or NULL */
+  int32_t* coverage;               /* [T, (z,) y, x] out or NULL */
+  int32_t* owner;                  /* [T, (z,) y, x] out or NULL */
+  int64_t* n_pix;                  /* [N] out */
+  int64_t* n_own;                  /* [N] out */
+  int64_t* n_nan;                  /* [N] out */
+  double* sum;                     /* [N] out */
+  double* sum_sq;                  /* [N] out */
+  double* own_sum_sq;              /* [N] out */
+  double* max_abs;                 /* [N] out */
+  double* rms;                     /* [N] out */
+  int64_t* cluster_n_pix;          /* [N] out or NULL */
+  double* cluster_sum_sq;          /* [N] out or NULL */
+  double* cost;                    /* [N] out or NULL */
+  int32_t* status;                 /* [1] out */
+} ctr_residual;
+int ctr_residual_device(ctr_handle* h, const ctr_residual* r, void* hip_stream);
+/* No device needed: the launch decision of ctr_residual_device from the scalars of r (its pointers
+ * are not looked at) and the default cap of a handle: tile [3] the pixels of a tile per axis (1
+ * beyond ndim), chunk the rows of a chunk, n_tiles the tiles of the call, grids [4] the workgroups of
+ * the check, frame, feature and cluster kernels (0: not launched), lds_bytes the LDS of a workgroup
+ * of the frame pass, scratch_bytes the scratch of the call. */
+int ctr_residual_plan(const ctr_residual* r, int32_t* tile, int32_t* chunk, int64_t* n_tiles, int64_t* grids,
+                      int64_t* lds_bytes, int64_t* scratch_bytes);
+
 /* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
  * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
  * (find_clusters, the stable sort by (frame, cluster), FitFunctions.feature_bounds, the feasibility
