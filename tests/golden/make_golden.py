@@ -365,7 +365,47 @@ def main():
     imf = (im / 255.).astype(np.float32)
     save_case('dtype_f32', table(p0, 3., 0.35, 0.02, 2, True), imf[None],
               dict(diameter=13))
+    edge_windows()
+
+
+def edge_windows():
+    """Clusters whose window the frame clips, with intermediates (window origin and shape, mask
+    pixel counts): a pair at the low corner, ten features across the high corner and a 3D pair
+    in a stack thinner than the window.  ``python tests/golden/make_golden.py edge_windows``
+    writes these three alone."""
+    rng = np.random.RandomState(77)
+    # a pair 2-4 px inside the low corner (radius 6: origin 0 on both axes)
+    truth = np.array([[2.4, 3.7], [3.1, 9.9]])
+    im = np.zeros((48, 40), np.uint8)
+    for p in truth:
+        artificial.draw_gaussian(im, p, 3., 100)
+    im = artificial.add_poisson_noise(im, 4, rng)
+    p0 = truth + rng.uniform(-0.3, 0.3, truth.shape)
+    save_case('edge_pair_low_corner', table(p0, 3., 90., 2., 2, True), im[None], dict(diameter=13))
+    # ten touching features in the high corner of a 64 x 61 frame (radius 4), the outermost
+    # centres 1.3 px inside: the window is cut at both upper ends
+    shape = (64, 61)
+    grid = np.array([[i, j] for i in range(4) for j in range(4) if i + j < 4], float)   # 10 points
+    truth = np.asarray(shape) - 1 - 1.3 - 6. * grid + rng.uniform(-0.3, 0., grid.shape)
+    im = np.zeros(shape, np.uint8)
+    for p in truth:
+        artificial.draw_gaussian(im, p, 2., 120)
+    im = artificial.add_poisson_noise(im, 4, rng)
+    p0 = truth + rng.uniform(-0.25, 0.25, truth.shape)
+    save_case('edge_cluster10_high_corner', table(p0, 2., 110., 2., 2, True), im[None], dict(diameter=9))
+    # a 3D pair in a stack of 5 slices, thinner than the 7-slice window (radius 3, 4, 4)
+    truth = np.array([[2.2, 14.3, 12.8], [2.6, 15.1, 18.9]])
+    im = np.zeros((5, 32, 35), np.uint8)
+    for p in truth:
+        artificial.draw_feature(im, p, (1.5, 2., 2.), 120, 'gauss')
+    im = artificial.add_poisson_noise(im, 4, rng)
+    p0 = truth + rng.uniform(-0.2, 0.2, truth.shape)
+    save_case('edge_pair_3d_thin_stack', table(p0, (1.5, 2., 2.), 110., 2., 3, False), im[None],
+              dict(diameter=(7, 9, 9)))
 
 
 if __name__ == '__main__':
-    main()
+    if sys.argv[1:] == ['edge_windows']:
+        edge_windows()
+    else:
+        main()
