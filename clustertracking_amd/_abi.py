@@ -396,6 +396,33 @@ class TwoPoint(C.Structure):
     ]
 
 
+CON_COUNT, CON_FILL, CON_EPISODES = 0, 1, 2                   # ctr_contacts.phase
+CON_OK, CON_BAD_TABLE, CON_OVERFLOW = 0, 1, 2                  # status[0] of ctr_contacts_device
+CON_MAX_LIFETIME = 1 << 20                                     # ctr_contacts.max_lifetime at most
+
+
+class Contacts(C.Structure):
+    """``ctr_contacts`` (include/ctrefine.h): contact episodes and bond lifetimes of linked particles;
+    ``pairs`` takes the ``PCF_PAIRS_*`` codes."""
+    _fields_ = [
+        ('phase', C.c_int32), ('ndim', C.c_int32), ('pairs', C.c_int32), ('reserved0', C.c_int32),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_particles', C.c_int64), ('gap', C.c_int64),
+        ('max_lifetime', C.c_int64), ('max_entries', C.c_int64),
+        ('on2', C.c_double), ('off2', C.c_double), ('mpp', C.c_double * MAX_NDIM),
+        ('pos', C.c_void_p), ('frame_offset', C.c_void_p), ('particle', C.c_void_p), ('group', C.c_void_p),
+        ('entry_start', C.c_void_p), ('n_entries', C.c_void_p), ('first_seen', C.c_void_p), ('last_seen', C.c_void_p),
+        ('key', C.c_void_p), ('frame', C.c_void_p), ('d2', C.c_void_p),
+        ('a', C.c_void_p), ('b', C.c_void_p), ('first', C.c_void_p), ('last', C.c_void_p), ('lifetime', C.c_void_p),
+        ('n_seen', C.c_void_p), ('left_open', C.c_void_p), ('right_open', C.c_void_p), ('min_d2', C.c_void_p),
+        ('max_d2', C.c_void_p),
+        ('pair_a', C.c_void_p), ('pair_b', C.c_void_p), ('pair_episodes', C.c_void_p), ('pair_frames', C.c_void_p),
+        ('pair_first', C.c_void_p), ('pair_last', C.c_void_p),
+        ('formed', C.c_void_p), ('broken', C.c_void_p), ('active', C.c_void_p), ('lifetime_count', C.c_void_p),
+        ('lifetime_above', C.c_void_p), ('duplicates', C.c_void_p), ('n_episodes', C.c_void_p), ('n_pairs', C.c_void_p),
+        ('status', C.c_void_p),
+    ]
+
+
 SHAPE_MAX_COORDS, SHAPE_TILE, SHAPE_HALO_CAP = 19, 256, 768    # coordinates of a tetramer; the tiling of the dynamics
 SHAPE_MAX_BOND_BINS, SHAPE_MAX_ANGLE_BINS = 4096, 1024         # counters of a workgroup in LDS
 

@@ -74,6 +74,8 @@ SIGNATURES = {
     'ctr_residual_device': _stage(_abi.Residual),
     'ctr_residual_plan': (C.c_int, [_P(_abi.Residual), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                     _P(C.c_int64), _P(C.c_int64)]),
+    'ctr_contacts_device': _stage(_abi.Contacts),
+    'ctr_contacts_plan': (C.c_int, [_P(_abi.Contacts), _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
     'ctr_refine_prepare_plan': (C.c_int, [_P(_abi.RefinePrepare), _P(C.c_int64)]),
     'ctr_find_link_refine_device': (C.c_int, [_H, _P(_abi.FindLink), _P(_abi.RefineCom), _S]),
@@ -212,6 +214,22 @@ def residual_plan(desc):
         msg = (lib.ctr_last_error(None) or b'').decode()
         raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
     return ResidualPlan(tuple(tile), chunk.value, n_tiles.value, tuple(grids), lds.value, scratch.value)
+
+
+ContactsPlan = collections.namedtuple('ContactsPlan', 'scratch_bytes scan_tiles grids')
+
+
+def contacts_plan(desc):
+    """The launch decision of ``ctr_contacts_device`` (``ctr_contacts_plan``, no device needed):
+    ``ContactsPlan(scratch_bytes, scan_tiles (rows, entries), grids (check, walk, entries, chains))``;
+    ``ValueError`` as the call itself."""
+    lib = load()
+    scratch, tiles, grids = C.c_int64(), (C.c_int64 * 2)(), (C.c_int64 * 4)()
+    rc = lib.ctr_contacts_plan(C.byref(desc), C.byref(scratch), tiles, grids)
+    if rc != _abi.OK:
+        msg = (lib.ctr_last_error(None) or b'').decode()
+        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
+    return ContactsPlan(scratch.value, tuple(tiles), tuple(grids))
 
 
 def refine_prepare_plan(desc):
@@ -448,6 +466,7 @@ for _name, _symbol, _too_large in (
         ('shape_dynamics_device', 'ctr_shape_dynamics_device', False),
         ('shape_histogram_device', 'ctr_shape_histogram_device', False),
         ('residual_device', 'ctr_residual_device', False),
+        ('contacts_device', 'ctr_contacts_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 

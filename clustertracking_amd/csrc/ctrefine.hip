@@ -168,6 +168,7 @@ struct ctr_handle {
   Scratch twopt;   // ctr_twopoint_device: the work items of the frames, the partner's row of every row and lag
   Scratch shape;   // ctr_shape_dynamics_device, ctr_shape_histogram_device: the coordinates of every frame, the partials of the tiles
   Scratch resid;   // ctr_residual_device: the residual and owner of every pixel where the caller takes no frames, the frame maxima
+  Scratch contacts;  // ctr_contacts_device: the work items of the frames, the sums of the scan tiles, the chains, episodes and pairs of the entries
   unsigned stage_max_grid = STAGE_MAX_GRID;   // run_stage: StageRun::max_grid (ctr_set_stage_max_grid)
 };
 
@@ -635,7 +636,7 @@ void ctr_destroy(ctr_handle* h) {
   // the last refine call, wherever its chains run, uses the handle's scratch until ev_done
   if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape, &h->resid}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape, &h->resid, &h->contacts}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1414,6 +1415,22 @@ int ctr_residual_plan(const ctr_residual* r, int32_t* tile, int32_t* chunk, int6
   for (int k = 0; grids && k < 4; ++k) grids[k] = plan.grids[k];
   if (lds_bytes) *lds_bytes = plan.lds_bytes;
   if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  return CTR_OK;
+}
+
+int ctr_contacts_device(ctr_handle* h, const ctr_contacts* d, void* hip_stream) {
+  return run_stage("ctr_contacts_device", h, &ctr_handle::contacts, d, hip_stream, ctr_contacts_launch);
+}
+
+int ctr_contacts_plan(const ctr_contacts* d, int64_t* scratch_bytes, int64_t* scan_tiles, int64_t* grids) {
+  const char* msg = "";
+  ctr_contacts_launch_plan plan = {};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
+  const int rc = ctr_contacts_launch(d, &run, &msg, &plan);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_contacts_plan: ") + msg);
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  for (int k = 0; scan_tiles && k < 2; ++k) scan_tiles[k] = plan.scan_tiles[k];
+  for (int k = 0; grids && k < 4; ++k) grids[k] = plan.grids[k];
   return CTR_OK;
 }
 

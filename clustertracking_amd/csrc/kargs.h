@@ -123,7 +123,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
 // tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd, tu_pair_corr,
-// tu_neighbors, tu_twopoint, tu_shape, tu_residual)
+// tu_neighbors, tu_twopoint, tu_shape, tu_residual, tu_contacts)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -234,5 +234,12 @@ struct ctr_residual_launch_plan {
   long long n_tiles, grids[4], lds_bytes, scratch_bytes;
 };
 int ctr_residual_launch(const ctr_residual* r, StageRun* stage, const char** msg, ctr_residual_launch_plan* plan);
+// contact episodes and bond lifetimes of linked particles (contacts_kernels.h; scratch: the first work
+// item of every frame, the sums of the scan tiles, the difference array of `active`, and per entry of
+// max_entries the chains, their episodes and the pairs): the launch decision goes to *plan (may be null)
+struct ctr_contacts_launch_plan {
+  long long scratch_bytes, scan_tiles[2], grids[4];
+};
+int ctr_contacts_launch(const ctr_contacts* d, StageRun* stage, const char** msg, ctr_contacts_launch_plan* plan);
 
 #endif  // CTREFINE_KARGS_H

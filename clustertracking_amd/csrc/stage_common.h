@@ -1,6 +1,7 @@
 // stage_common.h -- what the stage units are made of: relaxed loads and stores, the ordered key of
-// a double, the workgroup scan, the check of a caller's frame_offset, the cluster labelling of a
-// frame, and on the host the grids, the error macro and the scratch carver.  Included inside the
+// a double, the workgroup scan, the scan over many workgroups, the check of a caller's
+// frame_offset, the cluster labelling of a frame, and on the host the grids, the error macro and
+// the scratch carver.  Included inside the
 // anonymous namespace of the units that use it, after device_common.h where that is included; only
 // label_frame needs it (scaled_dist2).
 #ifndef CTREFINE_STAGE_COMMON_H
@@ -72,6 +73,42 @@ __device__ __forceinline__ V workgroup_scan_n(long long n, Load load, Store stor
     carry += total;
   }
   return carry;
+}
+
+// Exclusive int64 scan of n values by any number of workgroups of THREADS, in three launches; the
+// kernel boundary is the only synchronisation, no workgroup waits on another.  A tile is THREADS
+// consecutive values, tiles are strided over the grid, and `sums` has a word per tile.
+// First launch, any grid: sums[tile] = the sum of load(i) over the tile.
+template <int THREADS, typename Load>
+__device__ __forceinline__ void grid_scan_sums(long long n, long long* sums, Load load) {
+  const long long tiles = (n + THREADS - 1) / THREADS;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long i = tile * THREADS + threadIdx.x;
+    long long total;
+    workgroup_scan<THREADS, long long>(i < n ? (long long)load(i) : 0LL, total);
+    if (threadIdx.x == 0) sums[tile] = total;
+  }
+}
+
+// Second launch, one workgroup: the exclusive scan of the tiles' sums, in place; returns the sum of
+// all n values, in every thread.
+template <int THREADS>
+__device__ __forceinline__ long long grid_scan_top(long long n, long long* sums) {
+  return workgroup_scan_n<THREADS, long long>(
+      (n + THREADS - 1) / THREADS, [&](long long k) { return sums[k]; }, [&](long long k, long long before) { sums[k] = before; });
+}
+
+// Third launch, any grid: store(i, sum of load(0 .. i - 1)) for every i < n.  load(i) and store(i)
+// belong to one thread, so a scan may replace its values.
+template <int THREADS, typename Load, typename Store>
+__device__ __forceinline__ void grid_scan_apply(long long n, const long long* sums, Load load, Store store) {
+  const long long tiles = (n + THREADS - 1) / THREADS;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long i = tile * THREADS + threadIdx.x;
+    long long total;
+    const long long before = workgroup_scan<THREADS, long long>(i < n ? (long long)load(i) : 0LL, total);
+    if (i < n) store(i, sums[tile] + before);
+  }
 }
 
 // ---- the caller's frame_offset, before an index is followed ---------------------------------

@@ -1616,6 +1616,150 @@ typedef struct ctr_twopoint {
 } ctr_twopoint;
 int ctr_twopoint_device(ctr_handle* h, const ctr_twopoint* d, void* hip_stream);
 
+/* ---- contact episodes and bond lifetimes of linked particles (ABI 8, additions) ----
+ * How long two particles stay together: g(r) above gives the bond length, the neighbours say how
+ * close rows come, the two-point correlations whether they move together; this is the quantity that
+ * separates a bonded cluster from a collision, the number that min_frames of
+ * ctr_cluster_tracks_device is compared with, and for self-assembling clusters the physics itself
+ * (association and dissociation rates, the survival curve of a bond).  Two knobs keep a lifetime
+ * from measuring the localisation noise and the dropout rate: a contact switches on below r_on and
+ * off at r_off >= r_on (a Schmitt trigger), and up to `gap` frames without the pair are bridged.
+ * The rule is the project's own; tests/_contacts.py restates it in NumPy.  Every output is an
+ * integer or a minimum / maximum of doubles: it equals the restatement exactly.
+ * Input: pos [N, ndim], ndim 2 or 3, rows sorted by frame; frame_offset [T + 1]; particle [N], ids
+ * below P, negative = unlinked; group [N] or null; mpp per axis, > 0; on2, off2, gap.
+ *   1. Inputs.  q = pos * mpp per axis, one rounding.  A row takes part when every coordinate of q is
+ *      finite and particle >= 0.
+ *   2. Thresholds.  r_on > 0, r_off >= r_on, in the units of pos * mpp; on2 = r_on * r_on and off2 =
+ *      r_off * r_off are computed once on the host.  gap is an integer >= 0.
+ *   3. Entries.  For every frame t and every ordered pair of rows (i, j) of that frame that take part,
+ *      with particle[i] < particle[j] and d2 < off2, there is an entry (a = particle[i], b =
+ *      particle[j], t, d2); d2 = the sum over the axes, in axis order, of (q_j - q_i)_a squared,
+ *      every product and sum rounded on its own.  CTR_PCF_PAIRS_SAME / _OTHER with group filter the
+ *      entries as in clause 6 of g(r).  The entries of row i are emitted in ascending j; entries lie
+ *      in (frame, i, j) order.  n_entries counts them.
+ *   4. Pair order.  The entries are sorted stably by key = a * P + b (P <= 2^31 - 1: below 2^62);
+ *      within a pair they stay in frame order.
+ *   5. Duplicates.  An entry with the key and the frame of the entry before it -- a particle repeated
+ *      in a frame -- is a duplicate: counted in `duplicates` and otherwise ignored; the first in
+ *      (frame, i, j) order counts.
+ *   6. Chains.  An entry that is no duplicate heads a chain when it is the first of its pair, or when
+ *      its frame exceeds the frame of the entry before it by more than gap + 1.  So up to `gap`
+ *      frames without an entry are bridged, whether one of the two was missing in them or the two
+ *      were r_off or more apart.
+ *   7. Episodes.  A chain holds at most one episode: it begins at the chain's first entry with d2 <
+ *      on2 and ends at the chain's last entry; a chain without such an entry has none.  Its fields:
+ *      a, b; first, last (frames); lifetime = last - first + 1; n_seen, the entries that are no
+ *      duplicates from the first on-entry on; min_d2, max_d2 over those.
+ *   8. Censoring.  first_seen[p], last_seen[p]: the first and last frame with a row of p that takes
+ *      part; T and -1 for a particle that never does.  An episode is left_open when its first
+ *      on-entry heads the chain and first - max(first_seen[a], first_seen[b]) <= gap; right_open when
+ *      min(last_seen[a], last_seen[b]) - last <= gap; complete when neither.
+ *   9. Series, int64 [T].  formed[first] += 1 for the episodes that are not left_open;
+ *      broken[last + 1] += 1 for those not right_open (last + 1 <= T - 1 by clause 8); active[t] =
+ *      the episodes with first <= t <= last.
+ *  10. Lifetimes.  lifetime_count [2, L]: row 0 the complete episodes, row 1 the open ones (either
+ *      side), at index lifetime - 1; lifetime_above [2]: those with lifetime > L.
+ *      count.sum() + above.sum() == n_episodes.
+ *  11. Pairs.  Episodes lie in (a, b, first) order.  Every pair with an episode has a row: pair_a,
+ *      pair_b, pair_episodes, pair_frames (the sum of its lifetimes), pair_first, pair_last; n_pairs
+ *      counts the rows.
+ *  12. A refused table.  A frame_offset that does not rise within [0, N] or a particle[i] >= P:
+ *      status[0] = CTR_CON_BAD_TABLE; counts, series and histogram 0, every column and first_seen /
+ *      last_seen -1, the doubles NaN; no kernel follows an index of a refused table.
+ *  13. Capacity.  Every per-entry, per-episode and per-pair buffer has max_entries rows.  n_entries >
+ *      max_entries: status[0] = CTR_CON_OVERFLOW, n_entries as counted, everything else as in 12.
+ *      Rows of the columns beyond n_episodes / n_pairs hold -1 and NaN.
+ * Three phases, each a call; the caller owns everything that passes from one to the next.
+ * CTR_CON_COUNT: cont_check; cont_count_defaults; cont_items (the scan of ceil(rows / 256) over the
+ * frames); cont_count: a work item is a frame and a tile of 256 of its rows, a thread owns a row, walks
+ * the frame's rows staged 256 at a time in LDS (the walk of g(r)), counts its entries into
+ * entry_start[i] and notes its frame in first_seen / last_seen with 64-bit integer atomic minima and
+ * maxima; then the exclusive scan of the N counts in place, entry_start[N] = n_entries.  A caller
+ * without a capacity reads that word here.  CTR_CON_FILL: cont_fill_defaults (the overflow, the key
+ * 2^63 - 1 in every slot without an entry); cont_items; cont_fill repeats the walk and writes key,
+ * frame and d2 of row i from entry_start[i] on: no atomic append.  Between FILL and EPISODES the
+ * caller sorts key stably and gathers frame and d2 by the permutation.  CTR_CON_EPISODES:
+ * cont_episode_defaults; the scan of the chain heads, which places the first entry of every chain;
+ * cont_chains, one chain per wavefront, the 64 lanes striding its entries, with shuffle reductions
+ * for the first on-entry, n_seen, the minimum and the maximum; the scan of the chains with an
+ * episode; cont_episodes, a thread per episode: its row, and integer atomics into formed, broken,
+ * the difference array of active and the histogram, one per distinct address among the lanes of a
+ * wavefront (the episodes of one lifetime share a bin); the scan of the pair heads; cont_pairs, one pair
+ * per wavefront; cont_active, one workgroup: the running sum of the difference array.  Every scan is
+ * three launches (cont_scan_sums: a sum per tile of 256 values; cont_scan_top: one workgroup over
+ * those; cont_scan_apply), so no workgroup waits on another.  256 threads each; integer atomics
+ * only: the same bytes on every call.
+ * Bytes that a call allocates per entry of max_entries: 20 for key, frame and d2 and 28 for their
+ * sorted copies and the permutation, 72 for the episode columns, 48 for the pair columns, 56 of the
+ * handle's scratch (the chains, their episodes, the pairs): 224 in all; besides, 8 (N + 1) for
+ * entry_start, 16 P, 24 T + 16 L, and of the scratch 16 (T + 1) + max(N, max_entries) / 32.
+ * Descriptors are checked before the handle.  Device pointers; asynchronous on `hip_stream`. */
+#define CTR_CON_COUNT 0              /* phase */
+#define CTR_CON_FILL 1
+#define CTR_CON_EPISODES 2
+#define CTR_CON_OK 0
+#define CTR_CON_BAD_TABLE 1
+#define CTR_CON_OVERFLOW 2
+#define CTR_CON_MAX_LIFETIME 1048576 /* 2^20: L at most */
+typedef struct ctr_contacts {
+  int32_t phase;                   /* CTR_CON_COUNT, _FILL, _EPISODES */
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t pairs;                   /* CTR_PCF_PAIRS_* */
+  int32_t reserved0;
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N */
+  int64_t n_particles;             /* P */
+  int64_t gap;                     /* 0 .. 2^31 - 1 */
+  int64_t max_lifetime;            /* L, 1 .. CTR_CON_MAX_LIFETIME (EPISODES) */
+  int64_t max_entries;             /* M >= 0: rows of every per-entry buffer (FILL, EPISODES) */
+  double on2;                      /* r_on squared, > 0 */
+  double off2;                     /* r_off squared, >= on2 */
+  double mpp[CTR_MAX_NDIM];        /* per axis, > 0 */
+  const double* pos;               /* [N, ndim] (COUNT, FILL) */
+  const int64_t* frame_offset;     /* [T + 1] (COUNT, FILL) */
+  const int64_t* particle;         /* [N] (COUNT, FILL) */
+  const int64_t* group;            /* [N], or null with CTR_PCF_PAIRS_ALL (COUNT, FILL) */
+  int64_t* entry_start;            /* [N + 1] COUNT out, FILL in */
+  int64_t* n_entries;              /* [1] COUNT out, FILL and EPISODES in */
+  int64_t* first_seen;             /* [P] COUNT out, EPISODES in */
+  int64_t* last_seen;              /* [P] COUNT out, EPISODES in */
+  int64_t* key;                    /* [M] FILL out; EPISODES in, sorted */
+  int32_t* frame;                  /* [M] FILL out; EPISODES in, in the order of key */
+  double* d2;                      /* [M] FILL out; EPISODES in, in the order of key */
+  int64_t* a;                      /* [M] episode columns, EPISODES out */
+  int64_t* b;
+  int64_t* first;
+  int64_t* last;
+  int64_t* lifetime;
+  int64_t* n_seen;
+  int32_t* left_open;              /* [M] 0 / 1 */
+  int32_t* right_open;
+  double* min_d2;
+  double* max_d2;
+  int64_t* pair_a;                 /* [M] pair columns, EPISODES out */
+  int64_t* pair_b;
+  int64_t* pair_episodes;
+  int64_t* pair_frames;
+  int64_t* pair_first;
+  int64_t* pair_last;
+  int64_t* formed;                 /* [T] EPISODES out */
+  int64_t* broken;                 /* [T] */
+  int64_t* active;                 /* [T] */
+  int64_t* lifetime_count;         /* [2, L] */
+  int64_t* lifetime_above;         /* [2] */
+  int64_t* duplicates;             /* [1] */
+  int64_t* n_episodes;             /* [1] */
+  int64_t* n_pairs;                /* [1] */
+  int32_t* status;                 /* [1] COUNT out; FILL in / out; EPISODES in */
+} ctr_contacts;
+int ctr_contacts_device(ctr_handle* h, const ctr_contacts* d, void* hip_stream);
+/* The launch decision of a call without a device: scratch_bytes of the handle; scan_tiles [2], the
+ * tiles of the scan over the N rows and over the max_entries entries; grids [4], the workgroups of
+ * cont_check, of the walks, of a kernel over the entries and of cont_chains, at the default cap of
+ * a grid.  Any of the pointers may be null. */
+int ctr_contacts_plan(const ctr_contacts* d, int64_t* scratch_bytes, int64_t* scan_tiles, int64_t* grids);
+
 /* ---- shape coordinates of tracked clusters: bonds, angles, flexibility (ABI 8, additions) ----
  * Everything ctr_orientation_device and ctr_diffusion_device report assumes that a tracked cluster is
  * a rigid body: a basis is built from the features' positions, and every change of it is read as
