@@ -32,6 +32,7 @@ from . import shape
 from .shape import (shape_arrays, shape_dynamics_arrays, shape_histogram_arrays, shape_names, shape_df, flexibility)
 from .residual import residual_arrays, residual   # the function shadows the submodule, as vanhove does
 from .contacts import contacts_arrays, contacts, bonds, contact_lifetimes   # the function shadows the submodule, as vanhove does
+from .fit_error import fit_error_arrays, fit_error   # the function shadows the submodule and carries distance_std
 
 link_df = link.link
 link_arrays = link.link_arrays
@@ -47,7 +48,8 @@ __all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', '
            'vanhove_arrays', 'vanhove', 'static', 'pair_correlation_arrays', 'pair_correlation',
            'neighbors_arrays', 'neighbors', 'proximity', 'twopoint_arrays', 'twopoint',
            'shape', 'shape_arrays', 'shape_dynamics_arrays', 'shape_histogram_arrays', 'shape_names', 'shape_df',
-           'flexibility', 'residual_arrays', 'residual', 'contacts_arrays', 'contacts', 'bonds', 'contact_lifetimes']
+           'flexibility', 'residual_arrays', 'residual', 'contacts_arrays', 'contacts', 'bonds', 'contact_lifetimes',
+           'fit_error_arrays', 'fit_error']
 
 logger = logging.getLogger(__name__)
 logger.addHandler(logging.NullHandler())

@@ -486,6 +486,28 @@ class Residual(C.Structure):
     ]
 
 
+FITERR_OK, FITERR_NOT_POSITIVE_DEFINITE, FITERR_NONFINITE, FITERR_EMPTY, FITERR_TOO_LARGE, FITERR_BAD_TABLE = range(6)   # ctr_fit_error.status
+FITERR_MAX_ROWS = 64                                           # rows of a cluster of ctr_fit_error_device
+FITERR_CLASSES = 3                                             # size classes of its launches
+
+
+class FitError(C.Structure):
+    """``ctr_fit_error`` (include/ctrefine.h): standard errors and covariance of a fitted table."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('frame_dtype', C.c_int32), ('fit_function', C.c_int32), ('isotropic', C.c_int32),
+        ('n_profile', C.c_int32), ('want_cov', C.c_int32), ('max_grid', C.c_int32), ('reserved0', C.c_int32),
+        ('modes', C.c_int32 * MAX_PARAMS),
+        ('n_frames', C.c_int64), ('n_features', C.c_int64), ('n_clusters', C.c_int64),
+        ('n_vars_total', C.c_int64), ('n_cov_total', C.c_int64),
+        ('shape', C.c_int64 * MAX_NDIM), ('radius', C.c_int64 * MAX_NDIM),
+        ('residual_factor', C.c_double),
+        ('frames', C.c_void_p), ('frame_offset', C.c_void_p), ('params', C.c_void_p), ('mask_pos', C.c_void_p),
+        ('order', C.c_void_p), ('cluster_offset', C.c_void_p), ('var_offset', C.c_void_p), ('cov_offset', C.c_void_p),
+        ('params_std', C.c_void_p), ('status', C.c_void_p), ('n_vars', C.c_void_p), ('n_pix', C.c_void_p),
+        ('cov', C.c_void_p), ('var_row', C.c_void_p), ('var_col', C.c_void_p),
+    ]
+
+
 PREPARE_BATCH, PREPARE_SCATTER = 0, 1                         # ctr_refine_prepare.mode
 PREPARE_OK, PREPARE_BAD_TABLE, PREPARE_INFEASIBLE = 0, 1, 2    # ctr_refine_prepare.status[0]
 

@@ -74,6 +74,9 @@ SIGNATURES = {
     'ctr_residual_device': _stage(_abi.Residual),
     'ctr_residual_plan': (C.c_int, [_P(_abi.Residual), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                     _P(C.c_int64), _P(C.c_int64)]),
+    'ctr_fit_error_device': _stage(_abi.FitError),
+    'ctr_fit_error_plan': (C.c_int, [_P(_abi.FitError), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
+                                     _P(C.c_int64)]),
     'ctr_contacts_device': _stage(_abi.Contacts),
     'ctr_contacts_plan': (C.c_int, [_P(_abi.Contacts), _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     'ctr_refine_prepare_device': _stage(_abi.RefinePrepare),
@@ -214,6 +217,24 @@ def residual_plan(desc):
         msg = (lib.ctr_last_error(None) or b'').decode()
         raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
     return ResidualPlan(tuple(tile), chunk.value, n_tiles.value, tuple(grids), lds.value, scratch.value)
+
+
+FitErrorPlan = collections.namedtuple('FitErrorPlan', 'max_vars chunk lds_bytes grid scratch_bytes')
+
+
+def fit_error_plan(desc):
+    """The launch decision of ``ctr_fit_error_device`` (``ctr_fit_error_plan``, no device needed):
+    ``FitErrorPlan(max_vars, chunk, lds_bytes (one entry per size class), grid, scratch_bytes)``;
+    ``ValueError`` / ``NotImplementedError`` as the call itself."""
+    lib = load()
+    k = _abi.FITERR_CLASSES
+    max_vars, chunk, lds = (C.c_int32 * k)(), (C.c_int32 * k)(), (C.c_int64 * k)()
+    grid, scratch = C.c_int64(), C.c_int64()
+    rc = lib.ctr_fit_error_plan(C.byref(desc), max_vars, chunk, lds, C.byref(grid), C.byref(scratch))
+    if rc != _abi.OK:
+        msg = (lib.ctr_last_error(None) or b'').decode()
+        raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
+    return FitErrorPlan(tuple(max_vars), tuple(chunk), tuple(lds), grid.value, scratch.value)
 
 
 ContactsPlan = collections.namedtuple('ContactsPlan', 'scratch_bytes scan_tiles grids')
@@ -467,6 +488,7 @@ for _name, _symbol, _too_large in (
         ('shape_histogram_device', 'ctr_shape_histogram_device', False),
         ('residual_device', 'ctr_residual_device', False),
         ('contacts_device', 'ctr_contacts_device', False),
+        ('fit_error_device', 'ctr_fit_error_device', False),
         ('refine_prepare_device', 'ctr_refine_prepare_device', False)):
     setattr(Engine, _name, _stage_method(_symbol, _too_large))
 

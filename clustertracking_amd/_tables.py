@@ -1,4 +1,4 @@
-"""The front-end of a table stage (``cluster_tracks``, ``drift``, ``msd``, ``vanhove``, ``static``, ``twopoint``, ``motion``, ``motion_ci``, ``shape``, ``residual``, ``contacts``):
+"""The front-end of a table stage (``cluster_tracks``, ``drift``, ``msd``, ``vanhove``, ``static``, ``twopoint``, ``motion``, ``motion_ci``, ``shape``, ``residual``, ``contacts``, ``fit_error``):
 the argument checks of a linked table, its placement on the device, the prologue and the tail of a
 call.  A stage module keeps its rule, its descriptor and its outputs; what two of them would spell
 alike lives here, and no stage module is imported.  Argument errors are raised before the engine is

@@ -169,6 +169,7 @@ struct ctr_handle {
   Scratch shape;   // ctr_shape_dynamics_device, ctr_shape_histogram_device: the coordinates of every frame, the partials of the tiles
   Scratch resid;   // ctr_residual_device: the residual and owner of every pixel where the caller takes no frames, the frame maxima
   Scratch contacts;  // ctr_contacts_device: the work items of the frames, the sums of the scan tiles, the chains, episodes and pairs of the entries
+  Scratch fiterr;  // ctr_fit_error_device: the word of the table check, the frame maxima
   unsigned stage_max_grid = STAGE_MAX_GRID;   // run_stage: StageRun::max_grid (ctr_set_stage_max_grid)
 };
 
@@ -636,7 +637,7 @@ void ctr_destroy(ctr_handle* h) {
   // the last refine call, wherever its chains run, uses the handle's scratch until ev_done
   if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape, &h->resid, &h->contacts}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape, &h->resid, &h->contacts, &h->fiterr}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1414,6 +1415,27 @@ int ctr_residual_plan(const ctr_residual* r, int32_t* tile, int32_t* chunk, int6
   if (n_tiles) *n_tiles = plan.n_tiles;
   for (int k = 0; grids && k < 4; ++k) grids[k] = plan.grids[k];
   if (lds_bytes) *lds_bytes = plan.lds_bytes;
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  return CTR_OK;
+}
+
+int ctr_fit_error_device(ctr_handle* h, const ctr_fit_error* e, void* hip_stream) {
+  return run_stage("ctr_fit_error_device", h, &ctr_handle::fiterr, e, hip_stream, ctr_fit_error_launch);
+}
+
+int ctr_fit_error_plan(const ctr_fit_error* e, int32_t* max_vars, int32_t* chunk, int64_t* lds_bytes, int64_t* grid,
+                       int64_t* scratch_bytes) {
+  const char* msg = "";
+  ctr_fit_error_launch_plan plan = {};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
+  const int rc = ctr_fit_error_launch(e, &run, &msg, &plan);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_fit_error_plan: ") + msg);
+  for (int k = 0; k < CTR_FITERR_CLASSES; ++k) {
+    if (max_vars) max_vars[k] = plan.max_vars[k];
+    if (chunk) chunk[k] = plan.chunk[k];
+    if (lds_bytes) lds_bytes[k] = plan.lds_bytes[k];
+  }
+  if (grid) *grid = plan.grid;
   if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
   return CTR_OK;
 }

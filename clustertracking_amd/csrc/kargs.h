@@ -123,7 +123,7 @@ KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpas
 int ctr_locate_launch(const ctr_locate* l, hipStream_t s, const char** msg);
 // The stage units (tu_characterize, tu_preprocess, tu_link, tu_motion, tu_motion_ci, tu_relocate, tu_findlink,
 // tu_refine_com, tu_train, tu_cluster_tracks, tu_refine_prepare, tu_drift, tu_msd, tu_pair_corr,
-// tu_neighbors, tu_twopoint, tu_shape, tu_residual, tu_contacts)
+// tu_neighbors, tu_twopoint, tu_shape, tu_residual, tu_contacts, tu_fit_error)
 // share one launch signature: ctr_<stage>_launch(descriptor, StageRun*, &msg, extras...).  Each
 // checks its descriptor, writes the scratch it needs into stage->scratch_bytes and, for
 // STAGE_LAUNCH, queues its whole pipeline on stage->stream.  CTR_OK or an error code with a static
@@ -241,5 +241,12 @@ struct ctr_contacts_launch_plan {
   long long scratch_bytes, scan_tiles[2], grids[4];
 };
 int ctr_contacts_launch(const ctr_contacts* d, StageRun* stage, const char** msg, ctr_contacts_launch_plan* plan);
+// standard errors and covariance of a fitted table (fit_error_kernels.h; scratch: the word that says
+// whether the tables were taken, the frame maxima): the launch decision goes to *plan (may be null)
+struct ctr_fit_error_launch_plan {
+  int max_vars[CTR_FITERR_CLASSES], chunk[CTR_FITERR_CLASSES];
+  long long lds_bytes[CTR_FITERR_CLASSES], grid, scratch_bytes;
+};
+int ctr_fit_error_launch(const ctr_fit_error* e, StageRun* stage, const char** msg, ctr_fit_error_launch_plan* plan);
 
 #endif  // CTREFINE_KARGS_H

@@ -172,7 +172,8 @@ typedef struct ctr_batch {
                                   definite.  Every parameter mode (second derivatives w.r.t.
                                   signal, centres and sizes).  NaN for clusters of the
                                   large-cluster path (> 64 features) and for the ring / disc /
-                                  inv_series profiles (the second derivatives are the gaussian's). */
+                                  inv_series profiles: their errors, and the covariance of any
+                                  cluster, come from the stage after the fit, ctr_fit_error_device. */
   double* result_rows;         /* [N, n_params + 1] or NULL: params_out and, last column, the cost of
                                   the row's cluster -- the rows of the result table (refine.py:426-427)
                                   in one block, written when the batch is done: what a pipeline sends
@@ -2010,6 +2011,122 @@ int ctr_residual_device(ctr_handle* h, const ctr_residual* r, void* hip_stream);
  * of the frame pass, scratch_bytes the scratch of the call. */
 int ctr_residual_plan(const ctr_residual* r, int32_t* tile, int32_t* chunk, int64_t* n_tiles, int64_t* grids,
                       int64_t* lds_bytes, int64_t* scratch_bytes);
+
+/* ---- standard errors and covariance of a fitted table (ABI 8, additions) ----
+ * The other step after ctr_refine_batch_device: how well every parameter is determined.  The exact
+ * Hessian of the reference's objective (FitFunctions.get_residual, fitfunc.py:421-450) at a fitted
+ * table, per cluster, for every profile, parameter mode and pixel type; from it the reference's
+ * sqrt(2 diag(inv H)) (refine.py:400-406) and, on request, the covariance of the cluster's
+ * variables.  Input: frames, params, frame_offset and mask_pos as ctr_residual takes them; order [N],
+ * the rows sorted by (frame, cluster label) with a stable sort; cluster_offset [C + 1], the ranges of
+ * the clusters in order.  The rule is the project's own (tests/_fit_error.py restates it in NumPy
+ * with plain loops); bounds and constraints do not enter, as in the reference.
+ *
+ *   Clusters.  A cluster is the set of rows of one frame with one value of `cluster`; the rows need
+ *     not be contiguous in the table; within a cluster the rows are taken in ascending row order.
+ *   Variables.  The layout is that of vect_from_params (fitfunc.py:207-263) for the modes of the
+ *     columns, in column order: a CTR_MODE_VAR column gives one variable per row, a
+ *     CTR_MODE_CLUSTER column one variable per cluster, a CTR_MODE_CONST column none;
+ *     CTR_MODE_GLOBAL is refused.  The background is CONST or CLUSTER.  The value of a cluster
+ *     variable is that of the cluster's first row where all its rows are equal (as
+ *     ctr_batch.params_out has them), else their sum in row order divided by their number; the
+ *     model reads that value for every row.  A constant background is that of the first row.
+ *   Pixels.  Covering, box clipping, r2, g and the NaN rule of the ring and disc "safe" forms are
+ *     ctr_residual's "Covering" and "Term of a row", with the values of the variables as above.
+ *     P is the number of pixels covered by at least one row of the cluster, NaN pixels included,
+ *     whatever other clusters cover.  A pixel whose residual is NaN enters no sum (the reference's
+ *     nansum).
+ *   Residual and Hessian.  res(x) = image(x) - background - sum_i signal_i g(r2_i(x), e_i) over the
+ *     covering rows of the cluster in row order.  F = sum res^2 / (P norm), norm = max(frame)^2 /
+ *     residual_factor (refine.py:354), the frame maximum of ctr_frame_max_device.  The Hessian of F
+ *     is 2 (J^T J + Q) / (P norm): J the Jacobian of res in the variables, Q = sum_x res(x)
+ *     d2res(x), exact in all variables -- signal, centres, sizes and every profile parameter.  With
+ *     m = s g(r2(c, size), e): m_ss = 0, m_sp = g' r2_p, m_se = g_e, m_pq = s (g'' r2_p r2_q + g'
+ *     r2_pq), m_pe = s g'_e r2_p, m_ee' = s g_ee' (p, q over centres and sizes, ' the derivative in
+ *     r2), and d2res = -d2m.  r2_c = -2 d / size^2, r2_size = -2 d^2 / size^3 (isotropic: -2 q /
+ *     size^3, q the sum of d^2), r2_cc = 2 / size^2, r2_c,size = 4 d / size^3, r2_size,size = 6 d^2
+ *     / size^4 (isotropic: 6 q / size^4), all others 0.  gauss (k = ndim / 2): g' = -k g, g'' = k^2 g.
+ *     ring and disc through r = sqrt(r2): g' = g_r / (2 r), g'' = g_rr / (4 r2) - g_r / (4 r^3), g'_e
+ *     = g_re / (2 r), with g = exp(phi), g_a = g phi_a, g_ab = g (phi_a phi_b + phi_ab); ring: phi =
+ *     -k w^2, w = (r - 1 + e) / e; disc: phi = -k u^2, u = (r - ds) / (1 - ds), in the region r2 <=
+ *     ds^2 g = 1 with all derivatives 0, the clamp disc_size >= 1 -> 0.999 has derivative 0 in
+ *     disc_size, disc_size <= 0 is the Gaussian.  inv_series: g = e0 / y, y the polynomial in r2; g'
+ *     = -e0 y' / y^2, g'' = e0 (2 y'^2 / y^3 - y'' / y^2), g_e0 = 1 / y, g_ek = -e0 r2^(N - k) / y^2,
+ *     g_e0,ek = -r2^(N - k) / y^2, g_ek,el = 2 e0 r2^(N - k) r2^(N - l) / y^3, g'_e0 = -y' / y^2, g'_ek
+ *     = -e0 ((N - k) r2^(N - k - 1) / y^2 - 2 y' r2^(N - k) / y^3).  Where the safe form makes the
+ *     disc's g 1 (q < 1, disc_size > 0) all derivatives are 0.  A feature's block in parameter space
+ *     is added to the rows and columns of the variables its parameters map to; a shared variable
+ *     collects every feature's block.
+ *   Result.  A = J^T J + Q is factored by Cholesky; a pivot that is not a positive finite number
+ *     makes the cluster CTR_FITERR_NOT_POSITIVE_DEFINITE.  Otherwise cov = P norm A^-1 and std_v =
+ *     sqrt(cov_vv).  params_std [N, n_params] is vect_to_params of std: a cluster variable's value
+ *     goes on every row of the cluster, a constant column is NaN, a failed cluster is all NaN.
+ *   Statuses, per cluster (every row carries its cluster's), as data and never as errors:
+ *     CTR_FITERR_OK; CTR_FITERR_NOT_POSITIVE_DEFINITE; CTR_FITERR_NONFINITE, a non-finite
+ *     parameter in a variable or in a value the model reads (a mask centre included);
+ *     CTR_FITERR_EMPTY, P == 0; CTR_FITERR_TOO_LARGE, more than 64 rows or more than CTR_MAX_VARS
+ *     variables (n_pix is then 0 and the cluster has no covariance block); CTR_FITERR_BAD_TABLE
+ *     on every row, when frame_offset, order, cluster_offset or the offsets of the covariance do
+ *     not fit together or a cluster's rows lie in more than one frame.
+ *   Order of the sums.  The covered pixels of a cluster are numbered by owner (the lowest covering
+ *     row of the cluster, in row order) and, within an owner, in row-major order of the clipped box
+ *     of its mask; every entry of J^T J adds the pixels in that order.  The block of a feature adds
+ *     the pixels of its box as ctr_residual's per-feature sums do (lane l the pixels l, l + 64, ...,
+ *     then the butterfly), and the blocks are added to A after J^T J in row order.  Cholesky and
+ *     the inverse take their terms in index order.
+ * No float atomics; every output is the same bytes on every call, on every stream, whatever else is
+ * in the batch.
+ *
+ * Launch (ctr_fit_error_plan).  One workgroup of 256 per cluster; the matrix lives in
+ * LDS as a packed triangle, and a cluster is taken by the launch of its size class (at most 16, 48
+ * or CTR_MAX_VARS variables), which sizes the LDS request.  Scratch: 16 B a frame for the frame
+ * maxima. */
+enum { CTR_FITERR_OK = 0, CTR_FITERR_NOT_POSITIVE_DEFINITE = 1, CTR_FITERR_NONFINITE = 2, CTR_FITERR_EMPTY = 3,
+       CTR_FITERR_TOO_LARGE = 4, CTR_FITERR_BAD_TABLE = 5 };
+#define CTR_FITERR_MAX_ROWS 64
+#define CTR_FITERR_CLASSES 3
+typedef struct ctr_fit_error {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t frame_dtype;             /* CTR_DTYPE_* */
+  int32_t fit_function;            /* CTR_FIT_* */
+  int32_t isotropic;               /* 1: one size column; 0: one per axis */
+  int32_t n_profile;               /* profile parameters: gauss 0, ring and disc 1, inv_series_<N> N + 1 */
+  int32_t want_cov;                /* 1: cov, var_row, var_col and their two offsets are given; 0: all NULL */
+  int32_t max_grid;                /* > 0: a cap on every grid below the handle's; 0: the handle's */
+  int32_t reserved0;
+  int32_t modes[CTR_MAX_PARAMS];   /* CTR_MODE_CONST, _VAR or _CLUSTER per column */
+  int64_t n_frames;                /* T */
+  int64_t n_features;              /* N < 2^31 - 1 */
+  int64_t n_clusters;              /* C */
+  int64_t n_vars_total;            /* entries of var_row and var_col (want_cov) */
+  int64_t n_cov_total;             /* entries of cov (want_cov) */
+  int64_t shape[CTR_MAX_NDIM];     /* (z,) y, x of a frame */
+  int64_t radius[CTR_MAX_NDIM];    /* of the masks, 1 .. 1024 */
+  double residual_factor;          /* > 0 (default 1e5) */
+  const void* frames;              /* [T, (z,) y, x] */
+  const int64_t* frame_offset;     /* [T + 1] */
+  const double* params;            /* [N, 2 + ndim + (isotropic ? 1 : ndim) + n_profile] */
+  const double* mask_pos;          /* [N, ndim] or NULL */
+  const int64_t* order;            /* [N] the rows sorted by (frame, cluster label), stable */
+  const int64_t* cluster_offset;   /* [C + 1] the clusters' ranges in order */
+  const int64_t* var_offset;       /* [C + 1] or NULL: the first variable of a cluster in var_row, var_col */
+  const int64_t* cov_offset;       /* [C + 1] or NULL: the first entry of a cluster's n_vars x n_vars block in cov */
+  double* params_std;              /* [N, n_params] out */
+  int32_t* status;                 /* [N] out: CTR_FITERR_* of the row's cluster */
+  int32_t* n_vars;                 /* [N] out: variables of the row's cluster */
+  int64_t* n_pix;                  /* [N] out: P of the row's cluster */
+  double* cov;                     /* [n_cov_total] out or NULL; NaN for a failed cluster */
+  int64_t* var_row;                /* [n_vars_total] out or NULL: the table row of a variable, -1 for a cluster variable */
+  int32_t* var_col;                /* [n_vars_total] out or NULL: its column */
+} ctr_fit_error;
+int ctr_fit_error_device(ctr_handle* h, const ctr_fit_error* e, void* hip_stream);
+/* No device needed: the launch decision of ctr_fit_error_device from the scalars of e (its pointers
+ * are not looked at) and the default cap of a handle: per size class (CTR_FITERR_CLASSES entries)
+ * max_vars the most variables it takes, chunk the pixel rows [J | res] it stages at once and
+ * lds_bytes its LDS request; grid the workgroups of a class's launch, scratch_bytes the scratch of
+ * the call. */
+int ctr_fit_error_plan(const ctr_fit_error* e, int32_t* max_vars, int32_t* chunk, int64_t* lds_bytes, int64_t* grid,
+                       int64_t* scratch_bytes);
 
 /* ---- refine from device tables: group, bound and lay out a batch (ABI 8, additions) ----
  * What refine_leastsq's host code does between the located features and ctr_refine_batch_device
