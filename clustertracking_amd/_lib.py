@@ -34,6 +34,7 @@ SIGNATURES = {
     'ctr_refine_batch': (C.c_int, [_H, _P(_abi.Problem), _P(_abi.Batch)]),
     'ctr_plan_create': (C.c_int, [_H, _P(_abi.Problem), C.c_int64, C.c_void_p, _P(C.c_void_p)]),
     'ctr_plan_destroy': (None, [C.c_void_p]),
+    'ctr_plan_tail': (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
     'ctr_refine_batch_device': (C.c_int, [_H, C.c_void_p, _P(_abi.Batch), _S]),
     'ctr_frame_max_device': (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, _S]),
     'ctr_synchronize': (C.c_int, [_H, _S]),
@@ -501,6 +502,16 @@ class Plan(object):
         if self._p:
             self._lib.ctr_plan_destroy(self._p)
             self._p = None
+
+    def tail(self):
+        """``ctr_plan_tail``: ``(fused, cap, tail_grid)`` -- whether the plan fits the likely slow
+        clusters of its pairs, 3-4-feature and 5-10-feature bins in one tail launch, the most
+        entries of a bin that launch takes, and its workgroups (0 if not fused)."""
+        fused, cap, grid = C.c_int32(), C.c_int32(), C.c_int32()
+        rc = self._lib.ctr_plan_tail(self._p, C.byref(fused), C.byref(cap), C.byref(grid))
+        if rc != _abi.OK:
+            raise ValueError("ctr_plan_tail: no plan (%d)" % rc)
+        return bool(fused.value), int(cap.value), int(grid.value)
 
     __del__ = close
 

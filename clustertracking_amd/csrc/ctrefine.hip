@@ -14,6 +14,8 @@
 //                         and contracted with v_mfma_f64_16x16x4_f64, partial accumulators meet
 //                         in LDS, register column-Cholesky (<= 31 variables) or cooperative LDS
 //                         Cholesky + range-space KKT step (constraints)
+//   refine_tail_kernel    CTR_FLAG_THROUGHPUT: the likely slow pairs and 3-10-feature clusters of a call
+//                         in one launch, each fitted by the statements of its bin's own kernel
 //   find_clusters_kernel  cluster labelling of a frame (find.py:72-93)
 // Clusters are binned by problem size on the host (ctr_plan_create); the bins run
 // concurrently on the lanes of the device (lane_sched.h).  gfx950 only; no CUDA paths, no CPU
@@ -65,9 +67,16 @@ constexpr int SLOT_SINGLES8 = 0, SLOT_SINGLES64 = 1, SLOT_PAIRS64 = 2, SLOT_PAIR
 // may run in two tiers (ctr_plan_create)
 constexpr int64_t NARROW_WINDOW = 600;
 constexpr int GATE_US = 20;  // head start of the block kernels over the small kernels (delay_kernel)
-// launches of a call that are chains of their own on the lanes: one per bin, and the bulk tier of
-// the pairs
-constexpr int LAUNCH_PAIRS16 = NBINS, NLAUNCH = NBINS + 1;
+// launches of a call that are chains of their own on the lanes: one per bin, the bulk tier of
+// the pairs, and the tail launch
+constexpr int LAUNCH_PAIRS16 = NBINS, LAUNCH_TAIL = NBINS + 1, NLAUNCH = NBINS + 2;
+// Most entries of a bin that the tail launch (tail_kernel.h) takes; the likely slow fits beyond it
+// stay with the bin's own launch.  It bounds the grid of a launch whose count is known on the
+// device only: the shards of the benchmark (cfg 2) have at most 110 such clusters in a bin, and
+// 3 * 256 workgroups that find nothing to do cost a few microseconds.
+constexpr int TAIL_CAP = 256;
+// the bins that a tail launch draws from, in the order of its segments (kargs.h: TailArgs)
+constexpr int TAIL_BINS[TAIL_SEGMENTS] = {BIN_SMALL2, 0, 1};
 
 // The duration of one launch of a plan, for the placement of its next call (lane_sched.h): a pair
 // of timing events around the kernel, read back without blocking once both have completed.  While
@@ -101,6 +110,10 @@ struct ctr_plan {
   // what the launch does besides, decided from the problem and the bin counts (ctr_plan_create)
   bool gate = false;          // the small kernels start GATE_US after the others (delay_kernel)
   bool pairs_split = false;   // the pairs bin runs in two tiers, 16 and 64 lanes per pair
+  // the likely slow fits of the pairs and of the block bins NT = 1, 2 run in one launch of
+  // refine_tail_kernel, of tail_grid workgroups
+  bool tail_fused = false;
+  int tail_grid = 0;
   int large_workgroups = 0;   // per large cluster, leader included
   // lowpass of the window (ctr_problem.noise_size): taps per axis on the device (kargs.h: lp_w)
   bool lowpass = false;
@@ -150,6 +163,8 @@ struct ctr_handle {
   // the kernel of every cell of the dispatch: [CTR_KFAM_*][ndim-2][iso][slot] (kernel_of); an
   // unreachable cell is null.  attr_set: its dynamic LDS limit is set (table_kernel)
   struct { KernelInfo k; bool attr_set; } kernels[NFAM][2][2][NSLOT] = {};
+  KernelInfo tail[2] = {};        // refine_tail_kernel by iso (2D); tail_attr_set: its dynamic LDS limit is set
+  bool tail_attr_set[2] = {false, false};
   hipEvent_t ev_done = nullptr;   // end of the last ctr_refine_batch_device call of this handle
   // ev_fork / ev_gate: the head chain of a call has prepared it / its small kernels may start;
   // ev_order: ctr_stream_wait_engine / ctr_engine_wait_stream; ev_own: what was queued
@@ -627,6 +642,7 @@ int ctr_create(ctr_handle** out, int device) {
     for (int di = 0; di < 2; ++di)
       for (int ii = 0; ii < 2; ++ii)
         for (int slot = 0; slot < NSLOT; ++slot) h->kernels[fam][di][ii][slot].k = kernel_of(fam, 2 + di, ii, slot);
+  for (int ii = 0; ii < 2; ++ii) h->tail[ii] = ctr_tail_kernel(2, ii);
   *out = h;
   return CTR_OK;
 }
@@ -702,6 +718,23 @@ int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
   // iteration, which is what the slow fits need; for the rest, four pairs per wavefront cost a
   // third of the machine time.
   plan->pairs_split = throughput && plan->bin_count[BIN_SMALL2] >= 64 && box_cap <= NARROW_WINDOW;
+  // One tail launch for the likely slow fits of the pairs and of the block bins NT = 1, 2
+  // (tail_kernel.h), where queue time is what counts (CTR_FLAG_THROUGHPUT) and at least two of
+  // them would otherwise hold a queue each.  Only the bins whose kernels the tail kernel holds:
+  // 2D, no lowpass, the throughput table of the gaussian.
+  {
+    int nonempty = 0;
+    bool family_ok = true;
+    for (int sgm = 0; sgm < TAIL_SEGMENTS; ++sgm) {
+      const int bin = TAIL_BINS[sgm];
+      if (plan->bin_count[bin] == 0) continue;
+      ++nonempty;
+      if (bin < MAXNT && plan->bin_family[bin] != CTR_KFAM_GAUSS_TP) family_ok = false;
+      plan->tail_grid += (int)std::min<int64_t>(plan->bin_count[bin], TAIL_CAP);
+    }
+    plan->tail_fused = throughput && p->ndim == 2 && !plan->lowpass && family_ok && nonempty >= 2;
+    if (!plan->tail_fused) plan->tail_grid = 0;
+  }
   if (plan->bin_count[BIN_LARGE] > 0) {
     // a leader workgroup of 512 threads per cluster + helpers for its pixel passes
     // (large_kernel.h): as many as fill the machine, none when the clusters alone do.
@@ -777,6 +810,14 @@ void ctr_plan_destroy(ctr_plan* plan) {
   delete plan;
 }
 
+int ctr_plan_tail(const ctr_plan* plan, int32_t* fused, int32_t* cap, int32_t* tail_grid) {
+  if (!plan) return CTR_ERR_INVALID;
+  if (fused) *fused = plan->tail_fused ? 1 : 0;
+  if (cap) *cap = TAIL_CAP;
+  if (tail_grid) *tail_grid = plan->tail_grid;
+  return CTR_OK;
+}
+
 int ctr_frame_max_device(ctr_handle* h, const void* frames, int32_t frame_dtype, int64_t n_frames,
                          int64_t frame_elems, double* out_max, void* hip_stream) {
   if (!h) return CTR_ERR_INVALID;
@@ -798,7 +839,7 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
   //           then frame maxima, counters and this call's order of the clusters; records ev_fork
   //           (and, after the delay of the gate, ev_gate)
   //   bins    one chain per kernel launch: waits for ev_fork (the small kernels for ev_gate),
-  //           runs the kernel
+  //           runs the kernel; the tail launch of a plan that has one is such a chain
   //   finish  waits for every bin chain, then result rows, done flag, ev_done
   // The bin chains go to the lanes of the device.  On a caller's stream the contract is stream
   // order: head and finish stay on that stream.  On the handle's own stream (hip_stream = NULL)
@@ -877,10 +918,44 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     if (rc) return rc;
     k.order = ord + plan->bin_begin[bin];
     k.n_bin = (int32_t)cnt;
+    // (with a tail launch, the workgroups of the entries it takes return at once)
+    const bool in_tail = plan->tail_fused && (bin == TAIL_BINS[1] || bin == TAIL_BINS[2]);
+    k.split = in_tail ? plan->d_front + 2 * bin : nullptr;
+    k.split_cap = in_tail ? TAIL_CAP : 0;
     guess(bin, lane_sched::CHAIN_BLOCK, cnt, bin < MAXNT ? bin + 1 : (bin == BIN_CONS2 ? 2 : 1));
     chains.push_back({bin, false, [k, ki, cnt](hipStream_t st) {
       void* kargs[] = {(void*)&k};
       return hipLaunchKernel(ki->fn, dim3((unsigned)cnt), dim3((unsigned)ki->threads), kargs, ki->smem, st);
+    }});
+    k.split = nullptr;
+    k.split_cap = 0;
+  }
+  // the tail launch: ungated, it carries workgroups with much LDS like the block kernels
+  if (plan->tail_fused) {
+    const KernelInfo* ki = &h->tail[ii];
+    if (!ki->fn) return fail(h, CTR_ERR_DEVICE, "no tail kernel instantiated for this problem");
+    if (!h->tail_attr_set[ii]) {
+      HIP_TRY(h, hipFuncSetAttribute(ki->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ki->smem));
+      h->tail_attr_set[ii] = true;
+    }
+    TailArgs ta;
+    std::memset(&ta, 0, sizeof ta);
+    ta.cap = TAIL_CAP;
+    for (int sgm = 0; sgm < TAIL_SEGMENTS; ++sgm) {
+      const int bin = TAIL_BINS[sgm];
+      const int64_t cnt = plan->bin_count[bin];
+      ta.close[sgm] = cnt > 0 ? plan->d_front + 2 * bin : nullptr;
+      ta.ord_off[sgm] = (int32_t)plan->bin_begin[bin];
+      ta.grid_begin[sgm + 1] = ta.grid_begin[sgm] + (int32_t)std::min<int64_t>(cnt, TAIL_CAP);
+    }
+    const unsigned grid = (unsigned)plan->tail_grid;
+    int* counter = h->d_counter + 4;
+    k.order = ord;
+    k.n_bin = 0;
+    guess(LAUNCH_TAIL, lane_sched::CHAIN_TAIL, (int64_t)grid, 1);
+    chains.push_back({LAUNCH_TAIL, false, [k, ki, ta, grid, counter](hipStream_t st) {
+      void* kargs[] = {(void*)&k, (void*)&ta, (void*)&counter};
+      return hipLaunchKernel(ki->fn, dim3(grid), dim3((unsigned)ki->threads), kargs, ki->smem, st);
     }});
   }
   if (plan->bin_count[BIN_LARGE] > 0) {
@@ -920,6 +995,18 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     k.order = ord + plan->bin_begin[BIN_SMALL2];
     k.n_bin = (int32_t)cnt;
     int64_t waves = cnt;   // (one wavefront per pair)
+    // With a tail launch the first min(close pairs, TAIL_CAP) entries are fitted there: the 64-lane
+    // launch takes the close pairs beyond the cap (two tiers) or beyond the cap and the far pairs (one).
+    bool launch64 = true;
+    if (plan->tail_fused) {
+      k.split = plan->d_front + 2 * BIN_SMALL2;
+      k.split_cap = TAIL_CAP;
+      k.split_part = 3;
+      if (plan->pairs_split) {
+        launch64 = cnt > TAIL_CAP;   // (else no close pair can be left over)
+        waves = std::max<int64_t>(cnt - TAIL_CAP, 1);
+      }
+    }
     if (plan->pairs_split) {
       // front_load_kernel has put the pairs closer than a quarter of the mask radius first and
       // counted them (on the device): the 64-lane kernel takes exactly those, the 16-lane kernel,
@@ -946,12 +1033,14 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     }
     if (waves > 8192) waves = 8192;
     guess(BIN_SMALL2, lane_sched::CHAIN_PAIRS64, cnt, 1);
-    chains.push_back({BIN_SMALL2, plan->gate, [k, ki, waves, counter](hipStream_t st) {
-      void* kargs[] = {(void*)&k, (void*)&counter};
-      return hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st);
-    }});
+    if (launch64)
+      chains.push_back({BIN_SMALL2, plan->gate, [k, ki, waves, counter](hipStream_t st) {
+        void* kargs[] = {(void*)&k, (void*)&counter};
+        return hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st);
+      }});
     k.split = nullptr;
     k.split_part = 0;
+    k.split_cap = 0;
   }
   if (plan->bin_count[BIN_SMALL1] > 0) {
     const int64_t cnt = plan->bin_count[BIN_SMALL1];

@@ -31,11 +31,14 @@ struct KArgs {
   double* params_std;    // [N, n_params] or nullptr (ctr_batch.params_std)
   const double* fmax;
   const int32_t* order;  // cluster ids of this bin
-  // small kernel only: part of the bin a launch takes.  split == nullptr: all of it;
-  // split_part 1: entries [0, *split) (the likely slow fits, front_load_kernel's count),
-  // split_part 2: entries [*split, n_bin)
+  // part of the bin a launch takes.  split == nullptr: all of it.  Else, with skip =
+  // min(*split, split_cap), the entries that refine_tail_kernel fits (0 without a tail launch):
+  // small kernel, split_part 1: entries [skip, *split) (the likely slow fits, front_load_kernel's
+  // count), split_part 2: entries [*split, n_bin), split_part 3: entries [skip, n_bin);
+  // block kernel: entries [skip, n_bin)
   const int32_t* split;
   int32_t split_part;
+  int32_t split_cap;
   // lowpass of the window (ctr_problem.noise_size): taps of axis a at lp_w[a * LP_STRIDE + 0 ..
   // 2 * lp_half[a]], normalised; an unfiltered axis has lp_half 0 and the single tap 1.
   // nullptr = no lowpass.  Only the LP instantiations of the block kernel read them.
@@ -47,6 +50,19 @@ struct KArgs {
 };
 
 constexpr int LP_STRIDE = 40;   // >= 2 * 16 + 1 taps (CTR_MAX_NOISE_SIZE = 4)
+
+// refine_tail_kernel (tail_kernel.h): the likely slow clusters of three bins of a call in one
+// launch.  Segment s -- 0: the pairs, 1 / 2: the block bins NT = 1 / 2 -- takes the workgroups
+// [grid_begin[s], grid_begin[s + 1]) and, of those, as many as min(*close[s], cap): the entries
+// order[ord_off[s] + 0 ..] that front_load_kernel has put first and counted.  An empty segment
+// has no workgroup and a null count.
+constexpr int TAIL_SEGMENTS = 3;
+struct TailArgs {
+  const int32_t* close[TAIL_SEGMENTS];
+  int32_t ord_off[TAIL_SEGMENTS];
+  int32_t grid_begin[TAIL_SEGMENTS + 1];
+  int32_t cap;
+};
 
 // a kernel of another translation unit: host-side handle for hipLaunchKernel /
 // hipFuncSetAttribute, dynamic LDS bytes and workgroup size
@@ -117,6 +133,8 @@ KernelInfo ctr_block_kernel_fit3d(int family, int ndim, int iso, int nt, int con
 KernelInfo ctr_block_kernel_inv(int family, int ndim, int iso, int nt, int cons);    // INV_SERIES
 // refine_small_kernel<ND, NF, ISO, SG>(KArgs, int* counter); nullptr if not instantiated
 const void* ctr_small_kernel(int ndim, int nf, int iso, int sg);
+// refine_tail_kernel<ND, ISO>(KArgs, TailArgs, int* counter); 2D only, {nullptr} otherwise
+KernelInfo ctr_tail_kernel(int ndim, int iso);
 KernelInfo ctr_large_kernel(int ndim, int iso, int lp);   // lp: with the lowpass of the window
 // feature location (tu_locate.hip, locate_kernels.h): checks the descriptor and queues the whole
 // pipeline on `s`.  CTR_OK or an error code with a static message in *msg.

@@ -32,7 +32,7 @@ inline int lanes_from_env(const char* text) {
 
 // ---- estimates ---------------------------------------------------------------------------------
 // what a chain runs: the guess of its duration before it has been measured depends on it
-enum ChainClass { CHAIN_HEAD, CHAIN_FINISH, CHAIN_SINGLES, CHAIN_PAIRS64, CHAIN_PAIRS16, CHAIN_BLOCK, CHAIN_LARGE, CHAIN_MARK };
+enum ChainClass { CHAIN_HEAD, CHAIN_FINISH, CHAIN_SINGLES, CHAIN_PAIRS64, CHAIN_PAIRS16, CHAIN_BLOCK, CHAIN_LARGE, CHAIN_MARK, CHAIN_TAIL };
 
 // milliseconds of a launch of `count` clusters, before its first measurement.  A bin lasts as long
 // as its slowest fit (the constant) plus its share of the machine (the slope); the orders of
@@ -49,6 +49,9 @@ inline double static_guess(ChainClass cls, long long count, int nt = 1) {
     case CHAIN_BLOCK: return (0.3 + 1e-3 * n) * std::max(nt, 1);
     case CHAIN_LARGE: return 2. + 1. * n;
     case CHAIN_MARK: return 0.01;
+    // (the tail launch lasts as long as the slowest fit of the call, 3 ms in cfg 2: by this guess it
+    // is placed before the bins it was taken from, as it is once it has been measured)
+    case CHAIN_TAIL: return 3. + 2e-3 * n;
   }
   return 0.01;
 }

@@ -1,0 +1,69 @@
+// tail_kernel.h -- refine_tail_kernel: the likely slow clusters of three bins in one launch
+// Part of the MI355X cluster-refinement engine; included by tu_tail.hip inside its anonymous
+// namespace, after block_kernel.h and small_kernel.h (device code only, gfx950).
+#ifndef CTREFINE_TAIL_KERNEL_H
+#define CTREFINE_TAIL_KERNEL_H
+
+// With CTR_FLAG_THROUGHPUT the step of many batches in flight is set by queue time:
+// a launch holds its hardware queue until its last workgroup ends, and the pairs, the 3-4-feature
+// and the 5-10-feature bins each end with a handful of clusters that iterate for milliseconds
+// while the machine is mostly idle.  Those clusters -- the ones front_load_kernel puts first in
+// their bins and counts -- run here instead, in one launch on one queue: the three tails overlap
+// and the bins' own launches become short.
+//
+// One workgroup of two wavefronts per entry; what a workgroup does is uniform over it (kargs.h:
+// TailArgs).  A cluster is fitted by the statements of its bin's own kernel, the same text with the
+// same template arguments (small_kernel_body.inc, block_kernel_body.inc):
+//   segment 0  pairs          refine_small_kernel<ND, 2, ISO, 64> on wavefront 0 (the other one leaves
+//                             before anything: that text has no workgroup barrier); the workgroups
+//                             of the segment pull the entries from a counter, as the bin's launch does
+//   segment 1  block, NT = 1  refine_block_kernel<ND, ISO, 1, 2, false>
+//   segment 2  block, NT = 2  refine_block_kernel<ND, ISO, 2, 2, false>
+// No workgroup waits for another one.  A workgroup beyond its segment's count -- the grid is laid
+// out for the cap, the count is known on the device only -- returns after a few scalar
+// instructions.  Occupancy does not matter for the few hundred workgroups of a call: one per SIMD
+// pair is asked for, whatever the three texts need in registers.
+template <int ND>
+struct SmemT {
+  static constexpr size_t b1 = SmemB<1, 2, false>::bytes, b2 = SmemB<2, 2, false>::bytes,
+                          bs = sizeof(double) * SmemS<ND, 2, 64>::total;
+  static constexpr size_t bytes = b1 > b2 ? (b1 > bs ? b1 : bs) : (b2 > bs ? b2 : bs);
+};
+
+template <int ND, bool ISO>
+__global__ void __launch_bounds__(2 * WAVE, 1) refine_tail_kernel(const KArgs k, const TailArgs t, int* __restrict__ counter) {
+  extern __shared__ double smem[];
+  const int b = (int)blockIdx.x;
+  const int seg = b >= t.grid_begin[2] ? 2 : (b >= t.grid_begin[1] ? 1 : 0);
+  // (selected, not indexed: the arguments stay in scalar registers)
+  const int32_t* close = seg == 2 ? t.close[2] : (seg == 1 ? t.close[1] : t.close[0]);
+  const int begin = seg == 2 ? t.grid_begin[2] : (seg == 1 ? t.grid_begin[1] : t.grid_begin[0]);
+  const int off = seg == 2 ? t.ord_off[2] : (seg == 1 ? t.ord_off[1] : t.ord_off[0]);
+  if (close == nullptr) return;
+  const int n_close = *close;
+  const int count = n_close < t.cap ? n_close : t.cap;
+  const int idx = b - begin;
+  if (idx >= count) return;
+  const int tid = (int)threadIdx.x;
+  if (seg == 0) {
+    if (tid >= WAVE) return;
+    constexpr int NF = 2, SG = 64;
+    const int lane = tid;
+    double* const lds = smem;
+    const int32_t* const order = k.order + off;
+    const int id_begin = 0, id_end = count;
+#include "small_kernel_body.inc"
+  } else if (seg == 1) {
+    constexpr int NT = 1, W = 2, FIT = CTR_FIT_GAUSS;
+    constexpr bool CONS = false, LP = false;
+    const int cl = k.order[off + idx];
+#include "block_kernel_body.inc"
+  } else {
+    constexpr int NT = 2, W = 2, FIT = CTR_FIT_GAUSS;
+    constexpr bool CONS = false, LP = false;
+    const int cl = k.order[off + idx];
+#include "block_kernel_body.inc"
+  }
+}
+
+#endif  // CTREFINE_TAIL_KERNEL_H

@@ -257,6 +257,17 @@ int ctr_refine_batch(ctr_handle* h, const ctr_problem* p, const ctr_batch* b);
 int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
                     const int32_t* feat_offset_host, ctr_plan** out);
 void ctr_plan_destroy(ctr_plan* plan);
+/* The tail launch of a plan (needs no device beyond the plan's own).  With CTR_FLAG_THROUGHPUT, in
+ * 2D, without a lowpass and with the gaussian profile, a plan with at least two non-empty bins
+ * among the pairs, the 3-4-feature and the 5-10-feature clusters (block kernel, nt = 1, 2; counts
+ * for the default parameter modes) fits the likely slow clusters of those bins -- two features
+ * closer than a quarter of the mask radius, or more than 8 features -- in one launch of their own,
+ * at most `cap` per bin; every cluster is fitted by the same kernel code as without it, the results
+ * are the same bits.  fused: 1 if the plan does so; cap: that bound (the same for every plan);
+ * tail_grid: workgroups of the launch, the sum over the three bins of min(clusters, cap), 0 if not
+ * fused.  Any of the pointers may be null.  Added in ABI 8 without a version change: it changes no
+ * existing struct or call. */
+int ctr_plan_tail(const ctr_plan* plan, int32_t* fused, int32_t* cap, int32_t* tail_grid);
 int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan,
                             const ctr_batch* b_device, void* hip_stream);
 
