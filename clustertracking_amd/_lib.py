@@ -35,6 +35,8 @@ SIGNATURES = {
     'ctr_plan_create': (C.c_int, [_H, _P(_abi.Problem), C.c_int64, C.c_void_p, _P(C.c_void_p)]),
     'ctr_plan_destroy': (None, [C.c_void_p]),
     'ctr_plan_tail': (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    'ctr_plan_tail_bins': (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32)]),
+    'ctr_set_tail_absorb': (C.c_int32, [_H, C.c_int32]),
     'ctr_refine_batch_device': (C.c_int, [_H, C.c_void_p, _P(_abi.Batch), _S]),
     'ctr_frame_max_device': (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, _S]),
     'ctr_synchronize': (C.c_int, [_H, _S]),
@@ -312,6 +314,12 @@ class Engine(object):
                     'ctr_plan_create')
         return Plan(self._lib, plan)
 
+    def set_tail_absorb(self, max_count):
+        """``ctr_set_tail_absorb``: the most clusters of a 3-4- or 5-10-feature bin that the tail
+        launch of a plan made from now on fits whole (0: never); returns the previous value.  A
+        negative ``max_count`` only asks."""
+        return int(self._lib.ctr_set_tail_absorb(self._h, int(max_count)))
+
     def refine_batch_device(self, plan, batch_struct, stream=None):
         self._check(self._lib.ctr_refine_batch_device(
             self._h, plan._p, C.byref(batch_struct), C.c_void_p(stream or 0)),
@@ -512,6 +520,16 @@ class Plan(object):
         if rc != _abi.OK:
             raise ValueError("ctr_plan_tail: no plan (%d)" % rc)
         return bool(fused.value), int(cap.value), int(grid.value)
+
+    def tail_bins(self):
+        """``ctr_plan_tail_bins``: ``(absorbed, own_launch)``, each three booleans -- pairs,
+        3-4-feature, 5-10-feature bin: whether the tail launch fits the whole bin, and whether
+        the bin's own launch (pairs: the 64-lane one) is queued."""
+        absorbed, own = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        rc = self._lib.ctr_plan_tail_bins(self._p, absorbed, own)
+        if rc != _abi.OK:
+            raise ValueError("ctr_plan_tail_bins: no plan (%d)" % rc)
+        return tuple(bool(v) for v in absorbed), tuple(bool(v) for v in own)
 
     __del__ = close
 

@@ -70,11 +70,21 @@ constexpr int GATE_US = 20;  // head start of the block kernels over the small k
 // launches of a call that are chains of their own on the lanes: one per bin, the bulk tier of
 // the pairs, and the tail launch
 constexpr int LAUNCH_PAIRS16 = NBINS, LAUNCH_TAIL = NBINS + 1, NLAUNCH = NBINS + 2;
-// Most entries of a bin that the tail launch (tail_kernel.h) takes; the likely slow fits beyond it
-// stay with the bin's own launch.  It bounds the grid of a launch whose count is known on the
-// device only: the shards of the benchmark (cfg 2) have at most 110 such clusters in a bin, and
-// 3 * 256 workgroups that find nothing to do cost a few microseconds.
+// Most workgroups that a bin has in the tail launch (tail_kernel.h).  They share the bin's entries
+// of that launch, however many, through a counter.  It bounds the grid of a launch whose count is
+// known on the device only: the shards of the benchmark (cfg 2) have at most 110 likely slow
+// clusters in a bin, and 3 * 256 workgroups that find nothing to do cost a few microseconds.
 constexpr int TAIL_CAP = 256;
+// A block bin (NT = 1, 2) of at most this many clusters is fitted whole by the tail launch and has
+// no launch of its own: its workgroups would run no faster there, and the launch would hold a
+// queue as long as the bin's slowest far cluster.  The default of ctr_set_tail_absorb, fixed by
+// measurement (profiles/tail_absorb_sweep.json): a bin of 6 440 3-4-feature
+// clusters still gains from it, and at about 32 fits of 5-10 features per workgroup the tail
+// launch would begin to outlast the slow fits it exists for.
+constexpr int TAIL_ABSORB = 32 * TAIL_CAP;
+// One tier of pairs (fewer than 64, or wide windows) is fitted whole by the tail launch up to this
+// many: beyond it a bin of wide-window pairs is no work for TAIL_CAP wavefronts.
+constexpr int TAIL_PAIRS_WHOLE = 8 * TAIL_CAP;
 // the bins that a tail launch draws from, in the order of its segments (kargs.h: TailArgs)
 constexpr int TAIL_BINS[TAIL_SEGMENTS] = {BIN_SMALL2, 0, 1};
 
@@ -114,6 +124,10 @@ struct ctr_plan {
   // refine_tail_kernel, of tail_grid workgroups
   bool tail_fused = false;
   int tail_grid = 0;
+  // per segment of a fused plan (kargs.h: TailArgs): the tail launch fits the whole bin / the bin's
+  // own launch (pairs: the 64-lane one) is queued.  Not fused: none whole, every non-empty bin its own
+  bool tail_whole[TAIL_SEGMENTS] = {false, false, false};
+  bool tail_own[TAIL_SEGMENTS] = {false, false, false};
   int large_workgroups = 0;   // per large cluster, leader included
   // lowpass of the window (ctr_problem.noise_size): taps per axis on the device (kargs.h: lp_w)
   bool lowpass = false;
@@ -165,6 +179,7 @@ struct ctr_handle {
   struct { KernelInfo k; bool attr_set; } kernels[NFAM][2][2][NSLOT] = {};
   KernelInfo tail[2] = {};        // refine_tail_kernel by iso (2D); tail_attr_set: its dynamic LDS limit is set
   bool tail_attr_set[2] = {false, false};
+  int32_t tail_absorb = TAIL_ABSORB;   // ctr_set_tail_absorb: for the plans made from now on
   hipEvent_t ev_done = nullptr;   // end of the last ctr_refine_batch_device call of this handle
   // ev_fork / ev_gate: the head chain of a call has prepared it / its small kernels may start;
   // ev_order: ctr_stream_wait_engine / ctr_engine_wait_stream; ev_own: what was queued
@@ -734,6 +749,19 @@ int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
     }
     plan->tail_fused = throughput && p->ndim == 2 && !plan->lowpass && family_ok && nonempty >= 2;
     if (!plan->tail_fused) plan->tail_grid = 0;
+    // What the tail launch takes of a bin, and whether the bin keeps a launch of its own.  Pairs:
+    // every pair of the 64-lane tier -- the close ones with two tiers, all of them with one -- so
+    // that launch is never queued.  (One tier is for fewer than 64 pairs or wide windows; a bin of
+    // more than TAIL_PAIRS_WHOLE wide-window pairs is no work for TAIL_CAP wavefronts and keeps its
+    // launch for all but the close ones, whatever the handle's setting.)  A block bin of at most
+    // tail_absorb clusters: all of it; a larger one: the close clusters, the bin's launch fits the
+    // others.
+    for (int sgm = 0; sgm < TAIL_SEGMENTS; ++sgm) {
+      const int64_t cnt = plan->bin_count[TAIL_BINS[sgm]];
+      const bool whole = sgm == 0 ? !plan->pairs_split && cnt <= TAIL_PAIRS_WHOLE : cnt <= (int64_t)h->tail_absorb;
+      plan->tail_whole[sgm] = plan->tail_fused && cnt > 0 && whole;
+      plan->tail_own[sgm] = cnt > 0 && !(plan->tail_fused && (whole || (sgm == 0 && plan->pairs_split)));
+    }
   }
   if (plan->bin_count[BIN_LARGE] > 0) {
     // a leader workgroup of 512 threads per cluster + helpers for its pixel passes
@@ -816,6 +844,22 @@ int ctr_plan_tail(const ctr_plan* plan, int32_t* fused, int32_t* cap, int32_t* t
   if (cap) *cap = TAIL_CAP;
   if (tail_grid) *tail_grid = plan->tail_grid;
   return CTR_OK;
+}
+
+int ctr_plan_tail_bins(const ctr_plan* plan, int32_t* absorbed, int32_t* own_launch) {
+  if (!plan) return CTR_ERR_INVALID;
+  for (int sgm = 0; sgm < TAIL_SEGMENTS; ++sgm) {
+    if (absorbed) absorbed[sgm] = plan->tail_whole[sgm] ? 1 : 0;
+    if (own_launch) own_launch[sgm] = plan->tail_own[sgm] ? 1 : 0;
+  }
+  return CTR_OK;
+}
+
+int32_t ctr_set_tail_absorb(ctr_handle* h, int32_t max_count) {
+  if (!h) return -1;
+  const int32_t before = h->tail_absorb;
+  if (max_count >= 0) h->tail_absorb = max_count;
+  return before;
 }
 
 int ctr_frame_max_device(ctr_handle* h, const void* frames, int32_t frame_dtype, int64_t n_frames,
@@ -918,10 +962,12 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     if (rc) return rc;
     k.order = ord + plan->bin_begin[bin];
     k.n_bin = (int32_t)cnt;
-    // (with a tail launch, the workgroups of the entries it takes return at once)
+    // (with a tail launch: a bin that it fits whole has no launch; of another, it takes the close
+    // clusters, all of them, and the workgroups of those entries return at once)
     const bool in_tail = plan->tail_fused && (bin == TAIL_BINS[1] || bin == TAIL_BINS[2]);
+    if (in_tail && !plan->tail_own[bin == TAIL_BINS[1] ? 1 : 2]) continue;
     k.split = in_tail ? plan->d_front + 2 * bin : nullptr;
-    k.split_cap = in_tail ? TAIL_CAP : 0;
+    k.split_cap = in_tail ? INT32_MAX : 0;
     guess(bin, lane_sched::CHAIN_BLOCK, cnt, bin < MAXNT ? bin + 1 : (bin == BIN_CONS2 ? 2 : 1));
     chains.push_back({bin, false, [k, ki, cnt](hipStream_t st) {
       void* kargs[] = {(void*)&k};
@@ -940,16 +986,20 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     }
     TailArgs ta;
     std::memset(&ta, 0, sizeof ta);
-    ta.cap = TAIL_CAP;
-    for (int sgm = 0; sgm < TAIL_SEGMENTS; ++sgm) {
+    int32_t at = 0;
+    for (int sgm : {1, 2, 0}) {   // (the order of the segments in the grid: kargs.h)
       const int bin = TAIL_BINS[sgm];
       const int64_t cnt = plan->bin_count[bin];
       ta.close[sgm] = cnt > 0 ? plan->d_front + 2 * bin : nullptr;
       ta.ord_off[sgm] = (int32_t)plan->bin_begin[bin];
-      ta.grid_begin[sgm + 1] = ta.grid_begin[sgm] + (int32_t)std::min<int64_t>(cnt, TAIL_CAP);
+      ta.whole[sgm] = plan->tail_whole[sgm] ? (int32_t)cnt : 0;
+      ta.grid_begin[sgm] = at;
+      at += (int32_t)std::min<int64_t>(cnt, TAIL_CAP);
     }
+    ta.grid_begin[TAIL_SEGMENTS] = at;
     const unsigned grid = (unsigned)plan->tail_grid;
-    int* counter = h->d_counter + 4;
+    if (at != plan->tail_grid) return fail(h, CTR_ERR_DEVICE, "internal: the tail launch's grid differs from the plan's");
+    int* counter = h->d_counter + 4;   // (one work counter per segment: 4, 5, 6)
     k.order = ord;
     k.n_bin = 0;
     guess(LAUNCH_TAIL, lane_sched::CHAIN_TAIL, (int64_t)grid, 1);
@@ -995,17 +1045,14 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     k.order = ord + plan->bin_begin[BIN_SMALL2];
     k.n_bin = (int32_t)cnt;
     int64_t waves = cnt;   // (one wavefront per pair)
-    // With a tail launch the first min(close pairs, TAIL_CAP) entries are fitted there: the 64-lane
-    // launch takes the close pairs beyond the cap (two tiers) or beyond the cap and the far pairs (one).
-    bool launch64 = true;
-    if (plan->tail_fused) {
+    // A tail launch fits every pair of the 64-lane tier -- the close ones with two tiers, all of
+    // them with one: that tier has no launch of its own then.  (But for one tier of more than
+    // TAIL_PAIRS_WHOLE pairs, wide windows: the launch takes all but the close ones.)
+    const bool launch64 = plan->tail_own[0];
+    if (launch64 && plan->tail_fused) {
       k.split = plan->d_front + 2 * BIN_SMALL2;
-      k.split_cap = TAIL_CAP;
+      k.split_cap = INT32_MAX;
       k.split_part = 3;
-      if (plan->pairs_split) {
-        launch64 = cnt > TAIL_CAP;   // (else no close pair can be left over)
-        waves = std::max<int64_t>(cnt - TAIL_CAP, 1);
-      }
     }
     if (plan->pairs_split) {
       // front_load_kernel has put the pairs closer than a quarter of the mask radius first and
@@ -1032,7 +1079,7 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
       if (waves > 2048) waves = 2048;   // persistent: a wavefront takes pair after pair
     }
     if (waves > 8192) waves = 8192;
-    guess(BIN_SMALL2, lane_sched::CHAIN_PAIRS64, cnt, 1);
+    if (launch64) guess(BIN_SMALL2, lane_sched::CHAIN_PAIRS64, cnt, 1);
     if (launch64)
       chains.push_back({BIN_SMALL2, plan->gate, [k, ki, waves, counter](hipStream_t st) {
         void* kargs[] = {(void*)&k, (void*)&counter};

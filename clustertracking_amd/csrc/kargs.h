@@ -32,9 +32,11 @@ struct KArgs {
   const double* fmax;
   const int32_t* order;  // cluster ids of this bin
   // part of the bin a launch takes.  split == nullptr: all of it.  Else, with skip =
-  // min(*split, split_cap), the entries that refine_tail_kernel fits (0 without a tail launch):
+  // min(*split, split_cap), the entries that refine_tail_kernel fits: split_cap is 0 without a
+  // tail launch and INT32_MAX with one, which takes every close cluster (skip = *split):
   // small kernel, split_part 1: entries [skip, *split) (the likely slow fits, front_load_kernel's
-  // count), split_part 2: entries [*split, n_bin), split_part 3: entries [skip, n_bin);
+  // count; queued without a tail launch only), split_part 2: entries [*split, n_bin), split_part 3:
+  // entries [skip, n_bin) (beside a tail launch, one tier of more pairs than that launch takes whole);
   // block kernel: entries [skip, n_bin)
   const int32_t* split;
   int32_t split_part;
@@ -52,16 +54,20 @@ struct KArgs {
 constexpr int LP_STRIDE = 40;   // >= 2 * 16 + 1 taps (CTR_MAX_NOISE_SIZE = 4)
 
 // refine_tail_kernel (tail_kernel.h): the likely slow clusters of three bins of a call in one
-// launch.  Segment s -- 0: the pairs, 1 / 2: the block bins NT = 1 / 2 -- takes the workgroups
-// [grid_begin[s], grid_begin[s + 1]) and, of those, as many as min(*close[s], cap): the entries
-// order[ord_off[s] + 0 ..] that front_load_kernel has put first and counted.  An empty segment
-// has no workgroup and a null count.
+// launch, and all of a bin that is small.  Segment s -- 0: the pairs, 1 / 2: the block bins
+// NT = 1 / 2 -- has the workgroups from grid_begin[s] up to the next segment's in the grid, which
+// holds the segments in the order 1, 2, 0 (the block clusters, the slowest of a call, are not
+// dispatched behind the workgroups of the pairs); grid_begin[TAIL_SEGMENTS] is the grid.  Its
+// workgroups share the entries order[ord_off[s] + 0 .. range): range = whole[s] where that is
+// positive (the bin's count: the tail launch fits the whole bin), else *close[s], the clusters
+// that front_load_kernel has put first and counted.  An empty segment has no workgroup and a null
+// count.
 constexpr int TAIL_SEGMENTS = 3;
 struct TailArgs {
   const int32_t* close[TAIL_SEGMENTS];
   int32_t ord_off[TAIL_SEGMENTS];
   int32_t grid_begin[TAIL_SEGMENTS + 1];
-  int32_t cap;
+  int32_t whole[TAIL_SEGMENTS];
 };
 
 // a kernel of another translation unit: host-side handle for hipLaunchKernel /

@@ -8,21 +8,27 @@
 // a launch holds its hardware queue until its last workgroup ends, and the pairs, the 3-4-feature
 // and the 5-10-feature bins each end with a handful of clusters that iterate for milliseconds
 // while the machine is mostly idle.  Those clusters -- the ones front_load_kernel puts first in
-// their bins and counts -- run here instead, in one launch on one queue: the three tails overlap
-// and the bins' own launches become short.
+// their bins and counts -- run here instead, in one launch on one queue: the three tails overlap.
+// The launch lives as long as the slowest fit of the call and uses a small part of the machine, so
+// its workgroups also fit the rest of a block bin that is small (ctrefine.hip: TAIL_ABSORB), and
+// every pair that would run at 64 lanes: those bins then have no launch of their own.
 //
-// One workgroup of two wavefronts per entry; what a workgroup does is uniform over it (kargs.h:
-// TailArgs).  A cluster is fitted by the statements of its bin's own kernel, the same text with the
-// same template arguments (small_kernel_body.inc, block_kernel_body.inc):
+// One workgroup of two wavefronts per entry of the grid; what a workgroup does is uniform over it
+// (kargs.h: TailArgs).  A cluster is fitted by the statements of its bin's own kernel, the same
+// text with the same template arguments (small_kernel_body.inc, block_kernel_body.inc):
 //   segment 0  pairs          refine_small_kernel<ND, 2, ISO, 64> on wavefront 0 (the other one leaves
-//                             before anything: that text has no workgroup barrier); the workgroups
-//                             of the segment pull the entries from a counter, as the bin's launch does
+//                             before anything: that text has no workgroup barrier)
 //   segment 1  block, NT = 1  refine_block_kernel<ND, ISO, 1, 2, false>
 //   segment 2  block, NT = 2  refine_block_kernel<ND, ISO, 2, 2, false>
-// No workgroup waits for another one.  A workgroup beyond its segment's count -- the grid is laid
-// out for the cap, the count is known on the device only -- returns after a few scalar
-// instructions.  Occupancy does not matter for the few hundred workgroups of a call: one per SIMD
-// pair is asked for, whatever the three texts need in registers.
+// The workgroups of a segment pull its entries, in the bin's front-loaded order, from a counter of
+// the segment (counter[segment]) until the entry is past the segment's range: the whole bin
+// (TailArgs::whole) or the close clusters that front_load_kernel has counted.  The pairs' text
+// does so itself, as in the bin's launch; around the block text it is the loop below: one thread
+// takes the entry, an LDS word and a barrier hand it to the workgroup, and a second barrier keeps
+// the next cluster's set-up out of the LDS that the write-back of this one still reads.  No
+// workgroup waits for another one; a workgroup that finds its segment's range used up returns.
+// Occupancy does not matter for the few hundred workgroups of a call: one per SIMD pair is asked
+// for, whatever the three texts need in registers.
 template <int ND>
 struct SmemT {
   static constexpr size_t b1 = SmemB<1, 2, false>::bytes, b2 = SmemB<2, 2, false>::bytes,
@@ -33,17 +39,16 @@ struct SmemT {
 template <int ND, bool ISO>
 __global__ void __launch_bounds__(2 * WAVE, 1) refine_tail_kernel(const KArgs k, const TailArgs t, int* __restrict__ counter) {
   extern __shared__ double smem[];
+  __shared__ int tail_entry;   // the entry that the workgroup fits next (block segments)
   const int b = (int)blockIdx.x;
-  const int seg = b >= t.grid_begin[2] ? 2 : (b >= t.grid_begin[1] ? 1 : 0);
+  // (the segments lie in the grid in the order TailArgs::grid_begin gives them: 1, 2, 0)
+  const int seg = b >= t.grid_begin[0] ? 0 : (b >= t.grid_begin[2] ? 2 : 1);
   // (selected, not indexed: the arguments stay in scalar registers)
   const int32_t* close = seg == 2 ? t.close[2] : (seg == 1 ? t.close[1] : t.close[0]);
-  const int begin = seg == 2 ? t.grid_begin[2] : (seg == 1 ? t.grid_begin[1] : t.grid_begin[0]);
+  const int whole = seg == 2 ? t.whole[2] : (seg == 1 ? t.whole[1] : t.whole[0]);
   const int off = seg == 2 ? t.ord_off[2] : (seg == 1 ? t.ord_off[1] : t.ord_off[0]);
   if (close == nullptr) return;
-  const int n_close = *close;
-  const int count = n_close < t.cap ? n_close : t.cap;
-  const int idx = b - begin;
-  if (idx >= count) return;
+  const int range = whole > 0 ? whole : *close;
   const int tid = (int)threadIdx.x;
   if (seg == 0) {
     if (tid >= WAVE) return;
@@ -51,18 +56,36 @@ __global__ void __launch_bounds__(2 * WAVE, 1) refine_tail_kernel(const KArgs k,
     const int lane = tid;
     double* const lds = smem;
     const int32_t* const order = k.order + off;
-    const int id_begin = 0, id_end = count;
+    const int id_begin = 0, id_end = range;
 #include "small_kernel_body.inc"
   } else if (seg == 1) {
     constexpr int NT = 1, W = 2, FIT = CTR_FIT_GAUSS;
     constexpr bool CONS = false, LP = false;
-    const int cl = k.order[off + idx];
+    for (;;) {
+      if (tid == 0) tail_entry = atomicAdd(counter + 1, 1);
+      __syncthreads();
+      const int tail_next = __builtin_amdgcn_readfirstlane(tail_entry);
+      if (tail_next >= range) break;
+      const int cl = k.order[off + tail_next];
+      {
 #include "block_kernel_body.inc"
+      }
+      __syncthreads();
+    }
   } else {
     constexpr int NT = 2, W = 2, FIT = CTR_FIT_GAUSS;
     constexpr bool CONS = false, LP = false;
-    const int cl = k.order[off + idx];
+    for (;;) {
+      if (tid == 0) tail_entry = atomicAdd(counter + 2, 1);
+      __syncthreads();
+      const int tail_next = __builtin_amdgcn_readfirstlane(tail_entry);
+      if (tail_next >= range) break;
+      const int cl = k.order[off + tail_next];
+      {
 #include "block_kernel_body.inc"
+      }
+      __syncthreads();
+    }
   }
 }
 

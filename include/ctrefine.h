@@ -262,12 +262,33 @@ void ctr_plan_destroy(ctr_plan* plan);
  * among the pairs, the 3-4-feature and the 5-10-feature clusters (block kernel, nt = 1, 2; counts
  * for the default parameter modes) fits the likely slow clusters of those bins -- two features
  * closer than a quarter of the mask radius, or more than 8 features -- in one launch of their own,
- * at most `cap` per bin; every cluster is fitted by the same kernel code as without it, the results
+ * on at most `cap` workgroups per bin, which share the bin's entries (what else the launch takes:
+ * ctr_plan_tail_bins); every cluster is fitted by the same kernel code as without it, the results
  * are the same bits.  fused: 1 if the plan does so; cap: that bound (the same for every plan);
  * tail_grid: workgroups of the launch, the sum over the three bins of min(clusters, cap), 0 if not
  * fused.  Any of the pointers may be null.  Added in ABI 8 without a version change: it changes no
  * existing struct or call. */
 int ctr_plan_tail(const ctr_plan* plan, int32_t* fused, int32_t* cap, int32_t* tail_grid);
+/* What the tail launch takes of each of its three bins -- [0] the pairs, [1] the 3-4-feature and
+ * [2] the 5-10-feature clusters -- beyond the likely slow ones.  The launch lasts as long as the
+ * slowest fit of the call on a small part of the machine, and its (at most `cap`) workgroups per
+ * bin share the bin's entries through a counter.  In a fused plan:
+ *   a block bin of at most max_count clusters (ctr_set_tail_absorb) is fitted whole by the tail
+ *     launch and has no launch of its own; of a larger one the tail launch takes the likely slow
+ *     clusters, all of them, and the bin's launch the others;
+ *   the pairs that would run at 64 lanes -- the likely slow ones where the bin runs in two tiers, all
+ *     of them where it runs in one -- are fitted by the tail launch, and the 64-lane launch is not
+ *     queued (the 16-lane tier is unchanged).  One tier of more than 8 * cap pairs (windows of more
+ *     than 600 pixels) keeps the 64-lane launch for all but the likely slow ones.
+ *   absorbed[s]:   1 if the tail launch fits the whole bin s;
+ *   own_launch[s]: 1 if the bin's own launch (pairs: the 64-lane one) is queued.
+ * A plan that does not fuse, and an empty bin: absorbed 0, own_launch 1 for a non-empty bin.  The
+ * results are the same bits whatever the setting.  Either pointer may be null. */
+int ctr_plan_tail_bins(const ctr_plan* plan, int32_t absorbed[3], int32_t own_launch[3]);
+/* max_count of the rule above for the plans that the handle creates from now on; returns the
+ * previous value (-1: null handle).  0: no block bin is fitted whole.  A negative max_count
+ * changes nothing (a query).  Default: 32 * cap. */
+int32_t ctr_set_tail_absorb(ctr_handle* h, int32_t max_count);
 int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan,
                             const ctr_batch* b_device, void* hip_stream);
 
