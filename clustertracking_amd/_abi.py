@@ -160,6 +160,17 @@ class Link(C.Structure):
     ]
 
 
+LINK_MAX_ROUNDS = 64
+
+
+class LinkAdaptive(C.Structure):
+    """``ctr_link_adaptive`` (include/ctrefine.h): linking with an adaptive search range."""
+    _fields_ = Link._fields_ + [
+        ('stop_rel', C.c_double), ('step', C.c_double), ('max_rounds', C.c_int32),
+        ('adaptive_round', C.c_void_p),
+    ]
+
+
 RELOCATE_OK, RELOCATE_CAPACITY, RELOCATE_BAD_FRAME = 0, 1, 2   # ctr_relocate.status[q]
 RELOCATE_MAX_MAXIMA, RELOCATE_MAX_BACKGROUND, RELOCATE_TILE_BYTES = 256, 512, 32768
 

@@ -49,6 +49,7 @@ SIGNATURES = {
     'ctr_locate_maxima_device': _stage(_abi.Locate),
     'ctr_characterize_device': _stage(_abi.Characterize),
     'ctr_link_device': _stage(_abi.Link),
+    'ctr_link_adaptive_device': _stage(_abi.LinkAdaptive),
     'ctr_preprocess_device': _stage(_abi.Preprocess),
     'ctr_orientation_device': _stage(_abi.Orientation),
     'ctr_diffusion_device': _stage(_abi.Diffusion),
@@ -473,6 +474,7 @@ for _name, _symbol, _too_large in (
         ('locate_maxima_device', 'ctr_locate_maxima_device', True),
         ('characterize_device', 'ctr_characterize_device', False),
         ('link_device', 'ctr_link_device', False),
+        ('link_adaptive_device', 'ctr_link_adaptive_device', False),
         ('preprocess_device', 'ctr_preprocess_device', True),
         ('orientation_device', 'ctr_orientation_device', False),
         ('diffusion_device', 'ctr_diffusion_device', False),

@@ -39,6 +39,10 @@
 // memory == 0: every kernel is launched once for the whole video.  memory > 0: level t needs the
 // `used` flags of level t - 1, so link_cand / link_solve are queued level by level (one workgroup
 // each for solve); the host waits for nothing in between.
+//
+// ctr_link_adaptive_device (include/ctrefine.h states the rule) launches link_solve_adaptive_kernel in
+// the place of link_solve_kernel, on either path: the same level solver with the rounds of the
+// adaptive search range looped inside the level's workgroup (lnk_solve_level<true>).
 #ifndef CTREFINE_LINK_KERNELS_H
 #define CTREFINE_LINK_KERNELS_H
 
@@ -165,9 +169,11 @@ __global__ __launch_bounds__(LNK_THREADS) void link_cand_kernel(LinkArgs a, int 
 // The sub-networks of one level: destinations [d0, d1), source window [w0, w1).  Every thread of the
 // workgroup calls it; s_changed: one word of LDS.  After it lab_d / lab_s hold the label of the
 // component (its smallest destination row; LNK_NONE: a source no destination lists) and cnt_s the
-// destinations that list a source; the last thing it does is a barrier.
-__device__ __forceinline__ void lnk_components(const LinkArgs& a, long long d0, long long d1, long long w0,
-                                               long long w1, int tid, int* s_changed) {
+// destinations that list a source; the last thing it does is a barrier.  ncand: the edges of
+// destination row i are the first ncand[i] entries of its candidate list (a.ncand: all of them; a
+// round of the adaptive linker: the prefix within its range, 0 for a row that is settled).
+__device__ __forceinline__ void lnk_components_of(const LinkArgs& a, const int* ncand, long long d0, long long d1,
+                                                  long long w0, long long w1, int tid, int* s_changed) {
   // ---- initial state of this level's words
   for (long long s = w0 + tid; s < w1; s += LNK_THREADS) {
     st_agent(&a.lab_s[s], LNK_NONE);
@@ -180,7 +186,7 @@ __device__ __forceinline__ void lnk_components(const LinkArgs& a, long long d0, 
   }
   __syncthreads();
   for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
-    const int nc = a.ncand[i];
+    const int nc = ncand[i];
     for (int k = 0; k < nc; ++k) atomicAdd(&a.cnt_s[a.cand_row[i * LNK_MAXC + k]], 1);
   }
   __syncthreads();
@@ -191,7 +197,7 @@ __device__ __forceinline__ void lnk_components(const LinkArgs& a, long long d0, 
     __syncthreads();
     bool changed = false;
     for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
-      const int nc = a.ncand[i];
+      const int nc = ncand[i];
       if (nc == 0) continue;
       const int mine = ld_agent(&a.lab_d[i]);
       int m = mine;
@@ -209,6 +215,11 @@ __device__ __forceinline__ void lnk_components(const LinkArgs& a, long long d0, 
     __syncthreads();
     if (!again) break;
   }
+}
+
+__device__ __forceinline__ void lnk_components(const LinkArgs& a, long long d0, long long d1, long long w0,
+                                               long long w1, int tid, int* s_changed) {
+  lnk_components_of(a, a.ncand, d0, d1, w0, w1, tid, s_changed);
 }
 
 // The assignment of one sub-network by one wavefront: shortest augmenting paths (Hungarian), one lane
@@ -275,107 +286,169 @@ __device__ __forceinline__ void lnk_hungarian(const double* cost, double* u, uns
   }
 }
 
-// One workgroup per level t = t_begin + blockIdx.x.
-__global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int t_begin) {
+// The adaptive search range (include/ctrefine.h: ctr_link_adaptive): what the adaptive
+// instantiation of the level solver takes besides LinkArgs.
+struct LinkAdaptiveArgs {
+  double stop_rel, step;
+  int max_rounds;
+  int* around;      // [N] out or null: the round a destination row was settled in (zeroed by the call)
+  // scratch of the handle
+  int* nc_k;        // [N] a destination row's edges in the current round: a prefix of its candidates
+  int* over;        // [N] by root row: k + 1 where the root's sub-network was oversize in round k (zeroed by the call)
+};
+
+// One level: destinations [off[t], off[t + 1]), every thread of the workgroup.  ADAPTIVE: rounds
+// k = 0, 1, .. inside the workgroup.  Round 0 is the plain linker's.  A wavefront that meets an
+// oversize sub-network at rho_k > stop_rel stamps its root (over[root] = k + 1) and raises the LDS
+// word s_over; in round k + 1 the rows whose label carries that stamp are the active ones, their
+// edges are the prefix of their sorted candidates with d2 <= (rho_{k+1} (1 + 1e-7))^2 (nc_k; every
+// other row: 0, so labelling, chaining and solving pass it by), and a row that keeps no edge is
+// settled by its owner lane.  Every barrier is uniform: s_over is read by all after a barrier.
+template <bool ADAPTIVE>
+__device__ __forceinline__ void lnk_solve_level(const LinkArgs& a, const LinkAdaptiveArgs& ad, int t) {
   __shared__ double s_cost[LNK_WAVES][LNK_MAX_SRC * LNK_MAX_DST];
   __shared__ double s_u[LNK_WAVES][LNK_MAX_SRC + 2];
   __shared__ int s_src[LNK_WAVES][LNK_MAX_SRC];
   __shared__ int s_dst[LNK_WAVES][LNK_MAX_DST];
   __shared__ unsigned char s_p[LNK_WAVES][LNK_MAX_SRC + LNK_MAX_DST + 2];
   __shared__ unsigned char s_way[LNK_WAVES][LNK_MAX_SRC + LNK_MAX_DST + 2];
-  __shared__ int s_changed, s_nroots;
+  __shared__ int s_changed, s_nroots, s_over;
 
-  const int t = t_begin + (int)blockIdx.x;
   const int tid = threadIdx.x;
   const long long d0 = a.off[t], d1 = a.off[t + 1];
   const long long tw = (long long)t - 1 - a.memory;
   const long long w0 = a.off[tw > 0 ? tw : 0], w1 = d0;
   if (d0 == d1 || w0 == w1) return;   // no destination or no source: nothing links (uniform)
 
-  if (tid == 0) s_nroots = 0;
-  lnk_components(a, d0, d1, w0, w1, tid, &s_changed);
-
-  // ---- 1 x 1 sub-networks link here; the others are chained to their root
-  for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
-    const int nc = a.ncand[i];
-    if (nc == 0) continue;
-    const int c = a.cand_row[i * LNK_MAXC];
-    if (nc == 1 && ld_agent(&a.cnt_s[c]) == 1) {
-      a.link[i] = c;
-      if (a.memory > 0) a.used[c] = 1;
-      st_agent(&a.cnt_s[c], 0);          // not a member of a chained component
-      continue;
+  double rho = 1.;
+  for (int round = 0;; ++round) {
+    const int* ncand = ADAPTIVE && round ? ad.nc_k : a.ncand;
+    if (tid == 0) {
+      s_nroots = 0;
+      if (ADAPTIVE) s_over = 0;
     }
-    const int root = ld_agent(&a.lab_d[i]);
-    if (root == (int)i) st_agent(&a.roots[d0 + atomicAdd(&s_nroots, 1)], (int)i);
-    st_agent(&a.next_d[i], atomicExch(&a.head_d[root], (int)i));
-  }
-  __syncthreads();   // the 1 x 1 sources are marked (cnt_s = 0) before the sources are chained
-  for (long long s = w0 + tid; s < w1; s += LNK_THREADS) {
-    if (ld_agent(&a.cnt_s[s]) == 0) continue;
-    const int root = ld_agent(&a.lab_s[s]);
-    st_agent(&a.next_s[s], atomicExch(&a.head_s[root], (int)s));
-  }
-  __syncthreads();
+    lnk_components_of(a, ncand, d0, d1, w0, w1, tid, &s_changed);
 
-  // ---- one wavefront per non-trivial sub-network
-  const int w = tid >> 6, lane = tid & 63;
-  const int nroots = s_nroots;
-  for (int ri = w; ri < nroots; ri += LNK_WAVES) {
-    const int root = ld_agent(&a.roots[d0 + ri]);
-    int ns = 0, nd = 0;
-    if (lane == 0) {   // members in ascending row order, whatever order they were chained in
-      for (int j = ld_agent(&a.head_s[root]); j >= 0; j = ld_agent(&a.next_s[j])) {
-        if (ns < LNK_MAX_SRC) {
-          int q = ns;
-          for (; q > 0 && s_src[w][q - 1] > j; --q) s_src[w][q] = s_src[w][q - 1];
-          s_src[w][q] = j;
+    // ---- 1 x 1 sub-networks link here; the others are chained to their root
+    for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
+      const int nc = ncand[i];
+      if (nc == 0) continue;
+      const int c = a.cand_row[i * LNK_MAXC];
+      if (nc == 1 && ld_agent(&a.cnt_s[c]) == 1) {
+        a.link[i] = c;
+        if (a.memory > 0) a.used[c] = 1;
+        st_agent(&a.cnt_s[c], 0);          // not a member of a chained component
+        if (ADAPTIVE && round && ad.around) ad.around[i] = round;
+        continue;
+      }
+      const int root = ld_agent(&a.lab_d[i]);
+      if (root == (int)i) st_agent(&a.roots[d0 + atomicAdd(&s_nroots, 1)], (int)i);
+      st_agent(&a.next_d[i], atomicExch(&a.head_d[root], (int)i));
+    }
+    __syncthreads();   // the 1 x 1 sources are marked (cnt_s = 0) before the sources are chained
+    for (long long s = w0 + tid; s < w1; s += LNK_THREADS) {
+      if (ld_agent(&a.cnt_s[s]) == 0) continue;
+      const int root = ld_agent(&a.lab_s[s]);
+      st_agent(&a.next_s[s], atomicExch(&a.head_s[root], (int)s));
+    }
+    __syncthreads();
+
+    // ---- one wavefront per non-trivial sub-network
+    const int w = tid >> 6, lane = tid & 63;
+    const int nroots = s_nroots;
+    for (int ri = w; ri < nroots; ri += LNK_WAVES) {
+      const int root = ld_agent(&a.roots[d0 + ri]);
+      int ns = 0, nd = 0;
+      if (lane == 0) {   // members in ascending row order, whatever order they were chained in
+        for (int j = ld_agent(&a.head_s[root]); j >= 0; j = ld_agent(&a.next_s[j])) {
+          if (ns < LNK_MAX_SRC) {
+            int q = ns;
+            for (; q > 0 && s_src[w][q - 1] > j; --q) s_src[w][q] = s_src[w][q - 1];
+            s_src[w][q] = j;
+          }
+          ++ns;
         }
-        ++ns;
-      }
-      for (int j = ld_agent(&a.head_d[root]); j >= 0; j = ld_agent(&a.next_d[j])) {
-        if (nd < LNK_MAX_DST) {
-          int q = nd;
-          for (; q > 0 && s_dst[w][q - 1] > j; --q) s_dst[w][q] = s_dst[w][q - 1];
-          s_dst[w][q] = j;
+        for (int j = ld_agent(&a.head_d[root]); j >= 0; j = ld_agent(&a.next_d[j])) {
+          if (nd < LNK_MAX_DST) {
+            int q = nd;
+            for (; q > 0 && s_dst[w][q - 1] > j; --q) s_dst[w][q] = s_dst[w][q - 1];
+            s_dst[w][q] = j;
+          }
+          ++nd;
         }
-        ++nd;
       }
-    }
-    ns = __shfl(ns, 0);
-    nd = __shfl(nd, 0);
-    if (ns > LNK_MAX_SRC) { if (lane == 0) lnk_report(a.status, 1, t, ns); continue; }
-    if (nd > LNK_MAX_DST) { if (lane == 0) lnk_report(a.status, 2, t, nd); continue; }
-    lnk_wave_sync();
-    for (int q = lane; q < ns * LNK_MAX_DST; q += 64) s_cost[w][q] = LNK_BIG;
-    const int m = nd + ns;   // columns 1..nd: destinations; nd+1..m: "no link", cost 0
-    for (int q = lane; q <= m; q += 64) { s_p[w][q] = 0; s_way[w][q] = 0; }
-    if (lane <= ns) s_u[w][lane] = 0.;
-    lnk_wave_sync();
-    if (lane < nd) {
-      const long long i = s_dst[w][lane];
-      const int nc = a.ncand[i];
-      for (int k = 0; k < nc; ++k) {
-        const int c = a.cand_row[i * LNK_MAXC + k];
-        int sl = 0;
-        while (sl < ns && s_src[w][sl] != c) ++sl;
-        if (sl < ns) s_cost[w][sl * LNK_MAX_DST + lane] = a.cand_d2[i * LNK_MAXC + k] - 2.;
+      ns = __shfl(ns, 0);
+      nd = __shfl(nd, 0);
+      if (ADAPTIVE && (ns > LNK_MAX_SRC || nd > LNK_MAX_DST) && rho > ad.stop_rel && round < ad.max_rounds) {
+        if (lane == 0) {   // its members come back in the next round, at a smaller range
+          st_agent(&ad.over[root], round + 1);
+          s_over = 1;
+        }
+        continue;
       }
-    }
-    lnk_wave_sync();
+      if (ns > LNK_MAX_SRC) { if (lane == 0) lnk_report(a.status, 1, t, ns); continue; }
+      if (nd > LNK_MAX_DST) { if (lane == 0) lnk_report(a.status, 2, t, nd); continue; }
+      lnk_wave_sync();
+      for (int q = lane; q < ns * LNK_MAX_DST; q += 64) s_cost[w][q] = LNK_BIG;
+      const int m = nd + ns;   // columns 1..nd: destinations; nd+1..m: "no link", cost 0
+      for (int q = lane; q <= m; q += 64) { s_p[w][q] = 0; s_way[w][q] = 0; }
+      if (lane <= ns) s_u[w][lane] = 0.;
+      lnk_wave_sync();
+      if (lane < nd) {
+        const long long i = s_dst[w][lane];
+        const int nc = ADAPTIVE ? ld_agent(&ncand[i]) : ncand[i];   // nc_k[i] is another lane's word
+        for (int k = 0; k < nc; ++k) {
+          const int c = a.cand_row[i * LNK_MAXC + k];
+          int sl = 0;
+          while (sl < ns && s_src[w][sl] != c) ++sl;
+          if (sl < ns) s_cost[w][sl * LNK_MAX_DST + lane] = a.cand_d2[i * LNK_MAXC + k] - (ADAPTIVE ? 2. * (rho * rho) : 2.);
+        }
+        if (ADAPTIVE && round && ad.around) ad.around[i] = round;
+      }
+      lnk_wave_sync();
 
-    lnk_hungarian(s_cost[w], s_u[w], s_p[w], s_way[w], ns, nd, lane);
-    const int c0 = lane + 1;
-    if (lane < nd) {
-      const int r = s_p[w][c0];
-      if (r && s_cost[w][(r - 1) * LNK_MAX_DST + lane] < 0.5 * LNK_BIG) {
-        const int src = s_src[w][r - 1];
-        a.link[s_dst[w][lane]] = src;
-        if (a.memory > 0) a.used[src] = 1;
+      lnk_hungarian(s_cost[w], s_u[w], s_p[w], s_way[w], ns, nd, lane);
+      const int c0 = lane + 1;
+      if (lane < nd) {
+        const int r = s_p[w][c0];
+        if (r && s_cost[w][(r - 1) * LNK_MAX_DST + lane] < 0.5 * LNK_BIG) {
+          const int src = s_src[w][r - 1];
+          a.link[s_dst[w][lane]] = src;
+          if (a.memory > 0) a.used[src] = 1;
+        }
       }
+      lnk_wave_sync();
     }
-    lnk_wave_sync();
+    if (!ADAPTIVE) break;
+
+    __syncthreads();
+    const int over = s_over;
+    __syncthreads();    // every thread has read the word before thread 0 clears it for the next round
+    if (!over) break;   // uniform: every thread read the same word after the barrier
+    // ---- the cut to rho_{k+1}: only the rows of the stamped roots stay active
+    rho *= ad.step;
+    const double b = rho * (1. + 1e-7);
+    const double b2 = b * b;
+    for (long long i = d0 + tid; i < d1; i += LNK_THREADS) {
+      const int prev = ncand[i];
+      int n = 0;
+      if (prev > 0 && ld_agent(&ad.over[ld_agent(&a.lab_d[i])]) == round + 1) {
+        while (n < prev && a.cand_d2[i * LNK_MAXC + n] <= b2) ++n;
+        if (n == 0 && ad.around) ad.around[i] = round + 1;   // the cut took its last edge
+      }
+      ad.nc_k[i] = n;
+    }
+    // the next thing another lane reads of these rows comes after the barriers of lnk_components_of
   }
+}
+
+// One workgroup per level t = t_begin + blockIdx.x.
+__global__ __launch_bounds__(LNK_THREADS) void link_solve_kernel(LinkArgs a, int t_begin) {
+  lnk_solve_level<false>(a, LinkAdaptiveArgs{}, t_begin + (int)blockIdx.x);
+}
+
+__global__ __launch_bounds__(LNK_THREADS) void link_solve_adaptive_kernel(LinkArgs a, LinkAdaptiveArgs ad, int t_begin) {
+  lnk_solve_level<true>(a, ad, t_begin + (int)blockIdx.x);
 }
 
 // row j comes before row i: positions compared axis by axis; equal positions keep their row order
@@ -442,13 +515,15 @@ __global__ __launch_bounds__(LNK_THREADS) void link_ids_kernel(LinkArgs a) {
 
 // ---- host: the scratch of a call
 // lays the scratch arrays of LinkArgs out from `base` (nullptr: only the size is wanted; else the
-// bytes at the front that every call zeroes)
-inline size_t lnk_layout(LinkArgs& a, char* base, long long n, int ndim, long long n_levels) {
+// bytes at the front that every call zeroes); ad: the adaptive linker's scratch too
+inline size_t lnk_layout(LinkArgs& a, char* base, long long n, int ndim, long long n_levels,
+                         LinkAdaptiveArgs* ad = nullptr) {
   size_t at = 0;
   const size_t N = (size_t)(n > 0 ? n : 1), L = (size_t)n_levels + 1;
   // the words that every call zeroes come first, in one block
   a.used = (int*)(base + carve(at, N * sizeof(int)));
   a.nbirth = (int*)(base + carve(at, L * sizeof(int)));
+  if (ad) ad->over = (int*)(base + carve(at, N * sizeof(int)));
   const size_t zeroed = at;
   a.spos = (double*)(base + carve(at, N * ndim * sizeof(double)));
   a.cand_d2 = (double*)(base + carve(at, N * LNK_MAXC * sizeof(double)));
@@ -457,6 +532,7 @@ inline size_t lnk_layout(LinkArgs& a, char* base, long long n, int ndim, long lo
                      &a.next_d, &a.next_s, &a.roots, &a.rank, &a.anc};
   for (int** p : per_row) *p = (int*)(base + carve(at, N * sizeof(int)));
   a.base = (long long*)(base + carve(at, L * sizeof(long long)));
+  if (ad) ad->nc_k = (int*)(base + carve(at, N * sizeof(int)));
   if (!base) return at;
   return zeroed;
 }

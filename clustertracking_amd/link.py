@@ -22,6 +22,39 @@ restates, vectorised per frame pair:
 
 The host path above is the default.  ``engine='device'`` (and :func:`link_arrays`) runs the same
 rule on the MI355X (``ctr_link_device``); there is no fallback from it.
+
+The adaptive search range (``adaptive_stop``, ``adaptive_step``; on the device
+``ctr_link_adaptive_device``) is this project's dense restatement of trackpy's published
+``adaptive_link_wrap``; parity with trackpy is not pinned.  A sub-network beyond the limits does not
+end the call: its range alone is shrunk, step by step, until it falls apart into pieces that can be
+solved.  All distances are scaled, position divided by ``search_range`` per axis.
+
+* ``stop_rel = max_a(adaptive_stop_a / search_range_a)`` must lie inside (0, 1), ``adaptive_step``
+  too.  ``rho_0 = 1`` and ``rho_{k+1} = rho_k * adaptive_step``, one double multiplication; ``K`` is
+  the smallest k with ``rho_k <= stop_rel``, found by that same loop, and at most 64.
+  ``adaptive_step`` without ``adaptive_stop`` is ignored, as in trackpy.
+* round 0: candidates and sub-networks are exactly the plain call's.  A 1 x 1 sub-network links; one
+  of at most 30 sources and at most 64 destinations is solved exactly.
+* an oversize sub-network at round k (more than 30 sources or more than 64 destinations): if
+  ``rho_k <= stop_rel`` the call fails (status ``OVERSIZE`` for the sources, ``CAPACITY`` for the
+  destinations; :class:`SubnetOversizeException` for both, naming the level and the size).
+  Otherwise its edges are cut to ``rho_{k+1}``: an edge stays iff ``d2 <= b * b`` with
+  ``b = rho_{k+1} * (1. + 1e-7)`` and ``d2 = sum_a (dst_a / sr_a - src_a / sr_a) ** 2``, summed in
+  axis order with no contraction: the number the device stores for a candidate, not the square of
+  the kd-tree's distance.  The connected components of the remaining edges among that sub-network's
+  members are the sub-networks of round k + 1.  A destination left without an edge starts a track; a
+  source left without an edge is unlinked and goes to memory as any lost source does.
+* a sub-network solved at round k maximises ``sum(2 rho_k ** 2 - d ** 2)``: the cost entry is
+  ``d2 - 2. * (rho * rho)``, trackpy's penalty for a missing link, the current range squared.
+* the limits stay 30 and 64 in adaptive mode, on the host too.  trackpy lowers its own limit to 15
+  there because its recursion is exponential; the assignment solver here is not.  So where the plain
+  call succeeds, the adaptive call returns the same ids.
+* the diagnostic ``adaptive_round`` (int32 per row, ``diag=True``) is the k of the round in which a
+  destination row was settled: its sub-network was within the limits at ``rho_k`` (whether or not
+  the solver linked the row), or the cut to ``rho_k`` took its last edge.  0 for the rows of level 0
+  and for rows without any candidate.
+
+Memory, births and ids are unchanged.
 """
 import numpy as np
 from scipy.optimize import linear_sum_assignment
@@ -34,6 +67,7 @@ from .utils import guess_pos_columns, validate_tuple
 
 MAX_NEIGHBORS = 10      # find_link.py:586
 MAX_SUB_NET_SIZE = 30   # find_link.py:582
+MAX_SUB_NET_DESTINATIONS = _abi.LINK_MAX_DESTINATIONS   # adaptive mode: the device solver's capacity, on the host too
 
 
 class SubnetOversizeException(Exception):
@@ -72,12 +106,86 @@ def _assign(n_src, n_dst, cand_src, cand_dst, cand_d):
     return link
 
 
+def _adaptive_plan(search_range, adaptive_stop, adaptive_step):
+    """``(stop_rel, step, K)`` of the adaptive search range (the module text), or ``ValueError``.
+    search_range: one positive value per axis."""
+    sr = np.asarray(search_range, dtype=np.float64)
+    stop = np.asarray(validate_tuple(adaptive_stop, len(sr)), dtype=np.float64)
+    with np.errstate(all='ignore'):
+        stop_rel = float(np.max(stop / sr))
+    if not 0 < stop_rel < 1:
+        raise ValueError("adaptive_stop must be positive and below search_range")
+    step = float(adaptive_step)
+    if not 0 < step < 1:
+        raise ValueError("adaptive_step must lie inside (0, 1)")
+    rho, k = 1., 0
+    while rho > stop_rel:
+        rho = rho * step
+        k += 1
+        if k > _abi.LINK_MAX_ROUNDS:
+            raise ValueError("adaptive_step reaches adaptive_stop only after more than %d rounds"
+                             % _abi.LINK_MAX_ROUNDS)
+    return stop_rel, step, k
+
+
+def _assign_adaptive(n_src, n_dst, cand_src, cand_dst, cand_d2, stop_rel, step, level):
+    """:func:`_assign` with the adaptive search range (the module text); cand_d2: the scaled squared
+    distances, summed in axis order.  Returns (link[dst] = src or -1, round[dst])."""
+    link = np.full(n_dst, -1, dtype=np.int64)
+    rounds = np.zeros(n_dst, dtype=np.int32)
+    edges = np.arange(len(cand_src))
+    rho, k = 1., 0
+    while len(edges):
+        src, dst, d2 = cand_src[edges], cand_dst[edges], cand_d2[edges]
+        graph = coo_matrix((np.ones(len(src)), (src, dst + n_src)), shape=(n_src + n_dst, n_src + n_dst))
+        _, comp = connected_components(graph, directed=False)
+        comp_of_cand = comp[src]
+        order = np.argsort(comp_of_cand, kind='stable')
+        bounds = np.flatnonzero(np.r_[True, np.diff(comp_of_cand[order]) != 0, True])
+        oversize = []
+        for a, b in zip(bounds[:-1], bounds[1:]):
+            idx = order[a:b]
+            s_ids, s_loc = np.unique(src[idx], return_inverse=True)
+            d_ids, d_loc = np.unique(dst[idx], return_inverse=True)
+            if len(s_ids) > MAX_SUB_NET_SIZE or len(d_ids) > MAX_SUB_NET_DESTINATIONS:
+                if rho <= stop_rel:
+                    if len(s_ids) > MAX_SUB_NET_SIZE:
+                        raise SubnetOversizeException("Subnetwork contains %d points (level %d, adaptive round %d)"
+                                                      % (len(s_ids), level, k))
+                    raise SubnetOversizeException("Subnetwork contains %d destinations (level %d, adaptive round %d)"
+                                                  % (len(d_ids), level, k))
+                oversize.append(edges[idx])
+                continue
+            rounds[d_ids] = k
+            if len(s_ids) == 1 and len(d_ids) == 1:
+                link[d_ids[0]] = s_ids[0]
+                continue
+            big = 1e6
+            cost = np.full((len(s_ids), len(d_ids) + len(s_ids)), big)
+            cost[s_loc, d_loc] = d2[idx] - 2. * (rho * rho)
+            cost[:, len(d_ids):] = 0.          # "no link" for any source
+            rows, cols = linear_sum_assignment(cost)
+            for r, c in zip(rows, cols):
+                if c < len(d_ids) and cost[r, c] < 0.5 * big:
+                    link[d_ids[c]] = s_ids[r]
+        if not oversize:
+            break
+        rho = rho * step
+        k += 1
+        b = rho * (1. + 1e-7)
+        cut = np.concatenate(oversize)
+        edges = cut[cand_d2[cut] <= b * b]
+        rounds[np.setdiff1d(cand_dst[cut], cand_dst[edges])] = k     # the cut took their last edge
+    return link, rounds
+
+
 def _check_engine(engine):
     if engine not in ('host', 'device'):
         raise ValueError("engine must be 'host' or 'device', not %r" % (engine,))
 
 
-def link_arrays(pos, frame_offset, search_range, memory=0, device=0, _on_device=False):
+def link_arrays(pos, frame_offset, search_range, memory=0, device=0, adaptive_stop=None, adaptive_step=0.95,
+                diag=False, _on_device=False):
     """Track ids of a level-sorted position table on the MI355X (``ctr_link_device``): the rule
     of :func:`link_levels`, the optimum of every sub-network from an exact assignment solver.
 
@@ -86,7 +194,17 @@ def link_arrays(pos, frame_offset, search_range, memory=0, device=0, _on_device=
     they are).  Returns int64 ids [N] as an ndarray (``_on_device``, internal: as the tensor).
     Raises :class:`SubnetOversizeException` for a sub-network of more than 30 sources and
     ``EngineError`` for one of more than 64 destinations (the solver's capacity), or when there
-    is no library or no GPU."""
+    is no library or no GPU.
+
+    ``adaptive_stop`` (a scalar or one value per axis) and ``adaptive_step``: the adaptive search
+    range of the module text (``ctr_link_adaptive_device``); both limits then raise
+    :class:`SubnetOversizeException`, and only for a sub-network that is still beyond them at
+    ``adaptive_stop``.  ``diag``: returns ``(ids, adaptive_round)``, the second int32 [N], all
+    zeros without ``adaptive_stop``."""
+    plan = None
+    if adaptive_stop is not None:         # refused before any device work
+        nd = pos.shape[1] if getattr(pos, 'ndim', 0) == 2 else len(np.atleast_1d(search_range))
+        plan = _adaptive_plan(validate_tuple(search_range, nd), adaptive_stop, adaptive_step)
     eng = _lib.default_engine(device)     # EngineError without a library or a GPU
     import torch
     dev = torch.device('cuda', device)
@@ -121,53 +239,78 @@ def link_arrays(pos, frame_offset, search_range, memory=0, device=0, _on_device=
         if n and not n_levels:
             raise ValueError("features without levels")
         particle = torch.empty(n, dtype=torch.int64, device=dev)
+        rounds = torch.zeros(n, dtype=torch.int32, device=dev) if diag else None
+
+        def result():
+            if _on_device:
+                return (particle, rounds) if diag else particle
+            return (particle.cpu().numpy(), rounds.cpu().numpy()) if diag else particle.cpu().numpy()
         if n == 0:          # nothing to launch (and an empty tensor has no address to pass)
-            return particle if _on_device else particle.cpu().numpy()
+            return result()
         n_tracks = torch.empty(1, dtype=torch.int64, device=dev)
         status = torch.empty(4, dtype=torch.int32, device=dev)
-        d = _abi.Link()
+        d = _abi.Link() if plan is None else _abi.LinkAdaptive()
         d.ndim, d.memory, d.n_levels, d.n_features = ndim, int(memory), n_levels, n
         for a in range(ndim):
             d.search_range[a] = float(sr[a])
         d.pos, d.frame_offset = pos_t.data_ptr(), off_t.data_ptr()
         d.particle, d.n_tracks, d.status = particle.data_ptr(), n_tracks.data_ptr(), status.data_ptr()
-        eng.on_current_stream(eng.link_device, d, dev=dev)
+        if plan is None:
+            eng.on_current_stream(eng.link_device, d, dev=dev)
+        else:
+            d.stop_rel, d.step, d.max_rounds = plan
+            d.adaptive_round = rounds.data_ptr() if diag else None
+            eng.on_current_stream(eng.link_adaptive_device, d, dev=dev)
         code, level, size, _ = (int(v) for v in status.cpu())   # the one synchronisation of the call
     if code == _abi.LINK_OVERSIZE:
         raise SubnetOversizeException("Subnetwork contains %d points (level %d)" % (size, level))
+    if code == _abi.LINK_CAPACITY and plan is not None:
+        raise SubnetOversizeException("Subnetwork contains %d destinations (level %d)" % (size, level))
     if code == _abi.LINK_CAPACITY:
         raise _lib.EngineError("ctr_link_device: a sub-network of level %d has %d destinations, the "
                                "device solver takes %d (CTR_ERR_UNSUPPORTED)"
                                % (level, size, _abi.LINK_MAX_DESTINATIONS))
     if code != _abi.LINK_OK:
         raise _lib.EngineError("ctr_link_device: unknown status %d" % code)
-    return particle if _on_device else particle.cpu().numpy()
+    return result()
 
 
-def _link_levels_device(levels, ndim, search_range, memory, device):
+def _link_levels_device(levels, ndim, search_range, memory, device, adaptive_stop, adaptive_step, diag):
     counts = [len(c) for c in levels]
     offs = np.r_[0, np.cumsum(counts)].astype(np.int64)
     pos = (np.concatenate([c.reshape(-1, ndim) for c in levels]) if levels else np.zeros((0, ndim)))
-    ids = link_arrays(pos, offs, search_range, memory, device)
-    return [ids[a:b] for a, b in zip(offs[:-1], offs[1:])]
+    if adaptive_stop is None and not diag:
+        ids = link_arrays(pos, offs, search_range, memory, device)
+        return [ids[a:b] for a, b in zip(offs[:-1], offs[1:])]
+    ids, rounds = link_arrays(pos, offs, search_range, memory, device, adaptive_stop, adaptive_step, diag=True)
+    ids = [ids[a:b] for a, b in zip(offs[:-1], offs[1:])]
+    return (ids, [rounds[a:b] for a, b in zip(offs[:-1], offs[1:])]) if diag else ids
 
 
-def link_levels(levels, search_range, memory=0, engine='host', device=0):
+def link_levels(levels, search_range, memory=0, engine='host', device=0, adaptive_stop=None, adaptive_step=0.95,
+                diag=False):
     """Link a sequence of coordinate arrays ``[n_t, ndim]`` (one per frame).
     Returns a list of integer id arrays aligned with the input.  ``engine='device'``: on the
-    MI355X through :func:`link_arrays` (no fallback: ``EngineError`` without a GPU)."""
+    MI355X through :func:`link_arrays` (no fallback: ``EngineError`` without a GPU).
+    ``adaptive_stop``, ``adaptive_step``: the adaptive search range of the module text, on either
+    engine.  ``diag``: returns ``(ids, adaptive_round)``, two lists of arrays aligned with the input
+    (the rounds int32, all zeros without ``adaptive_stop``)."""
     _check_engine(engine)
     levels = [np.asarray(c, dtype=np.float64) for c in levels]
     if len(levels) == 0:
+        if adaptive_stop is not None:
+            _adaptive_plan(validate_tuple(search_range, len(np.atleast_1d(search_range))), adaptive_stop, adaptive_step)
         if engine == 'device':
             _lib.default_engine(device)
-        return []
+        return ([], []) if diag else []
     ndim = levels[0].shape[1] if levels[0].ndim == 2 else len(np.atleast_1d(search_range))
     sr = np.asarray(validate_tuple(search_range, ndim), dtype=np.float64)
+    plan = None if adaptive_stop is None else _adaptive_plan(sr, adaptive_stop, adaptive_step)
     if engine == 'device':
-        return _link_levels_device(levels, ndim, tuple(sr), memory, device)
+        return _link_levels_device(levels, ndim, tuple(sr), memory, device, adaptive_stop, adaptive_step, diag)
     next_id = 0
     ids_out = []
+    rounds_out = []
     # sources of the next level: previous level + remembered lost features
     src_pos = np.zeros((0, ndim))
     src_id = np.zeros(0, dtype=np.int64)
@@ -177,6 +320,7 @@ def link_levels(levels, search_range, memory=0, engine='host', device=0):
     for t, pos in enumerate(levels):
         pos = pos.reshape(-1, ndim)
         n = len(pos)
+        rounds = np.zeros(n, dtype=np.int32)
         if t == 0:
             ids = np.arange(n, dtype=np.int64)      # find_link.py:620-623
             next_id = n
@@ -194,7 +338,15 @@ def link_levels(levels, search_range, memory=0, engine='host', device=0):
                 inds = inds.reshape(n, -1)
                 ok = np.isfinite(dists)
                 cand_dst = np.nonzero(ok)[0]
-                link = _assign(n_src, n, inds[ok], cand_dst, dists[ok])
+                if plan is None:
+                    link = _assign(n_src, n, inds[ok], cand_dst, dists[ok])
+                else:
+                    cand_src = inds[ok]
+                    d2 = np.zeros(len(cand_src))
+                    for a in range(ndim):       # in axis order, as the device sums it
+                        df = pos[cand_dst, a] / sr[a] - all_src_pos[cand_src, a] / sr[a]
+                        d2 = d2 + df * df
+                    link, rounds = _assign_adaptive(n_src, n, cand_src, cand_dst, d2, plan[0], plan[1], t)
             linked = link >= 0
             ids[linked] = all_src_id[link[linked]]
             # new tracks in lexicographic order of position (find_link.py:379-383,703)
@@ -214,13 +366,17 @@ def link_levels(levels, search_range, memory=0, engine='host', device=0):
                 mem_age = np.concatenate([mem_age[keep_mem] + 1,
                                           np.zeros(int(lost_new.sum()), dtype=np.int64)])
         ids_out.append(ids)
+        rounds_out.append(rounds)
         src_pos, src_id = pos, ids
-    return ids_out
+    return (ids_out, rounds_out) if diag else ids_out
 
 
-def link(f, search_range, memory=0, pos_columns=None, t_column='frame', engine='host', device=0):
+def link(f, search_range, memory=0, pos_columns=None, t_column='frame', engine='host', device=0, adaptive_stop=None,
+         adaptive_step=0.95, diag=False):
     """Return a copy of ``f`` (sorted by frame) with a ``particle`` column.  ``engine='device'``
-    links on the MI355X (:func:`link_arrays`); the host path is the default."""
+    links on the MI355X (:func:`link_arrays`); the host path is the default.  ``adaptive_stop``,
+    ``adaptive_step``: the adaptive search range of the module text; ``diag`` adds the column
+    ``adaptive_round``."""
     _check_engine(engine)
     if pos_columns is None:
         pos_columns = guess_pos_columns(f)
@@ -229,6 +385,12 @@ def link(f, search_range, memory=0, pos_columns=None, t_column='frame', engine='
     pos = result[pos_columns].values
     uniq, starts = np.unique(frames, return_index=True)
     stops = np.r_[starts[1:], len(frames)]
-    ids = link_levels([pos[a:b] for a, b in zip(starts, stops)], search_range, memory, engine, device)
+    ids = link_levels([pos[a:b] for a, b in zip(starts, stops)], search_range, memory, engine, device,
+                      adaptive_stop, adaptive_step, diag)
+    rounds = None
+    if diag:
+        ids, rounds = ids
     result['particle'] = np.concatenate(ids) if len(ids) else np.zeros(0, dtype=np.int64)
+    if diag:
+        result['adaptive_round'] = np.concatenate(rounds) if len(rounds) else np.zeros(0, dtype=np.int32)
     return result

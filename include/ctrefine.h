@@ -504,6 +504,55 @@ typedef struct ctr_link {
 } ctr_link;
 int ctr_link_device(ctr_handle* h, const ctr_link* l, void* hip_stream);
 
+/* ctr_link_device with an adaptive search range (link.py states the same rule): a
+ * sub-network beyond the limits does not end the call, its range is shrunk step by step until it
+ * falls apart into pieces that can be solved.  A dense restatement of trackpy's published
+ * adaptive_link_wrap (adaptive_stop / adaptive_step); parity with trackpy is not pinned.
+ * All distances are scaled (position / search_range per axis).  rho_0 = 1, rho_{k+1} = rho_k * step
+ * (one double multiplication); stop_rel = max over the axes of adaptive_stop / search_range, formed
+ * by the caller; max_rounds = the smallest k with rho_k <= stop_rel, found by that same loop.
+ *   round 0: candidates and sub-networks exactly ctr_link_device's.  A 1 x 1 sub-network links; one
+ *     of at most CTR_LINK_MAX_SOURCES sources and at most CTR_LINK_MAX_DESTINATIONS destinations is
+ *     solved exactly.
+ *   an oversize sub-network at round k (more sources or more destinations than that): if
+ *     rho_k <= stop_rel the call fails, status CTR_LINK_OVERSIZE for the sources (looked at first),
+ *     CTR_LINK_CAPACITY for the destinations, status[1] the level, status[2] the size.  Otherwise
+ *     its edges are cut to rho_{k+1}: an edge stays iff d2 <= b * b, b = rho_{k+1} * (1. + 1e-7),
+ *     d2 = sum over the axes, in axis order and without contraction, of
+ *     (dst_a / sr_a - src_a / sr_a)^2, the number the candidate search stored.  The connected
+ *     components of the remaining edges among that sub-network's members are the sub-networks of
+ *     round k + 1.  A destination left without an edge starts a track; a source left without an
+ *     edge is unlinked and goes to memory as any lost source does.
+ *   a sub-network solved at round k maximises sum(2 rho_k^2 - d^2): the cost entry is
+ *     d2 - 2. * (rho * rho), trackpy's penalty for a missing link, the current range squared.
+ *     k = 0 gives ctr_link_device's bytes.
+ *   limits: they stay CTR_LINK_MAX_SOURCES and CTR_LINK_MAX_DESTINATIONS.  trackpy lowers its own
+ *     limit to 15 in adaptive mode because its recursion is exponential; the assignment solver here
+ *     is not.  So where ctr_link_device succeeds, this call returns the same ids, byte for byte.
+ * adaptive_round[i] (may be NULL) is the k of the round in which destination row i was settled: its
+ * sub-network was within the limits at rho_k (whether or not the solver linked the row), or the cut
+ * to rho_k took its last edge.  0 for the rows of level 0 and for rows without any candidate.
+ * Memory, births, ids, status, scratch and streams as ctr_link_device.  The descriptor is checked
+ * before the handle: ctr_link's checks, stop_rel and step inside (0, 1), max_rounds in 1..64. */
+#define CTR_LINK_MAX_ROUNDS 64
+typedef struct ctr_link_adaptive {
+  int32_t ndim;                /* the fields of ctr_link */
+  int32_t memory;
+  int64_t n_levels;
+  int64_t n_features;
+  double search_range[CTR_MAX_NDIM];
+  const double* pos;
+  const int64_t* frame_offset;
+  int64_t* particle;
+  int64_t* n_tracks;
+  int32_t* status;
+  double stop_rel;             /* in (0, 1) */
+  double step;                 /* in (0, 1) */
+  int32_t max_rounds;          /* 1 .. CTR_LINK_MAX_ROUNDS */
+  int32_t* adaptive_round;     /* [N] out, or NULL */
+} ctr_link_adaptive;
+int ctr_link_adaptive_device(ctr_handle* h, const ctr_link_adaptive* l, void* hip_stream);
+
 /* Relocation candidates of lost features on the device: the rule of the reference's
  * FindLinker.get_relocate_candidates (find_link.py:811-867), the look-again step that
  * makes find_link more than locate followed by link.  The loop around it (shortage per sub-network,
