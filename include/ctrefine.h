@@ -104,7 +104,10 @@ enum {
   CTR_STATUS_OK = 0,
   CTR_STATUS_OUT_OF_BOUNDS = 1, /* no coordinate inside the frame (refine.py:33-34) or empty mask */
   CTR_STATUS_NONFINITE = 2,     /* non-finite initial parameters (refine.py:356-357) */
-  CTR_STATUS_NO_CONVERGENCE = 3,/* solver failed / iteration limit (refine.py:376-377) */
+  CTR_STATUS_NO_CONVERGENCE = 3,/* solver failed / iteration limit (refine.py:376-377).  An empty bound
+                                   interval on a variable (low > high; the reference's SciPy call raises
+                                   on such a box) is this status, with n_rounds 1 and n_iter 0; bounds of
+                                   constant columns are not read */
   CTR_STATUS_RMS_DEV = 4,       /* rms deviation above max_rms_dev (refine.py:391-394) */
   CTR_STATUS_TOO_LARGE = 5      /* beyond the engine: a cluster of the large-cluster path in which a feature
                                    has more than CTR_MAX_NEIGHBOURS overlapping neighbours, or whose

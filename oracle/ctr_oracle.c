@@ -613,7 +613,7 @@ static double mu0_sizevar = 1.;
 void ctro_set_mu0_sizevar(double x) { mu0_sizevar = x; }
 void ctro_set_trace(int on) { trace = on; }
 
-typedef struct { double S; long P; int iters; int ok; } solve_t;
+typedef struct { double S; long P; int iters; int ok; int infeasible; } solve_t;
 static void full_second_order(const ctx_t* c, const double* v, double* Qf);
 
 /* Retraction onto the constraint manifold c(x) = 0 (constraints.py:59-137): minimum-norm
@@ -832,7 +832,7 @@ static solve_t solve(const ctx_t* c, const double* v0, const double* lo, const d
   const int maxiter = c->p->solver_maxiter > 0 ? c->p->solver_maxiter : 100;
   const double xtol = c->p->xtol > 0 ? c->p->xtol : 1e-9;
   const double ftol = c->p->ftol > 0 ? c->p->ftol : 1e-14;
-  solve_t out = {NAN, 0, 0, 0};
+  solve_t out = {NAN, 0, 0, 0, 0};
   double *g = malloc(sizeof(double) * nv), *A = malloc(sizeof(double) * nv * nv);
   double *gt = malloc(sizeof(double) * nv), *At = malloc(sizeof(double) * nv * nv);
   double *Q = calloc((size_t)nv * nv, sizeof(double)), *Qt = calloc((size_t)nv * nv, sizeof(double));
@@ -863,9 +863,17 @@ static solve_t solve(const ctx_t* c, const double* v0, const double* lo, const d
   int last_accepted = 1, it = 0;
   double prev_step = INFINITY; /* relative size of the last accepted step */
   double gain = INFINITY; /* relative decrease of the objective by the last accepted step */
+  /* params_std is built from the sums of the last pixel pass, which must belong to the final
+   * point: with compute_error the small and block kernels do not take the fast exit below
+   * (small_kernel_body.inc, block_kernel_body.inc: `k.params_std == nullptr`), and neither does
+   * the oracle.  The large-cluster path gives no params_std and always takes it.  The two exits
+   * agree to xtol while the step sizes fall at one rate; after a change of the active set (a start
+   * clipped into its box and released again) the fast exit can stop 1e-6 px short of the minimum,
+   * which the plain exit reaches: tests/test_gpu_endings.py, start_clipped of gauss_tp-2d-iso-nt3. */
+  const int std_at_solution = c->b->params_std != NULL && c->L.n <= 64 && nv <= CTR_MAX_VARS;
 
   for (int i = 0; i < nv; ++i) {
-    if (lo[i] > hi[i]) goto done; /* infeasible box (SciPy raises ValueError) */
+    if (lo[i] > hi[i]) { out.infeasible = 1; goto done; } /* empty box (SciPy raises ValueError): no pixel pass */
     v[i] = v0[i] < lo[i] ? lo[i] : (v0[i] > hi[i] ? hi[i] : v0[i]);
   }
   memset(mult, 0, sizeof mult);
@@ -1064,7 +1072,7 @@ static solve_t solve(const ctx_t* c, const double* v0, const double* lo, const d
      * one would be <= r * step.  Where that is below xtol the fit is finished by TAKING this
      * step, without the pixel pass that would only confirm it (the point returned is then as
      * exact as the one the plain test returns an iteration later; S from the model). */
-    if (fast_exit && last_accepted && pred > 0. && stepmax < prev_step && isfinite(prev_step) &&
+    if (fast_exit && !std_at_solution && last_accepted && pred > 0. && stepmax < prev_step && isfinite(prev_step) &&
         stepmax * (stepmax / prev_step) <= xtol) {
       memcpy(v, vt, sizeof(double) * nv);
       S -= 2. * pred;
@@ -1332,6 +1340,7 @@ static void refine_one(const ctr_problem* p, const ctr_batch* b, int64_t cl,
       make_fwin(&c);                                            /* refine.py:37-40 */
       solve_t r = solve(&c, v0, lo, hi, v);
       b->n_iter[cl] += r.iters;
+      if (r.infeasible) { status = CTR_STATUS_NO_CONVERGENCE; break; } /* low > high on a variable: solver failed */
       if (r.P == 0) { status = CTR_STATUS_OUT_OF_BOUNDS; break; }
       if (!r.ok) { status = CTR_STATUS_NO_CONVERGENCE; break; } /* refine.py:376-377 */
       rms = sqrt(((r.S / (double)r.P) / norm) / p->residual_factor); /* refine.py:379 */
