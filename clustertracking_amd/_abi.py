@@ -171,7 +171,18 @@ class LinkAdaptive(C.Structure):
     ]
 
 
-RELOCATE_OK, RELOCATE_CAPACITY, RELOCATE_BAD_FRAME = 0, 1, 2   # ctr_relocate.status[q]
+LINK_PREDICT_VELOCITY, LINK_PREDICT_DRIFT = 1, 2   # ctr_link_predict.predictor
+
+
+class LinkPredict(C.Structure):
+    """``ctr_link_predict`` (include/ctrefine.h): linking with a velocity or drift prediction;
+    ``max_rounds == 0``: no adaptive search range."""
+    _fields_ = LinkAdaptive._fields_ + [
+        ('predictor', C.c_int32), ('initial_velocity', C.c_double * MAX_NDIM), ('velocity', C.c_void_p),
+    ]
+
+
+RELOCATE_OK, RELOCATE_CAPACITY, RELOCATE_BAD_FRAME = 0, 1, 2  # ctr_relocate.status[q]
 RELOCATE_MAX_MAXIMA, RELOCATE_MAX_BACKGROUND, RELOCATE_TILE_BYTES = 256, 512, 32768
 
 

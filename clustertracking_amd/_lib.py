@@ -50,6 +50,7 @@ SIGNATURES = {
     'ctr_characterize_device': _stage(_abi.Characterize),
     'ctr_link_device': _stage(_abi.Link),
     'ctr_link_adaptive_device': _stage(_abi.LinkAdaptive),
+    'ctr_link_predict_device': _stage(_abi.LinkPredict),
     'ctr_preprocess_device': _stage(_abi.Preprocess),
     'ctr_orientation_device': _stage(_abi.Orientation),
     'ctr_diffusion_device': _stage(_abi.Diffusion),
@@ -475,6 +476,7 @@ for _name, _symbol, _too_large in (
         ('characterize_device', 'ctr_characterize_device', False),
         ('link_device', 'ctr_link_device', False),
         ('link_adaptive_device', 'ctr_link_adaptive_device', False),
+        ('link_predict_device', 'ctr_link_predict_device', False),
         ('preprocess_device', 'ctr_preprocess_device', True),
         ('orientation_device', 'ctr_orientation_device', False),
         ('diffusion_device', 'ctr_diffusion_device', False),

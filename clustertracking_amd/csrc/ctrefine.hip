@@ -1439,6 +1439,10 @@ int ctr_link_adaptive_device(ctr_handle* h, const ctr_link_adaptive* l, void* hi
   return run_stage("ctr_link_adaptive_device", h, &ctr_handle::link, l, hip_stream, ctr_link_adaptive_launch);
 }
 
+int ctr_link_predict_device(ctr_handle* h, const ctr_link_predict* l, void* hip_stream) {
+  return run_stage("ctr_link_predict_device", h, &ctr_handle::link, l, hip_stream, ctr_link_predict_launch);
+}
+
 int ctr_relocate_device(ctr_handle* h, const ctr_relocate* r, void* hip_stream) {
   return run_stage("ctr_relocate_device", h, nullptr, r, hip_stream, ctr_relocate_launch);
 }

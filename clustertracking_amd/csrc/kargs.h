@@ -172,6 +172,7 @@ int ctr_characterize_launch(const ctr_characterize* c, StageRun* stage, const ch
 int ctr_preprocess_launch(const ctr_preprocess* p, StageRun* stage, const char** msg);       // preprocess_kernels.h
 int ctr_link_launch(const ctr_link* l, StageRun* stage, const char** msg);                   // link_kernels.h; scratch
 int ctr_link_adaptive_launch(const ctr_link_adaptive* l, StageRun* stage, const char** msg);   // ... with the adaptive search range
+int ctr_link_predict_launch(const ctr_link_predict* l, StageRun* stage, const char** msg);     // ... with prediction (link_predict_kernels.h)
 int ctr_orientation_launch(const ctr_orientation* o, StageRun* stage, const char** msg);     // motion_kernels.h
 int ctr_diffusion_launch(const ctr_diffusion* d, StageRun* stage, const char** msg);         // ... scratch: its partial sums
 // bootstrap interval of the diffusion tensor (motion_ci_kernels.h; scratch): the launch decision

@@ -43,6 +43,7 @@
 // ctr_link_adaptive_device (include/ctrefine.h states the rule) launches link_solve_adaptive_kernel in
 // the place of link_solve_kernel, on either path: the same level solver with the rounds of the
 // adaptive search range looped inside the level's workgroup (lnk_solve_level<true>).
+// ctr_link_predict_device: link_predict_kernels.h.
 #ifndef CTREFINE_LINK_KERNELS_H
 #define CTREFINE_LINK_KERNELS_H
 
@@ -118,8 +119,10 @@ __global__ __launch_bounds__(LNK_THREADS) void link_prep_kernel(LinkArgs a) {
   }
 }
 
+// src: the scaled positions the sources are offered at, [N, ND]: a.spos, or the predicted ones
+// (link_predict_kernels.h)
 template <int ND>
-__global__ __launch_bounds__(LNK_THREADS) void link_cand_kernel(LinkArgs a, int t_begin, int t_end) {
+__device__ __forceinline__ void lnk_cand(const LinkArgs& a, const double* src, int t_begin, int t_end) {
   const long long r0 = a.off[t_begin], r1 = a.off[t_end];
   const long long stride = (long long)gridDim.x * LNK_THREADS;
   const double bound = (1. + 1e-7) * (1. + 1e-7);
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(LNK_THREADS) void link_cand_kernel(LinkArgs a, int 
       double d2 = 0.;
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
-        const double df = pd[d] - a.spos[s * ND + d];
+        const double df = pd[d] - src[s * ND + d];
         d2 += df * df;
       }
       if (!(d2 <= bound)) continue;
@@ -164,6 +167,11 @@ __global__ __launch_bounds__(LNK_THREADS) void link_cand_kernel(LinkArgs a, int 
     }
     a.ncand[i] = n;
   }
+}
+
+template <int ND>
+__global__ __launch_bounds__(LNK_THREADS) void link_cand_kernel(LinkArgs a, int t_begin, int t_end) {
+  lnk_cand<ND>(a, a.spos, t_begin, t_end);
 }
 
 // The sub-networks of one level: destinations [d0, d1), source window [w0, w1).  Every thread of the
@@ -516,8 +524,20 @@ __global__ __launch_bounds__(LNK_THREADS) void link_ids_kernel(LinkArgs a) {
 // ---- host: the scratch of a call
 // lays the scratch arrays of LinkArgs out from `base` (nullptr: only the size is wanted; else the
 // bytes at the front that every call zeroes); ad: the adaptive linker's scratch too
+// Prediction (include/ctrefine.h: ctr_link_predict): what the kernels of link_predict_kernels.h take
+// besides LinkArgs.
+struct LinkPredictArgs {
+  int predictor;    // CTR_LINK_PREDICT_*
+  double v0[3];
+  double* w;        // [N, ndim] the velocity of every row: the caller's array, or scratch
+  // scratch of the handle
+  double* w_own;    // [N, ndim] w when the caller passes no array
+  double* ppos;     // [N, ndim] the predicted scaled position of a row as a source of the current level
+  double* u;        // [n_levels, ndim] the drift of every level (CTR_LINK_PREDICT_DRIFT)
+};
+
 inline size_t lnk_layout(LinkArgs& a, char* base, long long n, int ndim, long long n_levels,
-                         LinkAdaptiveArgs* ad = nullptr) {
+                         LinkAdaptiveArgs* ad = nullptr, LinkPredictArgs* pr = nullptr) {
   size_t at = 0;
   const size_t N = (size_t)(n > 0 ? n : 1), L = (size_t)n_levels + 1;
   // the words that every call zeroes come first, in one block
@@ -533,6 +553,11 @@ inline size_t lnk_layout(LinkArgs& a, char* base, long long n, int ndim, long lo
   for (int** p : per_row) *p = (int*)(base + carve(at, N * sizeof(int)));
   a.base = (long long*)(base + carve(at, L * sizeof(long long)));
   if (ad) ad->nc_k = (int*)(base + carve(at, N * sizeof(int)));
+  if (pr) {
+    pr->w_own = (double*)(base + carve(at, N * ndim * sizeof(double)));
+    pr->ppos = (double*)(base + carve(at, N * ndim * sizeof(double)));
+    pr->u = (double*)(base + carve(at, L * ndim * sizeof(double)));
+  }
   if (!base) return at;
   return zeroed;
 }

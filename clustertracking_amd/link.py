@@ -55,6 +55,44 @@ solved.  All distances are scaled, position divided by ``search_range`` per axis
   and for rows without any candidate.
 
 Memory, births and ids are unchanged.
+
+Prediction (``predictor``, ``initial_velocity``; on the device ``ctr_link_predict_device``) links a
+sample that moves: a track is looked for where it is expected to be, not where it last was.  The
+rule is the project's own, after trackpy's nearest-velocity and drift predictors; parity with
+trackpy is not pinned.  Every row i of level t(i) gets a velocity ``w_i [ndim]`` in pixels per level
+once the links of its level are decided.  ``v0`` is ``initial_velocity`` (default zeros).
+
+* own velocity of a linked row: for a row i of level t that is linked to source row s of level t_s,
+  ``q_i[a] = (p_i[a] - p_s[a]) / (double)(t - t_s)``: one subtraction and one division.
+* ``predictor='velocity'``: level 0: ``w_i = v0``.  A linked row: ``w_i = q_i``.  An unlinked row (a
+  birth) takes ``w_j`` of the linked row j of the same level that is nearest in scaled coordinates:
+  the scaled distance is ``sum_a (p_i[a] / sr[a] - p_j[a] / sr[a]) ** 2``, summed in axis order; a
+  tie goes to the lower row; there is no distance limit.  If the level has no linked row, the birth
+  takes ``v0``.
+* ``predictor='drift'``: one vector per level, ``u_0 = v0``.  For level t >= 1 with M linked rows:
+  ``u_t[a] = S_a / M`` if M > 0, otherwise ``u_t = u_{t-1}``.  ``S_a`` is summed in this fixed order:
+  partial sum l of 256 starts at ``0.`` and adds ``q_i[a]`` of the linked rows among rows
+  ``r0 + l, r0 + l + 256, ..`` of the level (r0: its first row), in ascending order; then for
+  ``h = 128, 64, .., 1``: ``part[l] += part[l + h]`` for ``l < h``; ``S_a = part[0]``.
+  ``w_i = u_t`` for every row of level t.
+* prediction: source s (a row of level t_s, the previous level or a remembered one) is offered to
+  level t at the predicted position ``P_s``.  ``'velocity'``:
+  ``P_s[a] = p_s[a] + w_s[a] * (double)(t - t_s)``; ``'drift'``: the same with ``u_{t-1}[a]`` in
+  place of ``w_s[a]``.  One multiplication, then one addition, with no contraction.
+  ``P_s[a] / sr[a]`` takes the place of ``p_s[a] / sr[a]`` in the candidate search, and so in the
+  ``d2`` that is stored.
+* everything else is unchanged: the ten nearest candidates, the ``1 + 1e-7`` bound, sub-networks,
+  the exact solver, the limits 30 and 64, birth order, ids and memory.  A remembered source still
+  leaves after ``memory`` levels; what changes is that it is predicted forward by its age.
+* the adaptive range composes with prediction: the rounds work on the ``d2`` of the predicted
+  positions.
+* limits of the rule: time is counted in levels.  In the table form (:func:`link`) a frame without
+  rows is not a level, as today, so a gap in the frame numbers is not a gap in time.  Without
+  ``initial_velocity``, a sample that already moves beyond the range at level 1 never acquires a
+  velocity: nothing links, and a level without linked rows passes ``v0`` on.
+
+``want_velocity=True`` returns the ``w`` of every row.  ``predictor=None`` runs exactly the code
+paths above.
 """
 import numpy as np
 from scipy.optimize import linear_sum_assignment
@@ -179,13 +217,80 @@ def _assign_adaptive(n_src, n_dst, cand_src, cand_dst, cand_d2, stop_rel, step, 
     return link, rounds
 
 
+PREDICTORS = {'velocity': _abi.LINK_PREDICT_VELOCITY, 'drift': _abi.LINK_PREDICT_DRIFT}
+DRIFT_PARTS = 256       # partial sums of the drift predictor's mean (the module text)
+
+
+def _predict_plan(predictor, initial_velocity, want_velocity, ndim):
+    """``(code, v0 [ndim] float64)`` of a predictive call, ``None`` without a predictor, or
+    ``ValueError`` (the module text)."""
+    if predictor is None:
+        if initial_velocity is not None:
+            raise ValueError("initial_velocity needs a predictor")
+        if want_velocity:
+            raise ValueError("want_velocity needs a predictor")
+        return None
+    if not isinstance(predictor, str) or predictor not in PREDICTORS:
+        raise ValueError("predictor must be None, 'velocity' or 'drift', not %r" % (predictor,))
+    if initial_velocity is None:
+        initial_velocity = 0.
+    if isinstance(initial_velocity, np.ndarray):
+        initial_velocity = initial_velocity.reshape(-1).tolist()
+    v0 = np.asarray(validate_tuple(initial_velocity, ndim), dtype=np.float64)
+    if not np.all(np.isfinite(v0)):
+        raise ValueError("initial_velocity must be finite")
+    return PREDICTORS[predictor], v0
+
+
+def _drift_mean(q, linked):
+    """``u_t`` of the drift predictor: the mean of q [n, ndim] over the linked rows, summed in the
+    order of the module text.  At least one row is linked."""
+    n, ndim = q.shape
+    trips = -(-n // DRIFT_PARTS)
+    padded = np.zeros((trips * DRIFT_PARTS, ndim))
+    padded[:n][linked] = q[linked]          # adding 0. for a row that is not linked changes no partial sum
+    part = np.zeros((DRIFT_PARTS, ndim))
+    for k in range(trips):
+        part = part + padded[k * DRIFT_PARTS:(k + 1) * DRIFT_PARTS]
+    h = DRIFT_PARTS // 2
+    while h:
+        part[:h] = part[:h] + part[h:2 * h]
+        h //= 2
+    return part[0] / float(np.count_nonzero(linked))
+
+
+def _level_velocity(code, pos, link, all_src_pos, all_src_t, t, sr, v0, u_prev):
+    """``w [n, ndim]`` of the rows of level t >= 1 once ``link`` is decided (the module text)."""
+    n, ndim = pos.shape
+    linked = link >= 0
+    q = np.zeros((n, ndim))
+    if linked.any():
+        src = link[linked]
+        q[linked] = (pos[linked] - all_src_pos[src]) / (t - all_src_t[src]).astype(np.float64)[:, None]
+    if code == _abi.LINK_PREDICT_DRIFT:
+        u = _drift_mean(q, linked) if linked.any() else u_prev
+        return np.broadcast_to(u, (n, ndim)).copy()
+    w = q
+    births = np.flatnonzero(~linked)
+    if len(births) and not linked.any():
+        w[births] = v0
+    elif len(births):
+        rows = np.flatnonzero(linked)
+        d2 = np.zeros((len(births), len(rows)))
+        for a in range(ndim):
+            df = (pos[births, a] / sr[a])[:, None] - (pos[rows, a] / sr[a])[None, :]
+            d2 = d2 + df * df
+        w[births] = q[rows[np.argmin(d2, axis=1)]]      # the first minimum: a tie goes to the lower row
+    return w
+
+
 def _check_engine(engine):
     if engine not in ('host', 'device'):
         raise ValueError("engine must be 'host' or 'device', not %r" % (engine,))
 
 
 def link_arrays(pos, frame_offset, search_range, memory=0, device=0, adaptive_stop=None, adaptive_step=0.95,
-                diag=False, _on_device=False):
+                diag=False, _on_device=False, predictor=None, initial_velocity=None, want_velocity=False):
     """Track ids of a level-sorted position table on the MI355X (``ctr_link_device``): the rule
     of :func:`link_levels`, the optimum of every sub-network from an exact assignment solver.
 
@@ -200,11 +305,17 @@ def link_arrays(pos, frame_offset, search_range, memory=0, device=0, adaptive_st
     range of the module text (``ctr_link_adaptive_device``); both limits then raise
     :class:`SubnetOversizeException`, and only for a sub-network that is still beyond them at
     ``adaptive_stop``.  ``diag``: returns ``(ids, adaptive_round)``, the second int32 [N], all
-    zeros without ``adaptive_stop``."""
+    zeros without ``adaptive_stop``.
+
+    ``predictor`` (``'velocity'`` or ``'drift'``) and ``initial_velocity`` (a scalar or one value per
+    axis, pixels per level): the prediction of the module text (``ctr_link_predict_device``, always
+    queued level by level; with ``adaptive_stop`` the two compose).  ``want_velocity`` appends the
+    velocities, float64 [N, ndim], to what is returned."""
     plan = None
+    nd = pos.shape[1] if getattr(pos, 'ndim', 0) == 2 else len(np.atleast_1d(search_range))
     if adaptive_stop is not None:         # refused before any device work
-        nd = pos.shape[1] if getattr(pos, 'ndim', 0) == 2 else len(np.atleast_1d(search_range))
         plan = _adaptive_plan(validate_tuple(search_range, nd), adaptive_stop, adaptive_step)
+    pred = _predict_plan(predictor, initial_velocity, want_velocity, nd)
     eng = _lib.default_engine(device)     # EngineError without a library or a GPU
     import torch
     dev = torch.device('cuda', device)
@@ -240,26 +351,35 @@ def link_arrays(pos, frame_offset, search_range, memory=0, device=0, adaptive_st
             raise ValueError("features without levels")
         particle = torch.empty(n, dtype=torch.int64, device=dev)
         rounds = torch.zeros(n, dtype=torch.int32, device=dev) if diag else None
+        velocity = torch.empty((n, ndim), dtype=torch.float64, device=dev) if want_velocity else None
 
         def result():
-            if _on_device:
-                return (particle, rounds) if diag else particle
-            return (particle.cpu().numpy(), rounds.cpu().numpy()) if diag else particle.cpu().numpy()
+            out = [particle] + ([rounds] if diag else []) + ([velocity] if want_velocity else [])
+            if not _on_device:
+                out = [o.cpu().numpy() for o in out]
+            return tuple(out) if len(out) > 1 else out[0]
         if n == 0:          # nothing to launch (and an empty tensor has no address to pass)
             return result()
         n_tracks = torch.empty(1, dtype=torch.int64, device=dev)
         status = torch.empty(4, dtype=torch.int32, device=dev)
-        d = _abi.Link() if plan is None else _abi.LinkAdaptive()
+        d = _abi.LinkPredict() if pred is not None else _abi.Link() if plan is None else _abi.LinkAdaptive()
         d.ndim, d.memory, d.n_levels, d.n_features = ndim, int(memory), n_levels, n
         for a in range(ndim):
             d.search_range[a] = float(sr[a])
         d.pos, d.frame_offset = pos_t.data_ptr(), off_t.data_ptr()
         d.particle, d.n_tracks, d.status = particle.data_ptr(), n_tracks.data_ptr(), status.data_ptr()
-        if plan is None:
-            eng.on_current_stream(eng.link_device, d, dev=dev)
-        else:
+        if plan is not None:
             d.stop_rel, d.step, d.max_rounds = plan
             d.adaptive_round = rounds.data_ptr() if diag else None
+        if pred is not None:
+            d.predictor = pred[0]             # max_rounds stays 0 without adaptive_stop
+            for a in range(ndim):
+                d.initial_velocity[a] = float(pred[1][a])
+            d.velocity = velocity.data_ptr() if want_velocity else None
+            eng.on_current_stream(eng.link_predict_device, d, dev=dev)
+        elif plan is None:
+            eng.on_current_stream(eng.link_device, d, dev=dev)
+        else:
             eng.on_current_stream(eng.link_adaptive_device, d, dev=dev)
         code, level, size, _ = (int(v) for v in status.cpu())   # the one synchronisation of the call
     if code == _abi.LINK_OVERSIZE:
@@ -275,10 +395,18 @@ def link_arrays(pos, frame_offset, search_range, memory=0, device=0, adaptive_st
     return result()
 
 
-def _link_levels_device(levels, ndim, search_range, memory, device, adaptive_stop, adaptive_step, diag):
+def _link_levels_device(levels, ndim, search_range, memory, device, adaptive_stop, adaptive_step, diag,
+                        predictor=None, initial_velocity=None, want_velocity=False):
     counts = [len(c) for c in levels]
     offs = np.r_[0, np.cumsum(counts)].astype(np.int64)
     pos = (np.concatenate([c.reshape(-1, ndim) for c in levels]) if levels else np.zeros((0, ndim)))
+
+    def split(v):
+        return [v[a:b] for a, b in zip(offs[:-1], offs[1:])]
+    if predictor is not None:
+        out = link_arrays(pos, offs, search_range, memory, device, adaptive_stop, adaptive_step, diag=diag,
+                          predictor=predictor, initial_velocity=initial_velocity, want_velocity=want_velocity)
+        return tuple(split(o) for o in out) if isinstance(out, tuple) else split(out)
     if adaptive_stop is None and not diag:
         ids = link_arrays(pos, offs, search_range, memory, device)
         return [ids[a:b] for a, b in zip(offs[:-1], offs[1:])]
@@ -288,35 +416,48 @@ def _link_levels_device(levels, ndim, search_range, memory, device, adaptive_sto
 
 
 def link_levels(levels, search_range, memory=0, engine='host', device=0, adaptive_stop=None, adaptive_step=0.95,
-                diag=False):
+                diag=False, predictor=None, initial_velocity=None, want_velocity=False):
     """Link a sequence of coordinate arrays ``[n_t, ndim]`` (one per frame).
     Returns a list of integer id arrays aligned with the input.  ``engine='device'``: on the
     MI355X through :func:`link_arrays` (no fallback: ``EngineError`` without a GPU).
     ``adaptive_stop``, ``adaptive_step``: the adaptive search range of the module text, on either
     engine.  ``diag``: returns ``(ids, adaptive_round)``, two lists of arrays aligned with the input
-    (the rounds int32, all zeros without ``adaptive_stop``)."""
+    (the rounds int32, all zeros without ``adaptive_stop``).
+    ``predictor`` (``'velocity'`` or ``'drift'``), ``initial_velocity`` (a scalar or one value per
+    axis, pixels per level): the prediction of the module text, on either engine; a level without
+    rows is a level here (time passes).  ``want_velocity`` appends the velocities, a list of float64
+    ``[n_t, ndim]`` arrays, to what is returned."""
     _check_engine(engine)
     levels = [np.asarray(c, dtype=np.float64) for c in levels]
     if len(levels) == 0:
         if adaptive_stop is not None:
             _adaptive_plan(validate_tuple(search_range, len(np.atleast_1d(search_range))), adaptive_stop, adaptive_step)
+        _predict_plan(predictor, initial_velocity, want_velocity, len(np.atleast_1d(search_range)))
         if engine == 'device':
             _lib.default_engine(device)
-        return ([], []) if diag else []
+        out = [[]] + ([[]] if diag else []) + ([[]] if want_velocity else [])
+        return tuple(out) if len(out) > 1 else out[0]
     ndim = levels[0].shape[1] if levels[0].ndim == 2 else len(np.atleast_1d(search_range))
     sr = np.asarray(validate_tuple(search_range, ndim), dtype=np.float64)
     plan = None if adaptive_stop is None else _adaptive_plan(sr, adaptive_stop, adaptive_step)
+    pred = _predict_plan(predictor, initial_velocity, want_velocity, ndim)
     if engine == 'device':
-        return _link_levels_device(levels, ndim, tuple(sr), memory, device, adaptive_stop, adaptive_step, diag)
+        return _link_levels_device(levels, ndim, tuple(sr), memory, device, adaptive_stop, adaptive_step, diag,
+                                   predictor, initial_velocity, want_velocity)
     next_id = 0
     ids_out = []
     rounds_out = []
+    vel_out = []
     # sources of the next level: previous level + remembered lost features
     src_pos = np.zeros((0, ndim))
     src_id = np.zeros(0, dtype=np.int64)
     mem_pos = np.zeros((0, ndim))
     mem_id = np.zeros(0, dtype=np.int64)
     mem_age = np.zeros(0, dtype=np.int64)
+    # prediction: the velocity of every source and the level it was seen at; the drift of the last level
+    src_w = mem_w = np.zeros((0, ndim))
+    mem_t = np.zeros(0, dtype=np.int64)
+    u_prev = None if pred is None else pred[1]
     for t, pos in enumerate(levels):
         pos = pos.reshape(-1, ndim)
         n = len(pos)
@@ -324,14 +465,24 @@ def link_levels(levels, search_range, memory=0, engine='host', device=0, adaptiv
         if t == 0:
             ids = np.arange(n, dtype=np.int64)      # find_link.py:620-623
             next_id = n
+            if pred is not None:
+                w = np.broadcast_to(pred[1], (n, ndim)).copy()
         else:
             all_src_pos = np.concatenate([src_pos, mem_pos])
             all_src_id = np.concatenate([src_id, mem_id])
             n_src = len(all_src_pos)
+            offered = all_src_pos
+            if pred is not None:                    # the sources at their predicted positions
+                all_src_t = np.concatenate([np.full(len(src_pos), t - 1, dtype=np.int64), mem_t])
+                age = (t - all_src_t).astype(np.float64)[:, None]
+                if pred[0] == _abi.LINK_PREDICT_DRIFT:
+                    offered = all_src_pos + u_prev[None, :] * age
+                else:
+                    offered = all_src_pos + np.concatenate([src_w, mem_w]) * age
             ids = np.full(n, -1, dtype=np.int64)
             link = np.full(n, -1, dtype=np.int64)
             if n_src and n:
-                tree = cKDTree(all_src_pos / sr, 15)
+                tree = cKDTree(offered / sr, 15)
                 k = min(MAX_NEIGHBORS, n_src)
                 dists, inds = tree.query(pos / sr, k, distance_upper_bound=1 + 1e-7)
                 dists = dists.reshape(n, -1)
@@ -344,7 +495,7 @@ def link_levels(levels, search_range, memory=0, engine='host', device=0, adaptiv
                     cand_src = inds[ok]
                     d2 = np.zeros(len(cand_src))
                     for a in range(ndim):       # in axis order, as the device sums it
-                        df = pos[cand_dst, a] / sr[a] - all_src_pos[cand_src, a] / sr[a]
+                        df = pos[cand_dst, a] / sr[a] - offered[cand_src, a] / sr[a]
                         d2 = d2 + df * df
                     link, rounds = _assign_adaptive(n_src, n, cand_src, cand_dst, d2, plan[0], plan[1], t)
             linked = link >= 0
@@ -355,12 +506,19 @@ def link_levels(levels, search_range, memory=0, engine='host', device=0, adaptiv
                 order = np.lexsort(pos[new].T[::-1])
                 ids[new[order]] = next_id + np.arange(len(new))
                 next_id += len(new)
+            if pred is not None:
+                w = _level_velocity(pred[0], pos, link, all_src_pos, all_src_t, t, sr, pred[1], u_prev)
+                if pred[0] == _abi.LINK_PREDICT_DRIFT and linked.any():
+                    u_prev = w[0]
             # memory bookkeeping (find_link.py:716-732)
             if memory > 0:
                 used = np.zeros(n_src, dtype=bool)
                 used[link[linked]] = True
                 lost_new = ~used[:len(src_pos)]
                 keep_mem = ~used[len(src_pos):] & (mem_age + 1 < memory)
+                if pred is not None:
+                    mem_w = np.concatenate([mem_w[keep_mem], src_w[lost_new]])
+                    mem_t = np.concatenate([mem_t[keep_mem], np.full(int(lost_new.sum()), t - 1, dtype=np.int64)])
                 mem_pos = np.concatenate([mem_pos[keep_mem], src_pos[lost_new]])
                 mem_id = np.concatenate([mem_id[keep_mem], src_id[lost_new]])
                 mem_age = np.concatenate([mem_age[keep_mem] + 1,
@@ -368,15 +526,21 @@ def link_levels(levels, search_range, memory=0, engine='host', device=0, adaptiv
         ids_out.append(ids)
         rounds_out.append(rounds)
         src_pos, src_id = pos, ids
-    return (ids_out, rounds_out) if diag else ids_out
+        if pred is not None:
+            vel_out.append(w)
+            src_w = w
+    out = [ids_out] + ([rounds_out] if diag else []) + ([vel_out] if want_velocity else [])
+    return tuple(out) if len(out) > 1 else out[0]
 
 
 def link(f, search_range, memory=0, pos_columns=None, t_column='frame', engine='host', device=0, adaptive_stop=None,
-         adaptive_step=0.95, diag=False):
+         adaptive_step=0.95, diag=False, predictor=None, initial_velocity=None, want_velocity=False):
     """Return a copy of ``f`` (sorted by frame) with a ``particle`` column.  ``engine='device'``
     links on the MI355X (:func:`link_arrays`); the host path is the default.  ``adaptive_stop``,
     ``adaptive_step``: the adaptive search range of the module text; ``diag`` adds the column
-    ``adaptive_round``."""
+    ``adaptive_round``.  ``predictor``, ``initial_velocity``: the prediction of the module text, time
+    counted in the frames that have rows; ``want_velocity`` adds one column ``v<pos column>`` per
+    axis."""
     _check_engine(engine)
     if pos_columns is None:
         pos_columns = guess_pos_columns(f)
@@ -385,12 +549,18 @@ def link(f, search_range, memory=0, pos_columns=None, t_column='frame', engine='
     pos = result[pos_columns].values
     uniq, starts = np.unique(frames, return_index=True)
     stops = np.r_[starts[1:], len(frames)]
-    ids = link_levels([pos[a:b] for a, b in zip(starts, stops)], search_range, memory, engine, device,
-                      adaptive_stop, adaptive_step, diag)
-    rounds = None
-    if diag:
-        ids, rounds = ids
+    if len(starts) == 0:
+        _predict_plan(predictor, initial_velocity, want_velocity, len(pos_columns))
+    out = link_levels([pos[a:b] for a, b in zip(starts, stops)], search_range, memory, engine, device,
+                      adaptive_stop, adaptive_step, diag, predictor, initial_velocity, want_velocity)
+    out = list(out) if (diag or want_velocity) else [out]
+    ids = out.pop(0)
     result['particle'] = np.concatenate(ids) if len(ids) else np.zeros(0, dtype=np.int64)
     if diag:
+        rounds = out.pop(0)
         result['adaptive_round'] = np.concatenate(rounds) if len(rounds) else np.zeros(0, dtype=np.int32)
+    if want_velocity:
+        vel = np.concatenate(out.pop(0)) if len(ids) else np.zeros((0, len(pos_columns)))
+        for a, name in enumerate(pos_columns):
+            result['v' + name] = vel[:, a]
     return result

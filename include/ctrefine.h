@@ -556,6 +556,65 @@ typedef struct ctr_link_adaptive {
 } ctr_link_adaptive;
 int ctr_link_adaptive_device(ctr_handle* h, const ctr_link_adaptive* l, void* hip_stream);
 
+/* ctr_link_device for a sample that moves (link.py states the same rule): a track is
+ * looked for where it is expected to be, not where it last was.  The rule is the project's own,
+ * after trackpy's nearest-velocity and drift predictors; parity with trackpy is not pinned.
+ * Every row i of level t(i) gets a velocity w_i [ndim] in pixels per level once the links of its
+ * level are decided.  v0 is initial_velocity.
+ *   own velocity of a linked row: for a row i of level t that is linked to source row s of level
+ *     t_s, q_i[a] = (p_i[a] - p_s[a]) / (double)(t - t_s): one subtraction and one division.
+ *   CTR_LINK_PREDICT_VELOCITY: level 0: w_i = v0.  A linked row: w_i = q_i.  An unlinked row (a
+ *     birth) takes w_j of the linked row j of the same level that is nearest in scaled coordinates:
+ *     the scaled distance is sum_a (p_i[a] / sr[a] - p_j[a] / sr[a])^2, summed in axis order; a tie
+ *     goes to the lower row; there is no distance limit.  If the level has no linked row, the birth
+ *     takes v0.
+ *   CTR_LINK_PREDICT_DRIFT: one vector per level, u_0 = v0.  For level t >= 1 with M linked rows:
+ *     u_t[a] = S_a / M if M > 0, otherwise u_t = u_{t-1}.  S_a is summed in this fixed order:
+ *     partial sum l of 256 starts at 0. and adds q_i[a] of the linked rows among rows
+ *     r0 + l, r0 + l + 256, .. of the level (r0: its first row), in ascending order; then for
+ *     h = 128, 64, .., 1: part[l] += part[l + h] for l < h; S_a = part[0].
+ *     w_i = u_t for every row of level t.
+ *   prediction: source s (a row of level t_s, the previous level or a remembered one) is offered to
+ *     level t at the predicted position P_s.  VELOCITY: P_s[a] = p_s[a] + w_s[a] * (double)(t - t_s);
+ *     DRIFT: the same with u_{t-1}[a] in place of w_s[a].  One multiplication, then one addition,
+ *     with no contraction.  P_s[a] / sr[a] takes the place of p_s[a] / sr[a] in the candidate
+ *     search, and so in the d2 that is stored.
+ *   everything else is unchanged: the ten nearest candidates, the 1 + 1e-7 bound, sub-networks, the
+ *     exact solver, the limits CTR_LINK_MAX_SOURCES and CTR_LINK_MAX_DESTINATIONS, birth order, ids
+ *     and memory.  A remembered source still leaves after `memory` levels; what changes is that it
+ *     is predicted forward by its age.
+ *   the adaptive range (max_rounds >= 1: the fields and the rule of ctr_link_adaptive;
+ *     max_rounds == 0: none, stop_rel, step and adaptive_round are not looked at) composes with
+ *     prediction: the rounds work on the d2 of the predicted positions.
+ *   limits of the rule: time is counted in levels, and a level without rows is a level.  Without
+ *     an initial_velocity, a sample that already moves beyond the range at level 1 never acquires a
+ *     velocity: nothing links, and a level without linked rows passes v0 on.
+ * velocity (may be NULL) receives w, [N, ndim].  The call is always queued level by level, as
+ * ctr_link_device with memory > 0; the host waits for nothing in between.  Status, scratch and
+ * streams as ctr_link_device.  The descriptor is checked before the handle: ctr_link's checks, the
+ * adaptive fields as above, predictor one of the two, initial_velocity finite. */
+enum { CTR_LINK_PREDICT_VELOCITY = 1, CTR_LINK_PREDICT_DRIFT = 2 };
+typedef struct ctr_link_predict {
+  int32_t ndim;                /* the fields of ctr_link_adaptive */
+  int32_t memory;
+  int64_t n_levels;
+  int64_t n_features;
+  double search_range[CTR_MAX_NDIM];
+  const double* pos;
+  const int64_t* frame_offset;
+  int64_t* particle;
+  int64_t* n_tracks;
+  int32_t* status;
+  double stop_rel;
+  double step;
+  int32_t max_rounds;          /* 0: no adaptive range; else 1 .. CTR_LINK_MAX_ROUNDS */
+  int32_t* adaptive_round;     /* [N] out, or NULL */
+  int32_t predictor;           /* CTR_LINK_PREDICT_* */
+  double initial_velocity[CTR_MAX_NDIM]; /* v0, pixels per level */
+  double* velocity;            /* [N, ndim] out, or NULL */
+} ctr_link_predict;
+int ctr_link_predict_device(ctr_handle* h, const ctr_link_predict* l, void* hip_stream);
+
 /* Relocation candidates of lost features on the device: the rule of the reference's
  * FindLinker.get_relocate_candidates (find_link.py:811-867), the look-again step that
  * makes find_link more than locate followed by link.  The loop around it (shortage per sub-network,
