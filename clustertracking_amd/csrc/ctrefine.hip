@@ -17,9 +17,9 @@
 //   refine_tail_kernel    CTR_FLAG_THROUGHPUT: the likely slow pairs and 3-10-feature clusters of a call
 //                         in one launch, each fitted by the statements of its bin's own kernel
 //   find_clusters_kernel  cluster labelling of a frame (find.py:72-93)
-// Clusters are binned by problem size on the host (ctr_plan_create); the bins run
-// concurrently on the lanes of the device (lane_sched.h).  gfx950 only; no CUDA paths, no CPU
-// fallback.
+// Clusters are binned by problem size on the host, and the launches of a call decided, once per
+// plan (ctr_plan_create, refine_plan.h); the bins run concurrently on the lanes of the device
+// (lane_sched.h).  gfx950 only; no CUDA paths, no CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,6 +36,7 @@
 
 #include "kargs.h"
 #include "lane_sched.h"
+#include "refine_plan.h"
 
 namespace {
 
@@ -51,42 +52,10 @@ std::mutex g_mutex;
 
 }  // namespace
 
-// bins: 0..MAXNT-1 generic kernel by NT-1; MAXNT = beyond the engine (see CTR_STATUS_TOO_LARGE);
-// MAXNT+1 / MAXNT+2 = singles / pairs with default modes (small kernel); MAXNT+3 = large
-// clusters (more than MAXF features or 16 MAXNT columns: refine_large_kernel)
-// MAXNT+4 / MAXNT+5 = clusters with equality constraints, NT = 1 / 2 (their own instantiation of
-// the block kernel)
-constexpr int BIN_TOO_LARGE = MAXNT, BIN_SMALL1 = MAXNT + 1, BIN_SMALL2 = MAXNT + 2, BIN_LARGE = MAXNT + 3,
-              BIN_CONS1 = MAXNT + 4, BIN_CONS2 = MAXNT + 5, NBINS = MAXNT + 6;
-static_assert(NBINS <= 16, "FrontArgs (aux_kernels.h) holds 16 bins");
-// slots of the handle's kernel table (ctr_handle::kernels): a block family's NT 1..8 at nt - 1 and
-// its constrained NT 1..2 at MAXNT + nt - 1; the small kernel's tiers; the large kernel's one at 0
-constexpr int NFAM = CTR_KFAM_LARGE_LOWPASS + 1, NSLOT = MAXNT + 2;
-constexpr int SLOT_SINGLES8 = 0, SLOT_SINGLES64 = 1, SLOT_PAIRS64 = 2, SLOT_PAIRS16 = 3;
-// pixels of a single-feature window up to which singles take 8 lanes (else 64) and a bin of pairs
-// may run in two tiers (ctr_plan_create)
-constexpr int64_t NARROW_WINDOW = 600;
+using namespace refine_plan;   // the bins, slots and launches of a plan, and their decision
+
+constexpr int NFAM = CTR_KFAM_LARGE_LOWPASS + 1;   // families of the handle's kernel table (ctr_handle::kernels)
 constexpr int GATE_US = 20;  // head start of the block kernels over the small kernels (delay_kernel)
-// launches of a call that are chains of their own on the lanes: one per bin, the bulk tier of
-// the pairs, and the tail launch
-constexpr int LAUNCH_PAIRS16 = NBINS, LAUNCH_TAIL = NBINS + 1, NLAUNCH = NBINS + 2;
-// Most workgroups that a bin has in the tail launch (tail_kernel.h).  They share the bin's entries
-// of that launch, however many, through a counter.  It bounds the grid of a launch whose count is
-// known on the device only: the shards of the benchmark (cfg 2) have at most 110 likely slow
-// clusters in a bin, and 3 * 256 workgroups that find nothing to do cost a few microseconds.
-constexpr int TAIL_CAP = 256;
-// A block bin (NT = 1, 2) of at most this many clusters is fitted whole by the tail launch and has
-// no launch of its own: its workgroups would run no faster there, and the launch would hold a
-// queue as long as the bin's slowest far cluster.  The default of ctr_set_tail_absorb, fixed by
-// measurement (profiles/tail_absorb_sweep.json): a bin of 6 440 3-4-feature
-// clusters still gains from it, and at about 32 fits of 5-10 features per workgroup the tail
-// launch would begin to outlast the slow fits it exists for.
-constexpr int TAIL_ABSORB = 32 * TAIL_CAP;
-// One tier of pairs (fewer than 64, or wide windows) is fitted whole by the tail launch up to this
-// many: beyond it a bin of wide-window pairs is no work for TAIL_CAP wavefronts.
-constexpr int TAIL_PAIRS_WHOLE = 8 * TAIL_CAP;
-// the bins that a tail launch draws from, in the order of its segments (kargs.h: TailArgs)
-constexpr int TAIL_BINS[TAIL_SEGMENTS] = {BIN_SMALL2, 0, 1};
 
 // The duration of one launch of a plan, for the placement of its next call (lane_sched.h): a pair
 // of timing events around the kernel, read back without blocking once both have completed.  While
@@ -112,25 +81,10 @@ struct ctr_plan {
   long long* d_ws_off = nullptr;   // [n_clusters] offset in doubles (0 for the other clusters)
   mutable int large_epoch = 0;     // launches of the large kernel on this plan (tags its leader / helper words)
   mutable LaunchTiming timing[NLAUNCH];   // guarded by the mutex of the device's lane pool
-  int64_t bin_begin[NBINS + 1] = {0};
-  int64_t bin_count[NBINS] = {0};
-  // choose_kernel's family and table slot of each bin (the same for every cluster of a bin)
-  int32_t bin_family[NBINS] = {0};
-  int32_t bin_slot[NBINS] = {0};
-  // what the launch does besides, decided from the problem and the bin counts (ctr_plan_create)
-  bool gate = false;          // the small kernels start GATE_US after the others (delay_kernel)
-  bool pairs_split = false;   // the pairs bin runs in two tiers, 16 and 64 lanes per pair
-  // the likely slow fits of the pairs and of the block bins NT = 1, 2 run in one launch of
-  // refine_tail_kernel, of tail_grid workgroups
-  bool tail_fused = false;
-  int tail_grid = 0;
-  // per segment of a fused plan (kargs.h: TailArgs): the tail launch fits the whole bin / the bin's
-  // own launch (pairs: the 64-lane one) is queued.  Not fused: none whole, every non-empty bin its own
-  bool tail_whole[TAIL_SEGMENTS] = {false, false, false};
-  bool tail_own[TAIL_SEGMENTS] = {false, false, false};
-  int large_workgroups = 0;   // per large cluster, leader included
-  // lowpass of the window (ctr_problem.noise_size): taps per axis on the device (kargs.h: lp_w)
-  bool lowpass = false;
+  // the bins and every launch of a call, decided once (refine_plan.h: make_plan); a call only
+  // places and enqueues them
+  RefinePlan rp;
+  // lowpass of the window (rp.lowpass; ctr_problem.noise_size): taps per axis on the device (kargs.h: lp_w)
   double* d_lp_w = nullptr;
   int lp_half[3] = {0, 0, 0};
 };
@@ -396,15 +350,6 @@ int gaussian_taps(double sigma, double* w) {
   return lw;
 }
 
-int n_vars(const ctr_problem* p, int n) {
-  int nv = 0;
-  for (int k = 0; k < p->n_params; ++k) {
-    if (p->modes[k] == CTR_MODE_VAR) nv += n;
-    else if (p->modes[k] != CTR_MODE_CONST) nv += 1;
-  }
-  return nv;
-}
-
 // at least `need` bytes in sc.  A block that grows is replaced once the device is idle: a kernel
 // of an earlier call, on whichever stream, may still use the old one.
 int reserve(ctr_handle* h, Scratch& sc, size_t need, const char* or_else) {
@@ -465,88 +410,6 @@ int launch_frame_max(ctr_handle* h, const void* frames, int dtype, int64_t n_fra
   if (too_large) return fail(h, CTR_ERR_INVALID, "frame block too large for one launch");
   HIP_TRY(h, e);
   return CTR_OK;
-}
-
-// a lowpass of the window (ctr_problem.noise_size / CTR_FLAG_WINDOW_FILTER; noise_size given
-// with every sigma 0: the reference's lowpass is then its threshold alone)
-bool lowpass_of(const ctr_problem* p) {
-  bool lp = (p->flags & CTR_FLAG_WINDOW_FILTER) != 0;
-  for (int a = 0; a < p->ndim; ++a) lp = lp || p->noise_size[a] > 0.;
-  return lp;
-}
-
-// pixels of a single-feature window (and of a mask's bounding box)
-int64_t window_volume(const ctr_problem* p) {
-  int64_t vol = 1;
-  for (int a = 0; a < p->ndim; ++a) vol *= 2 * (int64_t)p->radius[a] + 1;
-  return vol;
-}
-
-// The per-cluster decision of ctr_plan_create: the bin, and the cell of the handle's kernel table
-// that the bin is launched with (family, slot).  p is validated, n >= 0.
-struct KernelChoice { int bin, family, slot; };
-
-KernelChoice choose_kernel(const ctr_problem* p, int64_t n) {
-  // singles / pairs with the default modes (fitfunc.py:356,379-387) go to the small kernel
-  bool default_modes = p->modes[0] == CTR_MODE_CLUSTER && p->modes[1] == CTR_MODE_VAR;
-  for (int a = 0; a < p->ndim; ++a) default_modes = default_modes && p->modes[2 + a] == CTR_MODE_VAR;
-  for (int k2 = 2 + p->ndim; k2 < p->n_params; ++k2) default_modes = default_modes && p->modes[k2] == CTR_MODE_CONST;
-  int npf = 0, nsh = 0;   // per-feature / shared variables
-  for (int k2 = 0; k2 < p->n_params; ++k2) {
-    if (p->modes[k2] == CTR_MODE_VAR) ++npf;
-    else if (p->modes[k2] != CTR_MODE_CONST) ++nsh;
-  }
-  const bool lowpass = lowpass_of(p);
-  // (the lowpass lives in its own instantiations of the block kernel: every cluster goes there)
-  if (lowpass) default_modes = false;
-  // (so do the ring / disc profiles; clusters beyond the block kernel get status 5 there)
-  const bool other_profile = p->fit_function != CTR_FIT_GAUSS;
-  if (other_profile) default_modes = false;
-  int bin;
-  const bool constrained = (p->constraint_kind == CTR_CONS_DIMER && n == 2);
-  const bool any_cons = (p->constraint_kind == CTR_CONS_DIMER && n == 2) ||
-                        (p->constraint_kind == CTR_CONS_TRIMER && n == 3) ||
-                        (p->constraint_kind == CTR_CONS_TETRAMER && n == 4);
-  if (n > 0x3fffffLL) bin = BIN_TOO_LARGE;
-  else if (n > MAXF) bin = BIN_LARGE;
-  else if (default_modes && n == 1) bin = BIN_SMALL1;
-  else if (default_modes && n == 2 && !constrained) bin = BIN_SMALL2;
-  else {
-    const int nv = n_vars(p, (int)n);
-    const int nt = (nv + 1 + 15) / 16;
-    bin = nt > MAXNT ? BIN_LARGE : (nt < 1 ? 0 : nt - 1);
-    if (bin < MAXNT && n > (16 * (bin + 1) < MAXF ? 16 * (bin + 1) : MAXF)) bin = BIN_LARGE;
-    if (any_cons && bin < 2) bin = bin == 0 ? BIN_CONS1 : BIN_CONS2;   // (at most 29 variables)
-    else if (any_cons && bin < MAXNT) bin = BIN_TOO_LARGE;             // (ring / disc with every column free)
-  }
-  if (bin == BIN_LARGE) {
-    // the large kernel's 16-column row: [r, shared.., own.., r_o, shared_o..]
-    bool wide_mask = false;   // (its list of mask pixels packs box coordinates in 10 bits per axis)
-    for (int a = 0; a < p->ndim; ++a) wide_mask = wide_mask || p->radius[a] > 500;
-    if (npf < 1 || 2 + 2 * nsh + npf > 16 || other_profile || wide_mask) bin = BIN_TOO_LARGE;
-  }
-  // which table the kernel comes from, and its slot there
-  int fam = CTR_KFAM_NONE;
-  if (bin == BIN_SMALL1 || bin == BIN_SMALL2) fam = CTR_KFAM_SMALL;
-  else if (bin == BIN_LARGE) fam = lowpass ? CTR_KFAM_LARGE_LOWPASS : CTR_KFAM_LARGE;
-  else if (bin != BIN_TOO_LARGE) {
-    if (p->fit_function == CTR_FIT_RING) fam = CTR_KFAM_RING;
-    else if (p->fit_function == CTR_FIT_DISC) fam = CTR_KFAM_DISC;
-    else if (p->fit_function == CTR_FIT_INV_SERIES) fam = CTR_KFAM_INV_SERIES;
-    else if (lowpass) fam = CTR_KFAM_LOWPASS;
-    // (2D only: a 3D window has thousands of pixels, more wavefronts per cluster pay there)
-    else if ((p->flags & CTR_FLAG_THROUGHPUT) != 0 && p->ndim == 2) fam = CTR_KFAM_GAUSS_TP;
-    else fam = CTR_KFAM_GAUSS;
-  }
-  int slot = 0;
-  if (bin < MAXNT) slot = bin;
-  else if (bin == BIN_CONS1 || bin == BIN_CONS2) slot = MAXNT + (bin == BIN_CONS2);
-  // singles: 8 lanes per cluster (eight clusters per wavefront: the solve, replicated in the lanes
-  // of a group, is shared by as many) while a window is a few passes, 64 once it is thousands of
-  // pixels (3D); pairs 64
-  else if (bin == BIN_SMALL1) slot = window_volume(p) > NARROW_WINDOW ? SLOT_SINGLES64 : SLOT_SINGLES8;
-  else if (bin == BIN_SMALL2) slot = SLOT_PAIRS64;
-  return KernelChoice{bin, fam, slot};
 }
 
 // The instantiation of one cell of the kernel table (ctr_create); {nullptr} where there is none.
@@ -690,98 +553,25 @@ int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
   if (rc) return fail(h, rc, msg);
   if (n_clusters < 0 || (n_clusters > 0 && !feat_offset_host)) return fail(h, CTR_ERR_INVALID, "bad cluster table");
   if (n_clusters > 0x7ffffff0LL) return fail(h, CTR_ERR_INVALID, "too many clusters for one batch");
-  std::vector<int32_t> bin_of((size_t)n_clusters);
   ctr_plan* plan = new ctr_plan();
   plan->prob = *p;
   plan->n_clusters = n_clusters;
   plan->device = h->device;
-  // (the lowpass lives in its own instantiations of the block kernel: ctr_cluster_kernel)
-  plan->lowpass = lowpass_of(p);
+  std::vector<int32_t> order, bin_of;
+  if (const char* why = make_plan(p, n_clusters, feat_offset_host, h->tail_absorb, &plan->rp, &order, &bin_of)) {
+    delete plan;
+    return fail(h, CTR_ERR_INVALID, why);
+  }
+  // the workspace of the large clusters (large_ws), one after the other
   std::vector<long long> ws_off((size_t)n_clusters, 0);
   long long ws_total = 0;
-  const long long box_cap = window_volume(p);   // pixels of a mask's bounding box (large_ws)
-  int npf = 0, nsh = 0;   // per-feature / shared variables
-  for (int k2 = 0; k2 < p->n_params; ++k2) {
-    if (p->modes[k2] == CTR_MODE_VAR) ++npf;
-    else if (p->modes[k2] != CTR_MODE_CONST) ++nsh;
-  }
-  for (int64_t c = 0; c < n_clusters; ++c) {
-    const int64_t n = (int64_t)feat_offset_host[c + 1] - feat_offset_host[c];
-    if (n < 0) { delete plan; return fail(h, CTR_ERR_INVALID, "feat_offset must be non-decreasing"); }
-    const KernelChoice kc = choose_kernel(p, n);
-    const int bin = kc.bin;
-    if (bin == BIN_LARGE) {
+  if (plan->rp.bin_count[BIN_LARGE] > 0) {
+    const int nsh = n_vars(p, 0), npf = n_vars(p, 1) - nsh;   // shared / per-feature variables
+    for (int64_t c = 0; c < n_clusters; ++c) {
+      if (bin_of[(size_t)c] != BIN_LARGE) continue;
       ws_off[(size_t)c] = ws_total;
-      ws_total += large_ws((int)n, npf, nsh, box_cap).total;
+      ws_total += large_ws(feat_offset_host[c + 1] - feat_offset_host[c], npf, nsh, window_volume(p)).total;
     }
-    // (family and slot depend on the problem alone: the launch takes them from the plan)
-    if (plan->bin_count[bin] == 0) { plan->bin_family[bin] = kc.family; plan->bin_slot[bin] = kc.slot; }
-    else if (plan->bin_family[bin] != kc.family || plan->bin_slot[bin] != kc.slot) {
-      delete plan;
-      return fail(h, CTR_ERR_INVALID, "internal: clusters of one bin with different kernels");
-    }
-    bin_of[(size_t)c] = bin;
-    plan->bin_count[bin]++;
-  }
-  plan->bin_begin[0] = 0;
-  for (int b = 0; b < NBINS; ++b) plan->bin_begin[b + 1] = plan->bin_begin[b] + plan->bin_count[b];
-  const bool throughput = (p->flags & CTR_FLAG_THROUGHPUT) != 0;
-  // the small kernels start a little later than the block and large kernels, if any (delay_kernel)
-  plan->gate = n_clusters > plan->bin_count[BIN_SMALL1] + plan->bin_count[BIN_SMALL2] + plan->bin_count[BIN_TOO_LARGE];
-  // Pairs in two tiers (CTR_FLAG_THROUGHPUT: +9 % with four batches in flight, but the
-  // one-batch-at-a-time step gets 12 % longer).  One wavefront per pair gives the shortest
-  // iteration, which is what the slow fits need; for the rest, four pairs per wavefront cost a
-  // third of the machine time.
-  plan->pairs_split = throughput && plan->bin_count[BIN_SMALL2] >= 64 && box_cap <= NARROW_WINDOW;
-  // One tail launch for the likely slow fits of the pairs and of the block bins NT = 1, 2
-  // (tail_kernel.h), where queue time is what counts (CTR_FLAG_THROUGHPUT) and at least two of
-  // them would otherwise hold a queue each.  Only the bins whose kernels the tail kernel holds:
-  // 2D, no lowpass, the throughput table of the gaussian.
-  {
-    int nonempty = 0;
-    bool family_ok = true;
-    for (int sgm = 0; sgm < TAIL_SEGMENTS; ++sgm) {
-      const int bin = TAIL_BINS[sgm];
-      if (plan->bin_count[bin] == 0) continue;
-      ++nonempty;
-      if (bin < MAXNT && plan->bin_family[bin] != CTR_KFAM_GAUSS_TP) family_ok = false;
-      plan->tail_grid += (int)std::min<int64_t>(plan->bin_count[bin], TAIL_CAP);
-    }
-    plan->tail_fused = throughput && p->ndim == 2 && !plan->lowpass && family_ok && nonempty >= 2;
-    if (!plan->tail_fused) plan->tail_grid = 0;
-    // What the tail launch takes of a bin, and whether the bin keeps a launch of its own.  Pairs:
-    // every pair of the 64-lane tier -- the close ones with two tiers, all of them with one -- so
-    // that launch is never queued.  (One tier is for fewer than 64 pairs or wide windows; a bin of
-    // more than TAIL_PAIRS_WHOLE wide-window pairs is no work for TAIL_CAP wavefronts and keeps its
-    // launch for all but the close ones, whatever the handle's setting.)  A block bin of at most
-    // tail_absorb clusters: all of it; a larger one: the close clusters, the bin's launch fits the
-    // others.
-    for (int sgm = 0; sgm < TAIL_SEGMENTS; ++sgm) {
-      const int64_t cnt = plan->bin_count[TAIL_BINS[sgm]];
-      const bool whole = sgm == 0 ? !plan->pairs_split && cnt <= TAIL_PAIRS_WHOLE : cnt <= (int64_t)h->tail_absorb;
-      plan->tail_whole[sgm] = plan->tail_fused && cnt > 0 && whole;
-      plan->tail_own[sgm] = cnt > 0 && !(plan->tail_fused && (whole || (sgm == 0 && plan->pairs_split)));
-    }
-  }
-  if (plan->bin_count[BIN_LARGE] > 0) {
-    // a leader workgroup of 512 threads per cluster + helpers for its pixel passes
-    // (large_kernel.h): as many as fill the machine, none when the clusters alone do.
-    // (Several batches in flight fill the machine by themselves: a waiting helper would only hold
-    //  the compute unit that another batch's leader needs.)
-    const int64_t per_cluster = 512 / plan->bin_count[BIN_LARGE];
-    plan->large_workgroups = throughput ? 1 : (int)(per_cluster < 1 ? 1 : (per_cluster > 8 ? 8 : per_cluster));
-  }
-  std::vector<int32_t> order((size_t)n_clusters);
-  {
-    int64_t cursor[NBINS];
-    for (int b = 0; b < NBINS; ++b) cursor[b] = plan->bin_begin[b];
-    for (int64_t c = 0; c < n_clusters; ++c) order[(size_t)cursor[bin_of[(size_t)c]]++] = (int32_t)c;
-    // inside a generic bin the clusters with the most features start first
-    for (int b = 0; b < MAXNT; ++b)
-      std::stable_sort(order.begin() + plan->bin_begin[b], order.begin() + plan->bin_begin[b + 1],
-                       [&](int32_t x, int32_t y) {
-                         return feat_offset_host[x + 1] - feat_offset_host[x] > feat_offset_host[y + 1] - feat_offset_host[y];
-                       });
   }
   if (n_clusters > 0) {
     if (hipSetDevice(h->device) != hipSuccess ||
@@ -794,7 +584,7 @@ int ctr_plan_create(ctr_handle* h, const ctr_problem* p, int64_t n_clusters,
       ctr_plan_destroy(plan);
       return fail(h, CTR_ERR_DEVICE, "cannot upload the plan");
     }
-    if (plan->lowpass) {
+    if (plan->rp.lowpass) {
       std::vector<double> taps(3 * LP_STRIDE, 0.);
       for (int a = 0; a < p->ndim; ++a) {
         if (p->noise_size[a] > 0.) plan->lp_half[a] = gaussian_taps(p->noise_size[a], taps.data() + a * LP_STRIDE);
@@ -840,17 +630,17 @@ void ctr_plan_destroy(ctr_plan* plan) {
 
 int ctr_plan_tail(const ctr_plan* plan, int32_t* fused, int32_t* cap, int32_t* tail_grid) {
   if (!plan) return CTR_ERR_INVALID;
-  if (fused) *fused = plan->tail_fused ? 1 : 0;
+  if (fused) *fused = plan->rp.tail_fused ? 1 : 0;
   if (cap) *cap = TAIL_CAP;
-  if (tail_grid) *tail_grid = plan->tail_grid;
+  if (tail_grid) *tail_grid = plan->rp.tail_grid;
   return CTR_OK;
 }
 
 int ctr_plan_tail_bins(const ctr_plan* plan, int32_t* absorbed, int32_t* own_launch) {
   if (!plan) return CTR_ERR_INVALID;
   for (int sgm = 0; sgm < TAIL_SEGMENTS; ++sgm) {
-    if (absorbed) absorbed[sgm] = plan->tail_whole[sgm] ? 1 : 0;
-    if (own_launch) own_launch[sgm] = plan->tail_own[sgm] ? 1 : 0;
+    if (absorbed) absorbed[sgm] = plan->rp.tail_whole[sgm] ? 1 : 0;
+    if (own_launch) own_launch[sgm] = plan->rp.tail_own[sgm] ? 1 : 0;
   }
   return CTR_OK;
 }
@@ -905,29 +695,33 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
   // near the solution (with the aggregated preconditioner 1e-8 far saves 12 % and costs parity:
   // 6e-7 vs 5e-8 px against the oracle)
   constexpr double LARGE_CG_TOL2_FAR = 1e-12, LARGE_CG_TOL2_NEAR = 1e-22;
-  KArgs k;
-  std::memset(&k, 0, sizeof k);   // (split = nullptr: a launch takes its whole bin)
-  k.prob = p;
-  k.frames = b->frames;
-  k.frame_dtype = b->frame_dtype;
-  for (int a = 0; a < 3; ++a) k.shape[a] = a < p.ndim ? b->shape[a] : 1;
-  k.frame_elems = frame_elems;
-  k.frame_index = b->frame_index;
-  k.feat_offset = b->feat_offset;
-  k.params = b->params;
-  k.low = b->low;
-  k.high = b->high;
-  k.params_out = b->params_out;
-  k.cost = b->cost;
-  k.status = b->status;
-  k.n_rounds = b->n_rounds;
-  k.n_iter = b->n_iter;
-  k.params_std = b->params_std;
-  k.fmax = (const double*)h->fmax.ptr;
-  k.lp_w = plan->lowpass ? plan->d_lp_w : nullptr;
-  k.cg_tol2_far = LARGE_CG_TOL2_FAR;
-  k.cg_tol2_near = LARGE_CG_TOL2_NEAR;
-  for (int a = 0; a < 3; ++a) k.lp_half[a] = plan->lp_half[a];
+  // what every launch of the call gets; a launch adds its bin and its part of it (LaunchSpec)
+  const KArgs base = [&] {
+    KArgs k;
+    std::memset(&k, 0, sizeof k);   // (no order, n_bin 0; split = nullptr: a launch takes its whole bin)
+    k.prob = p;
+    k.frames = b->frames;
+    k.frame_dtype = b->frame_dtype;
+    for (int a = 0; a < 3; ++a) k.shape[a] = a < p.ndim ? b->shape[a] : 1;
+    k.frame_elems = frame_elems;
+    k.frame_index = b->frame_index;
+    k.feat_offset = b->feat_offset;
+    k.params = b->params;
+    k.low = b->low;
+    k.high = b->high;
+    k.params_out = b->params_out;
+    k.cost = b->cost;
+    k.status = b->status;
+    k.n_rounds = b->n_rounds;
+    k.n_iter = b->n_iter;
+    k.params_std = b->params_std;
+    k.fmax = (const double*)h->fmax.ptr;
+    k.lp_w = plan->rp.lowpass ? plan->d_lp_w : nullptr;
+    k.cg_tol2_far = LARGE_CG_TOL2_FAR;
+    k.cg_tol2_near = LARGE_CG_TOL2_NEAR;
+    for (int a = 0; a < 3; ++a) k.lp_half[a] = plan->lp_half[a];
+    return k;
+  }();
   const int ii = p.isotropic ? 1 : 0;
   // From here on the pool's mutex is held: the plan's timing entries (their guesses included) and
   // the lanes' books belong to it.  An error return in the middle of the enqueue (HIP_TRY) leaves
@@ -949,160 +743,57 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     std::function<hipError_t(hipStream_t)> run;
   };
   std::vector<Chain> chains;
-  auto guess = [&](int launch, lane_sched::ChainClass cls, int64_t count, int nt) {
-    plan->timing[launch].est.guess = lane_sched::static_guess(cls, count, nt);
-  };
-  // block bins: NT 8 -> 1, then the constrained NT 2 -> 1
-  for (int i = 0; i < MAXNT + 2; ++i) {
-    const int bin = i < MAXNT ? MAXNT - 1 - i : (i == MAXNT ? BIN_CONS2 : BIN_CONS1);
-    const int64_t cnt = plan->bin_count[bin];
-    if (cnt == 0) continue;
-    const KernelInfo* ki;
-    rc = table_kernel(h, plan->bin_family[bin], p.ndim, ii, plan->bin_slot[bin], &ki);
-    if (rc) return rc;
-    k.order = ord + plan->bin_begin[bin];
-    k.n_bin = (int32_t)cnt;
-    // (with a tail launch: a bin that it fits whole has no launch; of another, it takes the close
-    // clusters, all of them, and the workgroups of those entries return at once)
-    const bool in_tail = plan->tail_fused && (bin == TAIL_BINS[1] || bin == TAIL_BINS[2]);
-    if (in_tail && !plan->tail_own[bin == TAIL_BINS[1] ? 1 : 2]) continue;
-    k.split = in_tail ? plan->d_front + 2 * bin : nullptr;
-    k.split_cap = in_tail ? INT32_MAX : 0;
-    guess(bin, lane_sched::CHAIN_BLOCK, cnt, bin < MAXNT ? bin + 1 : (bin == BIN_CONS2 ? 2 : 1));
-    chains.push_back({bin, false, [k, ki, cnt](hipStream_t st) {
-      void* kargs[] = {(void*)&k};
-      return hipLaunchKernel(ki->fn, dim3((unsigned)cnt), dim3((unsigned)ki->threads), kargs, ki->smem, st);
-    }});
-    k.split = nullptr;
-    k.split_cap = 0;
-  }
-  // the tail launch: ungated, it carries workgroups with much LDS like the block kernels
-  if (plan->tail_fused) {
-    const KernelInfo* ki = &h->tail[ii];
-    if (!ki->fn) return fail(h, CTR_ERR_DEVICE, "no tail kernel instantiated for this problem");
-    if (!h->tail_attr_set[ii]) {
-      HIP_TRY(h, hipFuncSetAttribute(ki->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ki->smem));
-      h->tail_attr_set[ii] = true;
+  // Which launches, with which grid, gate, counter and part of a bin: the plan's list
+  // (refine_plan.h), in the order in which the placement gets them.
+  const RefinePlan& rp = plan->rp;
+  for (const LaunchSpec& sp : rp.launches) {
+    const KernelInfo* ki = nullptr;
+    if (sp.kind == KIND_TAIL) {
+      ki = &h->tail[ii];
+      if (!ki->fn) return fail(h, CTR_ERR_DEVICE, "no tail kernel instantiated for this problem");
+      if (!h->tail_attr_set[ii]) {
+        HIP_TRY(h, hipFuncSetAttribute(ki->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ki->smem));
+        h->tail_attr_set[ii] = true;
+      }
+    } else if (sp.kind != KIND_MARK) {
+      rc = table_kernel(h, sp.family, p.ndim, ii, sp.slot, &ki);
+      if (rc) return rc;
     }
+    KArgs k = base;
+    k.order = sp.bin < 0 ? ord : ord + rp.bin_begin[sp.bin];
+    k.n_bin = sp.bin < 0 ? 0 : (int32_t)rp.bin_count[sp.bin];
+    k.split = sp.split ? plan->d_front + 2 * sp.bin : nullptr;
+    k.split_part = sp.split_part;
+    k.split_cap = sp.split_cap;
+    plan->timing[sp.launch].est.guess = lane_sched::static_guess(sp.cls, sp.count, sp.nt);
+    const int kind = sp.kind;
+    const bool delay = sp.delay_first;
+    const unsigned grid = (unsigned)sp.grid;
+    int* counter = sp.counter < 0 ? nullptr : h->d_counter + sp.counter;   // (the tail launch: one per segment)
     TailArgs ta;
     std::memset(&ta, 0, sizeof ta);
-    int32_t at = 0;
-    for (int sgm : {1, 2, 0}) {   // (the order of the segments in the grid: kargs.h)
-      const int bin = TAIL_BINS[sgm];
-      const int64_t cnt = plan->bin_count[bin];
-      ta.close[sgm] = cnt > 0 ? plan->d_front + 2 * bin : nullptr;
-      ta.ord_off[sgm] = (int32_t)plan->bin_begin[bin];
-      ta.whole[sgm] = plan->tail_whole[sgm] ? (int32_t)cnt : 0;
-      ta.grid_begin[sgm] = at;
-      at += (int32_t)std::min<int64_t>(cnt, TAIL_CAP);
+    for (int sgm = 0; kind == KIND_TAIL && sgm < TAIL_SEGMENTS; ++sgm) {
+      ta.close[sgm] = rp.bin_count[TAIL_BINS[sgm]] > 0 ? plan->d_front + 2 * TAIL_BINS[sgm] : nullptr;
+      ta.ord_off[sgm] = rp.tail.ord_off[sgm];
+      ta.whole[sgm] = rp.tail.whole[sgm];
     }
-    ta.grid_begin[TAIL_SEGMENTS] = at;
-    const unsigned grid = (unsigned)plan->tail_grid;
-    if (at != plan->tail_grid) return fail(h, CTR_ERR_DEVICE, "internal: the tail launch's grid differs from the plan's");
-    int* counter = h->d_counter + 4;   // (one work counter per segment: 4, 5, 6)
-    k.order = ord;
-    k.n_bin = 0;
-    guess(LAUNCH_TAIL, lane_sched::CHAIN_TAIL, (int64_t)grid, 1);
-    chains.push_back({LAUNCH_TAIL, false, [k, ki, ta, grid, counter](hipStream_t st) {
-      void* kargs[] = {(void*)&k, (void*)&ta, (void*)&counter};
-      return hipLaunchKernel(ki->fn, dim3(grid), dim3((unsigned)ki->threads), kargs, ki->smem, st);
-    }});
-  }
-  if (plan->bin_count[BIN_LARGE] > 0) {
-    const int64_t cnt = plan->bin_count[BIN_LARGE];
-    const KernelInfo* ki;
-    rc = table_kernel(h, plan->bin_family[BIN_LARGE], p.ndim, ii, plan->bin_slot[BIN_LARGE], &ki);
-    if (rc) return rc;
-    k.order = ord + plan->bin_begin[BIN_LARGE];
-    k.n_bin = (int32_t)cnt;
+    for (int sgm = 0; sgm <= TAIL_SEGMENTS; ++sgm) ta.grid_begin[sgm] = rp.tail.grid_begin[sgm];
     double* wsp = plan->d_ws;
     const long long* wso = plan->d_ws_off;
-    int epoch = ++plan->large_epoch;
-    const unsigned grid = (unsigned)(cnt * plan->large_workgroups);
-    guess(BIN_LARGE, lane_sched::CHAIN_LARGE, cnt, 1);
-    chains.push_back({BIN_LARGE, false, [k, ki, grid, wsp, wso, epoch](hipStream_t st) {
-      void* kargs[] = {(void*)&k, (void*)&wsp, (void*)&wso, (void*)&epoch};
+    const int epoch = kind == KIND_LARGE ? ++plan->large_epoch : 0;
+    chains.push_back({sp.launch, sp.gated, [=](hipStream_t st) {
+      if (delay) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, st, (unsigned long long)GATE_US * 100ull);
+      void* kargs[4] = {(void*)&k, nullptr, nullptr, nullptr};
+      switch (kind) {   // the kernel's arguments after KArgs
+        case KIND_BLOCK: break;
+        case KIND_SMALL: kargs[1] = (void*)&counter; break;
+        case KIND_TAIL: kargs[1] = (void*)&ta; kargs[2] = (void*)&counter; break;
+        case KIND_LARGE: kargs[1] = (void*)&wsp; kargs[2] = (void*)&wso; kargs[3] = (void*)&epoch; break;
+        case KIND_MARK:
+          hipLaunchKernelGGL(mark_kernel, dim3(grid), dim3(256), 0, st, k, (int)CTR_STATUS_TOO_LARGE);
+          return hipGetLastError();
+      }
       return hipLaunchKernel(ki->fn, dim3(grid), dim3((unsigned)ki->threads), kargs, ki->smem, st);
-    }});
-  }
-  if (plan->bin_count[BIN_TOO_LARGE] > 0) {
-    const int64_t cnt = plan->bin_count[BIN_TOO_LARGE];
-    k.order = ord + plan->bin_begin[BIN_TOO_LARGE];
-    k.n_bin = (int32_t)cnt;
-    guess(BIN_TOO_LARGE, lane_sched::CHAIN_MARK, cnt, 1);
-    chains.push_back({BIN_TOO_LARGE, false, [k, cnt](hipStream_t st) {
-      hipLaunchKernelGGL(mark_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, k, (int)CTR_STATUS_TOO_LARGE);
-      return hipGetLastError();
-    }});
-  }
-  // the small kernels start GATE_US after the others, where there are others (plan->gate)
-  if (plan->bin_count[BIN_SMALL2] > 0) {
-    const int64_t cnt = plan->bin_count[BIN_SMALL2];
-    const KernelInfo* ki;
-    rc = table_kernel(h, plan->bin_family[BIN_SMALL2], p.ndim, ii, plan->bin_slot[BIN_SMALL2], &ki);
-    if (rc) return rc;
-    int* counter = h->d_counter + 2;
-    k.order = ord + plan->bin_begin[BIN_SMALL2];
-    k.n_bin = (int32_t)cnt;
-    int64_t waves = cnt;   // (one wavefront per pair)
-    // A tail launch fits every pair of the 64-lane tier -- the close ones with two tiers, all of
-    // them with one: that tier has no launch of its own then.  (But for one tier of more than
-    // TAIL_PAIRS_WHOLE pairs, wide windows: the launch takes all but the close ones.)
-    const bool launch64 = plan->tail_own[0];
-    if (launch64 && plan->tail_fused) {
-      k.split = plan->d_front + 2 * BIN_SMALL2;
-      k.split_cap = INT32_MAX;
-      k.split_part = 3;
-    }
-    if (plan->pairs_split) {
-      // front_load_kernel has put the pairs closer than a quarter of the mask radius first and
-      // counted them (on the device): the 64-lane kernel takes exactly those, the 16-lane kernel,
-      // a chain of its own, the others -- which kernel fits a pair depends on the pair alone,
-      // not on the order of the batch.
-      const KernelInfo* kb;
-      rc = table_kernel(h, plan->bin_family[BIN_SMALL2], p.ndim, ii, SLOT_PAIRS16, &kb);
-      if (rc) return rc;
-      k.split = plan->d_front + 2 * BIN_SMALL2;
-      int* cbulk = h->d_counter + 3;
-      k.split_part = 2;
-      int64_t wb = (cnt + 3) / 4;
-      if (wb > 8192) wb = 8192;
-      guess(LAUNCH_PAIRS16, lane_sched::CHAIN_PAIRS16, cnt, 1);
-      chains.push_back({LAUNCH_PAIRS16, plan->gate, [k, kb, wb, cbulk](hipStream_t st) {
-        // (a little later still than the first tier, whose few wavefronts must not queue up
-        // behind the thousands of this one)
-        hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, st, (unsigned long long)GATE_US * 100ull);
-        void* kargs[] = {(void*)&k, (void*)&cbulk};
-        return hipLaunchKernel(kb->fn, dim3((unsigned)wb), dim3(WAVE), kargs, 0, st);
-      }});
-      k.split_part = 1;
-      if (waves > 2048) waves = 2048;   // persistent: a wavefront takes pair after pair
-    }
-    if (waves > 8192) waves = 8192;
-    if (launch64) guess(BIN_SMALL2, lane_sched::CHAIN_PAIRS64, cnt, 1);
-    if (launch64)
-      chains.push_back({BIN_SMALL2, plan->gate, [k, ki, waves, counter](hipStream_t st) {
-        void* kargs[] = {(void*)&k, (void*)&counter};
-        return hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st);
-      }});
-    k.split = nullptr;
-    k.split_part = 0;
-    k.split_cap = 0;
-  }
-  if (plan->bin_count[BIN_SMALL1] > 0) {
-    const int64_t cnt = plan->bin_count[BIN_SMALL1];
-    const KernelInfo* ki;
-    rc = table_kernel(h, plan->bin_family[BIN_SMALL1], p.ndim, ii, plan->bin_slot[BIN_SMALL1], &ki);
-    if (rc) return rc;
-    int* counter = h->d_counter + 1;
-    k.order = ord + plan->bin_begin[BIN_SMALL1];
-    k.n_bin = (int32_t)cnt;
-    int64_t waves = plan->bin_slot[BIN_SMALL1] == SLOT_SINGLES64 ? cnt : (cnt + 7) / 8;
-    if (waves > 8192) waves = 8192;
-    guess(BIN_SMALL1, lane_sched::CHAIN_SINGLES, cnt, 1);
-    chains.push_back({BIN_SMALL1, plan->gate, [k, ki, waves, counter](hipStream_t st) {
-      void* kargs[] = {(void*)&k, (void*)&counter};
-      return hipLaunchKernel(ki->fn, dim3((unsigned)waves), dim3(WAVE), kargs, 0, st);
     }});
   }
 
@@ -1148,18 +839,17 @@ int ctr_refine_batch_device(ctr_handle* h, const ctr_plan* plan, const ctr_batch
     FrontArgs fa;
     fa.nbins = NBINS;
     fa.keep_bin = BIN_SMALL1;
-    for (int bin = 0; bin < NBINS; ++bin) { fa.begin[bin] = (int)plan->bin_begin[bin]; fa.count[bin] = (int)plan->bin_count[bin]; }
+    for (int bin = 0; bin < NBINS; ++bin) { fa.begin[bin] = (int)rp.bin_begin[bin]; fa.count[bin] = (int)rp.bin_count[bin]; }
     HIP_TRY(h, hipMemsetAsync(plan->d_front, 0, sizeof(int) * 2 * NBINS, s));
     // the work counters of the small-kernel launches, here rather than in their chains: a
     // fill kernel queued behind the gate would wait for a slot on a machine already flooded
     HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int) * 8, s));
-    k.order = nullptr;   // (the arguments of a bin's launch have no meaning here)
-    k.n_bin = 0;
-    hipLaunchKernelGGL(front_load_kernel, dim3((unsigned)((plan->n_clusters + 255) / 256)), dim3(256), 0, s, k, fa,
+    // (base: no order, n_bin 0 -- the arguments of a bin's launch have no meaning here)
+    hipLaunchKernelGGL(front_load_kernel, dim3((unsigned)((plan->n_clusters + 255) / 256)), dim3(256), 0, s, base, fa,
                        plan->d_order, ord, plan->d_front, (int)plan->n_clusters);
   }
   HIP_TRY(h, hipEventRecord(h->ev_fork, s));
-  if (plan->gate) {
+  if (rp.gate) {
     hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(WAVE), 0, s, (unsigned long long)GATE_US * 100ull);
     HIP_TRY(h, hipEventRecord(h->ev_gate, s));
   }

@@ -1,6 +1,8 @@
 // kargs.h -- what the translation units of the engine share: kernel arguments and the
 // functions through which ctrefine.hip (host runtime) gets at the kernels compiled elsewhere.
 // The engine is split into several .hip files only so that they compile in parallel.
+// Which launches of a call get which KArgs::split* and TailArgs values is decided on the host, in
+// refine_plan.h (LaunchSpec); the sizes both sides share are in engine_dims.h.
 #ifndef CTREFINE_KARGS_H
 #define CTREFINE_KARGS_H
 
@@ -10,6 +12,7 @@
 #include <cstdint>
 
 #include "ctrefine.h"
+#include "engine_dims.h"
 
 struct KArgs {
   ctr_problem prob;
@@ -61,8 +64,7 @@ constexpr int LP_STRIDE = 40;   // >= 2 * 16 + 1 taps (CTR_MAX_NOISE_SIZE = 4)
 // workgroups share the entries order[ord_off[s] + 0 .. range): range = whole[s] where that is
 // positive (the bin's count: the tail launch fits the whole bin), else *close[s], the clusters
 // that front_load_kernel has put first and counted.  An empty segment has no workgroup and a null
-// count.
-constexpr int TAIL_SEGMENTS = 3;
+// count.  (TAIL_SEGMENTS: engine_dims.h)
 struct TailArgs {
   const int32_t* close[TAIL_SEGMENTS];
   int32_t ord_off[TAIL_SEGMENTS];

@@ -26,8 +26,8 @@ import clustertracking_amd as cta
 from clustertracking_amd import _abi, artificial
 from clustertracking_amd import constraints as cons
 
-MAXF = 64     # features per cluster of the small / block kernels (device_common.h)
-MAXNT = 8     # tiles of 16 columns of the block kernel (device_common.h)
+MAXF = 64     # features per cluster of the small / block kernels (engine_dims.h)
+MAXNT = 8     # tiles of 16 columns of the block kernel (engine_dims.h)
 GEOMS = ((2, True), (2, False), (3, True), (3, False))
 PROFILES = ('gauss', 'ring', 'disc', 'inv_series')
 INV_ORDER = 2                     # inv_series_2 fits every geometry (CTR_MAX_PARAMS)
