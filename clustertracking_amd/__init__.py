@@ -14,6 +14,7 @@ from .relocate import relocate_arrays, relocate_candidates
 from .find_link import find_link, find_link_arrays
 from .refine_com import refine_com, refine_com_arrays
 from .train import train_leastsq, train_arrays
+from .refine_global import refine_global_arrays, refine_global   # the function shadows the submodule, as vanhove does
 from .fitfunc import FitFunctions
 from .utils import ArrayReader, RefineException
 from . import constraints, artificial, link, motion, motion_ci, preprocessing
@@ -37,7 +38,7 @@ from .fit_error import fit_error_arrays, fit_error   # the function shadows the 
 link_df = link.link
 link_arrays = link.link_arrays
 
-__all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', 'find_clusters', 'grey_dilation', 'locate_maxima',
+__all__ = ['refine_leastsq', 'refine_arrays', 'train_leastsq', 'train_arrays', 'refine_global', 'refine_global_arrays', 'find_clusters', 'grey_dilation', 'locate_maxima',
            'characterize', 'characterize_arrays', 'locate', 'relocate_arrays', 'relocate_candidates', 'find_link', 'find_link_arrays', 'refine_com', 'refine_com_arrays', 'lowpass', 'bandpass', 'preprocess', 'preprocessing',
            'percentile_threshold', 'where_close', 'drop_close', 'link', 'link_df', 'link_arrays', 'FitFunctions', 'constraints',
            'artificial', 'ArrayReader', 'RefineException', 'prepare_batch',

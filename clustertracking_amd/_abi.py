@@ -258,6 +258,30 @@ class Train(C.Structure):
     ]
 
 
+REFINE_GLOBAL_MAX_GLOBALS, REFINE_GLOBAL_MAX_COLUMNS = 8, 48
+
+
+class RefineGlobal(C.Structure):
+    """``ctr_refine_global`` (include/ctrefine.h): shared and per-feature parameters in one problem."""
+    _fields_ = [
+        ('ndim', C.c_int32), ('isotropic', C.c_int32), ('fit_function', C.c_int32),
+        ('n_params', C.c_int32), ('modes', C.c_int32 * MAX_PARAMS), ('radius', C.c_int32 * MAX_NDIM),
+        ('frame_dtype', C.c_int32), ('solver_maxiter', C.c_int32), ('max_iter', C.c_int32),
+        ('max_features', C.c_int32), ('max_locals', C.c_int32), ('check_every', C.c_int32),
+        ('reserved0', C.c_int32),
+        ('n_frames', C.c_int64), ('shape', C.c_int64 * MAX_NDIM),
+        ('n_problems', C.c_int64), ('n_clusters', C.c_int64), ('n_features', C.c_int64),
+        ('residual_factor', C.c_double), ('max_rms_dev', C.c_double), ('max_shift', C.c_double),
+        ('xtol', C.c_double), ('ftol', C.c_double),
+        ('frames', C.c_void_p), ('params', C.c_void_p), ('feat_offset', C.c_void_p),
+        ('frame_index', C.c_void_p), ('problem_offset', C.c_void_p),
+        ('start', C.c_void_p), ('low', C.c_void_p), ('high', C.c_void_p),
+        ('local_start', C.c_void_p), ('local_low', C.c_void_p), ('local_high', C.c_void_p),
+        ('params_out', C.c_void_p), ('globals', C.c_void_p), ('cost', C.c_void_p), ('status', C.c_void_p),
+        ('n_rounds', C.c_void_p), ('n_iter', C.c_void_p),
+    ]
+
+
 TRACKS_PAIRS, TRACKS_COMPONENTS = 0, 1                        # ctr_cluster_tracks.phase
 TRACKS_OK, TRACKS_BAD_TABLE, TRACKS_ROUNDS = 0, 1, 2           # status[0] of both calls
 TRACKS_NO_KEY = 0x7fffffffffffffff

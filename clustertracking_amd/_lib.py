@@ -59,6 +59,8 @@ SIGNATURES = {
     'ctr_find_link_device': _stage(_abi.FindLink),
     'ctr_refine_com_device': _stage(_abi.RefineCom),
     'ctr_train_device': _stage(_abi.Train),
+    'ctr_refine_global_device': _stage(_abi.RefineGlobal),
+    'ctr_refine_global_plan': (C.c_int, [_P(_abi.RefineGlobal), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
     'ctr_cluster_tracks_device': _stage(_abi.ClusterTracks),
     'ctr_cluster_tracks_plan': (C.c_int, [_P(_abi.ClusterTracks), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
     'ctr_track_positions_device': _stage(_abi.TrackPositions),
@@ -256,6 +258,16 @@ def contacts_plan(desc):
         msg = (lib.ctr_last_error(None) or b'').decode()
         raise (ValueError if rc == _abi.ERR_INVALID else NotImplementedError)(msg)
     return ContactsPlan(scratch.value, tuple(tiles), tuple(grids))
+
+
+RefineGlobalPlan = collections.namedtuple('RefineGlobalPlan', 'scratch_bytes launches_per_iteration tiles row_doubles')
+
+
+def refine_global_plan(desc):
+    """The launch decision of ``ctr_refine_global_device`` (``ctr_refine_global_plan``, no device
+    needed): ``RefineGlobalPlan(scratch_bytes, launches_per_iteration, tiles, row_doubles)``;
+    ``ValueError`` / ``NotImplementedError`` as the call itself."""
+    return RefineGlobalPlan(*_plan('ctr_refine_global_plan', desc, C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()))
 
 
 def refine_prepare_plan(desc):
@@ -485,6 +497,7 @@ for _name, _symbol, _too_large in (
         ('find_link_device', 'ctr_find_link_device', False),
         ('refine_com_device', 'ctr_refine_com_device', False),
         ('train_device', 'ctr_train_device', False),
+        ('refine_global_device', 'ctr_refine_global_device', False),
         ('cluster_tracks_device', 'ctr_cluster_tracks_device', False),
         ('track_positions_device', 'ctr_track_positions_device', False),
         ('drift_device', 'ctr_drift_device', False),

@@ -143,6 +143,7 @@ struct ctr_handle {
   // ctr_link_device, ctr_find_link_device and ctr_find_link_refine_device; ctr_diffusion_device and ctr_diffusion_ci_device (partial sums, rows, statistics)
   Scratch link, motion;
   Scratch train;   // ctr_train_device: frame maxima, partial sums, solver state
+  Scratch global;  // ctr_refine_global_device: frame maxima, a row per cluster, Schur and evaluation tables, solver state
   Scratch tracks;  // ctr_cluster_tracks_device: labels, member counts, the words of the rounds
   Scratch prepare; // ctr_refine_prepare_device: scaled positions, member counts, ranks, clusters per frame
   Scratch drift;   // ctr_drift_device: the step of every frame
@@ -531,7 +532,7 @@ void ctr_destroy(ctr_handle* h) {
   // the last refine call, wherever its chains run, uses the handle's scratch until ev_done
   if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape, &h->resid, &h->contacts, &h->fiterr}) {
+  for (Scratch* sc : {&h->buf, &h->enc, &h->fmax, &h->link, &h->motion, &h->train, &h->global, &h->tracks, &h->prepare, &h->drift, &h->msd, &h->pcf, &h->nbr, &h->twopt, &h->shape, &h->resid, &h->contacts, &h->fiterr}) {
     if (sc->ptr) (void)hipFree(sc->ptr);
     if (sc->event) (void)hipEventDestroy(sc->event);
   }
@@ -1147,6 +1148,24 @@ int ctr_refine_com_device(ctr_handle* h, const ctr_refine_com* c, void* hip_stre
 
 int ctr_train_device(ctr_handle* h, const ctr_train* t, void* hip_stream) {
   return run_stage("ctr_train_device", h, &ctr_handle::train, t, hip_stream, ctr_train_launch);
+}
+
+int ctr_refine_global_device(ctr_handle* h, const ctr_refine_global* d, void* hip_stream) {
+  return run_stage("ctr_refine_global_device", h, &ctr_handle::global, d, hip_stream, ctr_refine_global_launch);
+}
+
+int ctr_refine_global_plan(const ctr_refine_global* d, int64_t* scratch_bytes, int32_t* launches_per_iteration,
+                           int32_t* tiles, int64_t* row_doubles) {
+  const char* msg = "";
+  ctr_global_launch_plan plan = {};
+  StageRun run = {STAGE_CHECK_SCALARS, nullptr, nullptr, 0, STAGE_MAX_GRID};
+  const int rc = ctr_refine_global_launch(d, &run, &msg, &plan);
+  if (rc != CTR_OK) return fail(nullptr, rc, std::string("ctr_refine_global_plan: ") + msg);
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  if (launches_per_iteration) *launches_per_iteration = plan.launches_per_iteration;
+  if (tiles) *tiles = plan.tiles;
+  if (row_doubles) *row_doubles = plan.row_doubles;
+  return CTR_OK;
 }
 
 int ctr_cluster_tracks_device(ctr_handle* h, const ctr_cluster_tracks* c, void* hip_stream) {

@@ -212,6 +212,14 @@ struct FindLinkRefine {
 int ctr_find_link_refine_launch(const FindLinkRefine* d, StageRun* stage, const char** msg);
 // training of shared fit parameters (train_kernels.h; scratch: frame maxima, partials, solver state)
 int ctr_train_launch(const ctr_train* t, StageRun* stage, const char** msg);
+// shared and per-feature parameters in one problem (global_kernels.h; scratch: frame maxima, a row per
+// cluster, the Schur and evaluation tables, solver state, mask centres): the launch decision goes
+// to *plan (may be null)
+struct ctr_global_launch_plan {
+  long long scratch_bytes, row_doubles;
+  int launches_per_iteration, tiles;
+};
+int ctr_refine_global_launch(const ctr_refine_global* t, StageRun* stage, const char** msg, ctr_global_launch_plan* plan);
 // cluster tracks (cluster_track_kernels.h; scratch: labels, member counts, the words of the rounds):
 // the round bound goes to *plan (may be null)
 struct ctr_tracks_plan {

@@ -82,7 +82,8 @@ def _check_options(ndim, diameter, separation, fit_function, param_mode, constra
         raise NotImplementedError(
             "param_mode 'global' couples all features into one problem "
             "(reference refine.py:319-332) and is not supported by the MI355X "
-            "engine; train_leastsq fits shared parameters with everything else constant")
+            "engine; train_leastsq fits shared parameters with everything else constant"
+            "; ct.refine_global fits them together with per-feature and per-cluster parameters")
     if not np.all(modes <= 3):
         raise NotImplementedError("param modes 'particle'/'frame' are not "
                                   "implemented (reference refine.py:339-340)")

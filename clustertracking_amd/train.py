@@ -7,7 +7,8 @@ by all features (``param_mode='global'``).  With nothing varying per feature the
 G shared values alone and the windows never move, so one iteration is a sum of a G x G normal
 matrix over all pixels of all clusters and a small bounded Levenberg-Marquardt step: the engine
 runs that, P independent problems per call.  General global mode -- per-feature variables beside
-shared ones -- stays out of scope (``refine_leastsq`` raises).  There is no CPU fallback.
+shared ones -- is ``refine_global`` (``refine_leastsq`` and this module refuse it).  There is no CPU
+fallback.
 """
 from collections import namedtuple
 

@@ -1012,7 +1012,8 @@ int ctr_diffusion_ci_plan(const ctr_diffusion_ci* d, int32_t* rows_in_lds, int64
  * (param_mode 'global').  With every other parameter constant the unknowns of a
  * problem are its G shared values alone (1 to 8), the windows never move, and the objective is a
  * sum over clusters.  General global mode (per-feature variables beside shared ones: an arrowhead
- * system over all clusters) stays refused by ctr_validate_problem.
+ * system over all clusters) is ctr_refine_global_device, below; ctr_validate_problem, and with it
+ * ctr_refine_batch, and this call still refuse it.
  * A call holds P independent problems; problem p owns the clusters [problem_offset[p],
  * problem_offset[p + 1]), cluster c the features [feat_offset[c], feat_offset[c + 1]) of `params`
  * and the frame frame_index[c].  For one problem:
@@ -1104,6 +1105,119 @@ typedef struct ctr_train {
   int32_t* n_iter;                 /* [P] out */
 } ctr_train;
 int ctr_train_device(ctr_handle* h, const ctr_train* t, void* hip_stream);
+
+/* ---- shared and per-feature parameters in one problem: general global mode (ABI 8, additions) ----
+ * What the reference's refine_leastsq does with a param_mode 'global' (refine.py:317-332): the G
+ * global columns are ONE value for all features of a problem, fitted together with whatever varies
+ * per feature ('var') or per cluster ('cluster').  Training (above) is the case without locals.
+ * A call holds P independent problems laid out as ctr_train lays them out (problem_offset,
+ * feat_offset, frame_index, params [N, n_params]).  For one problem:
+ *   objective: windows, union boxes, masks, P_c, the NaN-pixel rule, bg_c (the background of the
+ *     cluster's first feature) and the ONE norm per problem are those of the training rule to the
+ *     letter; the masks are built on the mask centres of the round, the model on the trial positions;
+ *   modes per column: CTR_MODE_CONST, _VAR, _CLUSTER, _GLOBAL.  At least one column is global
+ *     (else CTR_ERR_INVALID); background, signal, the size column(s) and the profile's columns may
+ *     be; a global position is CTR_ERR_UNSUPPORTED; the background is never VAR (fitfunc.py:389-392);
+ *   variables: the G <= 8 global columns, in column order, are the shared variables.  The locals of
+ *     cluster c, L_c of them, in column order: a CLUSTER column one entry, a VAR column one entry per
+ *     feature of the cluster in row order.  L_c = 0 is allowed; a problem whose clusters all have
+ *     L_c = 0 is a training problem;
+ *   start and bounds are the caller's (refine.py:361-364, fitfunc.py:535-558): start, low, high
+ *     [P, G] as in training; local_start, local_low, local_high [C, max_locals], row c holding the
+ *     L_c locals of cluster c in the order above (a VAR entry its own value and bounds, a CLUSTER
+ *     entry the mean over the cluster's rows, the min of the lows and the max of the highs).  The
+ *     start is clipped into the box; low > high anywhere fails the problem (NO_CONVERGENCE);
+ *   rounds (refine.py:365-388): up to max_iter window rounds.  Every round minimises from the
+ *     call's start vector with the call's bounds; only the mask centres move, to the last round's
+ *     positions.  The rounds end when every feature of the problem is less than max_shift from
+ *     its mask centre (squared distance < max_shift^2), as ctr_refine_batch does per cluster; after
+ *     the last round cost = sqrt(F / residual_factor);
+ *   minimiser: the training's bounded Levenberg-Marquardt on the whole vector, everything as written
+ *     there: Gauss-Newton matrix, Marquardt scaling by its diagonal, active set on the box,
+ *     projection, predicted decrease of the full model at the projected step, Nielsen's update,
+ *     mu0 = 1, the stopping tests and the flat-trial rule (the projected gradient over locals and
+ *     globals).  The damped matrix is an arrowhead -- a block A_c + mu D_c per cluster, its coupling
+ *     B_c to the G shared columns, the G x G corner -- and the step is solved in four stages: the
+ *     free locals of every cluster are eliminated with a Cholesky in the cluster's workgroup; the
+ *     Schur rows G_c - B_c^T (A_c + mu D_c)^-1 B_c and the reduced gradients are summed per problem
+ *     in a fixed order; the G x G system is solved in the problem's workgroup; every cluster
+ *     back-substitutes and projects.  A block or a corner that is not positive definite rejects the
+ *     step (more damping) without a pixel pass;
+ *   result: params_out [N, n_params] (the fitted columns of the problem's rows, every other entry
+ *     as in params), globals [P, G], cost [P], status [P], n_rounds [P], n_iter [P] (iterations of
+ *     all rounds).  A failed problem leaves its rows as they came in and has NaN cost and globals
+ *     (refine.py:408-412); statuses as in training; TOO_LARGE: a cluster of more than 64 features,
+ *     of more than max_locals locals or of more than 48 columns (L_c + G + 1).  A failed problem
+ *     never stops a kernel and leaves the other problems' bytes alone.
+ * Per iteration four kernels run on the stream (global_kernels.h): one workgroup per cluster
+ * back-substitutes and builds the rows [J_local | J_global | r] of its window in LDS row tiles,
+ * contracted with v_mfma_f64_16x16x4_f64 (A_c, B_c, the cluster's part of the corner, both gradients
+ * and F_c out of one contraction); one workgroup per problem judges the trial; one wavefront per
+ * cluster factors and forms its Schur row; one workgroup per problem solves the corner.  A cluster
+ * keeps A_c, B_c, g_c of the accepted point in a row of the handle's scratch sized by max_locals, so
+ * a rejected trial costs no second pixel pass.  The kernel boundary is the only synchronisation; no
+ * floating-point atomics; every sum in an order fixed by the cluster alone (its pixels go in tiles of
+ * 64 to four virtual waves, tile k to k mod 4, whose partial sums are added in their order, however
+ * many wavefronts and column tiles the call's largest cluster makes the kernel use): the same bytes
+ * alone, in a batch with any other problems, on any stream and for any check_every.  The workgroups of a finished problem return
+ * at once.
+ * The host queues iterations and reads one word every check_every >= 1 iterations (the count of
+ * finished problems; a problem re-windows on the device); the call returns with the stream
+ * synchronised.  There is no blind queue.
+ * max_features and max_locals are the caller's statement; the device checks every cluster again.
+ * problem_offset must rise from 0 to C, as for ctr_train: the device checks each problem's own
+ * range, not that the ranges of different problems are disjoint; overlapping ranges are memory-safe
+ * and give undefined results with a status of OK.
+ * ctr_refine_global_plan (no device needed) gives the scratch bytes, the launches per iteration
+ * (4), the 16-column tiles of a row (1 .. 3) and the doubles of a cluster's scratch row.
+ * The descriptor is checked before the handle.  Device pointers. */
+#define CTR_REFINE_GLOBAL_MAX_GLOBALS 8
+#define CTR_REFINE_GLOBAL_MAX_COLUMNS 48
+typedef struct ctr_refine_global {
+  int32_t ndim;                    /* 2 or 3 */
+  int32_t isotropic;               /* 1: one 'size' column; 0: one per axis */
+  int32_t fit_function;            /* CTR_FIT_* */
+  int32_t n_params;                /* as ctr_problem.n_params */
+  int32_t modes[CTR_MAX_PARAMS];   /* CTR_MODE_* per column */
+  int32_t radius[CTR_MAX_NDIM];    /* mask radius per axis, >= 1 */
+  int32_t frame_dtype;             /* CTR_DTYPE_* */
+  int32_t solver_maxiter;          /* 1 .. 10000: iterations of one round (default 100) */
+  int32_t max_iter;                /* 1 .. 1000: window rounds (refine.py:365; default 10) */
+  int32_t max_features;            /* features of the largest cluster, <= 64 */
+  int32_t max_locals;              /* locals of the largest cluster; max_locals + G + 1 <= 48 */
+  int32_t check_every;             /* >= 1: iterations between two looks at the finished count */
+  int32_t reserved0;
+  int64_t n_frames;
+  int64_t shape[CTR_MAX_NDIM];     /* (z,) y, x */
+  int64_t n_problems;              /* P */
+  int64_t n_clusters;              /* C */
+  int64_t n_features;              /* N */
+  double residual_factor;          /* > 0 (default 1e5) */
+  double max_rms_dev;              /* refine.py:391 (default 1) */
+  double max_shift;                /* refine.py:384 (default 1) */
+  double xtol;                     /* <= 0 -> 1e-9 */
+  double ftol;                     /* <= 0 -> 1e-14 */
+  const void* frames;              /* [n_frames, *shape] */
+  const double* params;            /* [N, n_params] */
+  const int32_t* feat_offset;      /* [C + 1] */
+  const int32_t* frame_index;      /* [C] */
+  const int32_t* problem_offset;   /* [P + 1] offsets into the clusters */
+  const double* start;             /* [P, G] */
+  const double* low;               /* [P, G], -inf = none */
+  const double* high;              /* [P, G], +inf = none */
+  const double* local_start;       /* [C, max_locals] */
+  const double* local_low;
+  const double* local_high;
+  double* params_out;              /* [N, n_params] out */
+  double* globals;                 /* [P, G] out */
+  double* cost;                    /* [P] out */
+  int32_t* status;                 /* [P] out */
+  int32_t* n_rounds;               /* [P] out */
+  int32_t* n_iter;                 /* [P] out */
+} ctr_refine_global;
+int ctr_refine_global_device(ctr_handle* h, const ctr_refine_global* d, void* hip_stream);
+int ctr_refine_global_plan(const ctr_refine_global* d, int64_t* scratch_bytes, int32_t* launches_per_iteration,
+                           int32_t* tiles, int64_t* row_doubles);
 
 /* ---- cluster tracks: which particles form one cluster over time (ABI 8, additions) ----
  * The step between the linker and the motion stage: ctr_link_device / ctr_find_link_device give every
